@@ -14,7 +14,12 @@ Launch forms (both work, and both run the ranks in the same environment -- rank_
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N ...                    (the driver's form)
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0: the headline and its roofline, kept to a few KB so that a reader of the tail of stdout
+can parse it.  The extra measurements of a --gpus 1 run (spectral-only, other windows, live cadence, ...) go to stderr as one
+line `bench.py extras: {...}`.
+
+--dump-outputs DIR writes what the timed path returned in its last timed step (raw and smoothed feature vectors) as
+DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import csv
@@ -320,16 +325,19 @@ def stream_bench(fx, args, C, T, N, device):
     for _ in range(args.steps):
         step()
     while st.in_flight():
-        st.collect(want_raw=False)
+        last = st.collect(want_raw=False)
     dt = time.perf_counter() - t0
     frames = C * T * args.steps
     in_bytes = hops.nbytes * args.steps
+    extra = {}
+    if args.dump_outputs:
+        extra["dumped_outputs"] = dump_outputs(args.dump_outputs, {"smoothed": last[1]})
     print(json.dumps({"metric": "frames/sec, streaming ingest (host hops -> pinned ring -> GPU -> host features)",
                       "value": frames / dt, "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                       "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "dtype": "f16" if args.fp16 else "f32",
                       "data": "synthetic", "pcie_inclusive": True, "host_to_device_GBps": in_bytes / dt / 1e9,
                       "config": {"workload": "%d channels x %d hops/batch x %d-pt windows (%d samples/hop), 3-slot pinned ring" % (C, T, N, N // 2),
-                                 "channels": C, "hops_per_batch": T, "window": N}}), flush=True)
+                                 "channels": C, "hops_per_batch": T, "window": N}, **extra}), flush=True)
 
 
 def _free_port():
@@ -445,13 +453,45 @@ def build_parser():
     ap.add_argument("--rank-timeout", type=int, default=600, help="seconds a rank may spend joining the group / communicator or in one barrier before it gives up")
     ap.add_argument("--analysers", default="both", choices=["both", "spectral", "harmonic"],
                     help="--pmc-child only (tools/pmc_quick.py): which of the reference's two analysers the profiled context constructs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32; rank 0's shard; at most 64 MB, "
+                         "a fixed seeded sample of channels above that, their indices in DIR/channels.npy)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--input-file", default=None, help=argparse.SUPPRESS)
     return ap
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Writes out_dir/<name>.npy (float32) for every [channels][...] array in `arrays` (torch tensors or ndarrays, one channel count).
+    Above DUMP_LIMIT_BYTES in all, the same seeded sample of channels is taken from each and its indices go to channels.npy (float64).
+    Returns a short record for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    channels = next(iter(arrays.values())).shape[0]
+    per_channel = sum(4 * math.prod(a.shape[1:]) for a in arrays.values())
+    keep = None
+    room = DUMP_LIMIT_BYTES - 4096                                 # (the .npy headers)
+    if per_channel * channels > room:
+        n = max(1, (room - 8 * channels) // per_channel)
+        keep = np.sort(np.random.default_rng(seed).choice(channels, size=min(n, channels), replace=False))
+        np.save(os.path.join(out_dir, "channels.npy"), keep.astype(np.float64))
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            import torch
+            a = (a if keep is None else a.index_select(0, torch.from_numpy(keep).to(a.device))).detach().cpu().numpy()
+        elif keep is not None:
+            a = a[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
+    return {"dir": out_dir, "files": sorted(list(arrays) + ([] if keep is None else ["channels"])),
+            "channels": channels if keep is None else int(keep.size), "sampled": keep is not None}
+
+
 def main():
     args = build_parser().parse_args()
+    if args.steps < 1:
+        build_parser().error("--steps must be at least 1")
     rank_environment()                      # before anything can start the HIP runtime (both launch forms)
     if args.pmc_child:
         return pmc_child(args)
@@ -571,6 +611,9 @@ def rank_main(args, engine, rank, world):
     barrier()
     dt = time.perf_counter() - t0
     frame_ms, epi_ms, calls = an.profile_end()
+    dumped = None
+    if args.dump_outputs and rank == 0:             # before anything else reuses raw / sm
+        dumped = dump_outputs(args.dump_outputs, {"raw": raw, "smoothed": sm})
 
     per_rank = None
     if collective:
@@ -671,9 +714,12 @@ def rank_main(args, engine, rank, world):
         }
         if per_rank is not None:
             out["per_rank"] = per_rank
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        side = None
         if world == 1 and not args.no_extra and not args.debug_collective and engine.name == "gpu":
-            extras(out, args, engine, fx, an, frames, raw, sm, N, count, T, launch_bytes, avg_launch_s,
-                   spectral_input=input_file if (want_pmc and not under_profiler()) else None)
+            side = extras(out, args, engine, fx, an, frames, raw, sm, N, count, T, launch_bytes, avg_launch_s,
+                          spectral_input=input_file if (want_pmc and not under_profiler()) else None)
         if input_file:
             try:
                 os.unlink(input_file)
@@ -686,6 +732,8 @@ def rank_main(args, engine, rank, world):
                 out["cpu_baseline"] = {"error": str(e)}
         else:
             out["cpu_baseline"] = None
+        if side is not None:
+            print("bench.py extras: " + json.dumps(side), file=sys.stderr, flush=True)
 
     if collective:
         dist.barrier()
@@ -696,17 +744,18 @@ def rank_main(args, engine, rank, world):
 
 
 def extras(out, args, engine, fx, an, frames, raw, sm, N, count, T, launch_bytes, avg_launch_s, spectral_input=None):
-    """Side measurements on the same line (never `value`).  Each one is guarded: a failure is reported in its own field
-    and the headline line still comes out."""
+    """Side measurements (never `value`), returned as one dict for stderr; `out` (the headline) is only read.  Each one is
+    guarded: a failure is reported in its own field and the headline line still comes out."""
     import torch
     extra_steps = 10
     dev = engine.device
+    side = {}
 
     def guarded(name, fn):
         try:
-            out[name] = fn()
+            side[name] = fn()
         except Exception as e:
-            out[name] = {"error": "%s: %s" % (type(e).__name__, e)}
+            side[name] = {"error": "%s: %s" % (type(e).__name__, e)}
 
     def spectral_only():
         # BASELINE configs[1] read literally is the spectral analyser alone ("fused window + FFT + magnitude +
@@ -1303,6 +1352,7 @@ def extras(out, args, engine, fx, an, frames, raw, sm, N, count, T, launch_bytes
     for name, fn in table:
         if only is None or name in only:
             guarded(name, fn)
+    return side
 
 
 if __name__ == "__main__":

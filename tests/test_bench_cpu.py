@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -139,3 +140,46 @@ def test_no_nested_profiler_children():
     assert bench.under_profiler({"LD_PRELOAD": "/opt/rocm/lib/librocprofiler-sdk-tool.so"})
     assert bench.under_profiler({"ROCPROF_OUTPUT_PATH": "/tmp/x"})
     assert bench.under_profiler({"ROCP_TOOL_LIBRARIES": "/opt/rocm/lib/rocprofiler-sdk/librocprofiler-sdk-tool.so"})
+
+
+def test_dump_outputs_writes_the_last_timed_step_and_steps_sets_the_timed_calls(tmp_path):
+    """--dump-outputs DIR: raw / smoothed of the LAST timed step as DIR/<name>.npy (float32), on inputs that are the same from run to
+    run; --steps is the number of timed calls.  rank_main on CPU with the oracle standing in for the GPU analyser."""
+    from test_sharded_cpu import _OracleEngine
+    from oracle import fx_oracle as fo
+    from importlib import import_module
+    fx = import_module("feature-extractor_amd")
+    C, T, N, steps, warmup = 3, 4, 1024, 3, 1
+    args = bench.build_parser().parse_args(["--channels-per-gpu", str(C), "--frames", str(T), "--steps", str(steps), "--warmup", str(warmup),
+                                            "--no-cpu-baseline", "--no-extra", "--no-pmc", "--dump-outputs", str(tmp_path / "out")])
+    d = bench.rank_main(args, _OracleEngine(), 0, 1)
+    assert d["steps"] == steps and d["roofline"]["launches_timed"] == steps and d["ms_per_step"] > 0
+    assert d["dumped_outputs"]["files"] == ["raw", "smoothed"] and not d["dumped_outputs"]["sampled"]
+    assert len(json.dumps(d)) < 4096                                  # a line a reader of the tail of stdout can parse whole
+    frames = fx.synth.frames(C, T, N)
+    want = [fo.Channel(N) for _ in range(C)]
+    for _ in range(warmup + steps):
+        got = [ch.process_frames(frames[c]) for c, ch in enumerate(want)]
+    for k, name in enumerate(("raw", "smoothed")):
+        a = np.load(str(tmp_path / "out" / (name + ".npy")))
+        assert a.dtype == np.float32 and a.shape == (C, T, 12)
+        assert np.array_equal(a, np.stack([g[k] for g in got]), equal_nan=True), name
+
+
+def test_dump_outputs_samples_channels_above_the_limit(tmp_path, monkeypatch):
+    """Above the size limit a fixed, seeded sample of channels is written (the same one every run), with its indices."""
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)
+    x = np.arange(1000 * 50 * 12, dtype=np.float32).reshape(1000, 50, 12)
+    recs = [bench.dump_outputs(str(tmp_path / k), {"raw": x, "smoothed": -x}) for k in ("a", "b")]
+    assert recs[0]["sampled"] and 0 < recs[0]["channels"] < 1000 and recs[0]["files"] == ["channels", "raw", "smoothed"]
+    total = sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a")))
+    assert total <= 1 << 20
+    keep = np.load(str(tmp_path / "a" / "channels.npy"))
+    assert keep.dtype == np.float64 and np.array_equal(keep, np.load(str(tmp_path / "b" / "channels.npy")))
+    raw = np.load(str(tmp_path / "a" / "raw.npy"))
+    assert raw.dtype == np.float32 and np.array_equal(raw, x[keep.astype(np.int64)])
+
+
+def test_steps_below_one_is_refused():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert p.returncode == 2 and "--steps" in p.stderr

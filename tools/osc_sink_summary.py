@@ -1,8 +1,10 @@
-"""profiles/rNN_osc_sink.txt from a bench line:  python tools/osc_sink_summary.py profiles/r06_bench.json > profiles/r06_osc_sink.txt"""
+"""profiles/rNN_osc_sink.txt from a bench line:  python tools/osc_sink_summary.py profiles/r06_bench.json > profiles/r06_osc_sink.txt
+(or from bench.py's stderr, where the extras line `bench.py extras: {...}` carries `osc_sink` since the result line was cut to the headline)"""
 import json
 import sys
 
-d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
+PREFIX = "bench.py extras: "
+d = json.loads([l[len(PREFIX):] if l.startswith(PREFIX) else l for l in open(sys.argv[1]) if l.startswith(("{", PREFIX))][-1])
 o = d["osc_sink"]
 out = ["The OSC sink at scale (bench.py extra `osc_sink`, %s; ref OSCFeatureAnalysisOutput.h:84-113,133, AnalyserTrackController.h:22-23)" % sys.argv[1], "",
        o["loopback"], "bar: " + o["bar"], "",
