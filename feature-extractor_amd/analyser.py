@@ -105,6 +105,23 @@ class BatchAnalyser:
         fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_uint], ctypes.c_int
         capi.check(fn(self._h, int(bits)))
 
+    def last_launches(self):
+        """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
+        (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc)."""
+        fn = self._lib.fx_last_launches_internal
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int], ctypes.c_int
+        cap = capi.LAUNCH_RECORD_CAP
+        buf = (ctypes.c_int * (cap * len(capi.LAUNCH_FIELDS)))()
+        n = fn(self._h, buf, cap)
+        if n > cap:
+            raise RuntimeError("the last call made %d launches; the record keeps %d" % (n, cap))
+        out = []
+        for i in range(n):
+            rec = dict(zip(capi.LAUNCH_FIELDS, buf[i * len(capi.LAUNCH_FIELDS):(i + 1) * len(capi.LAUNCH_FIELDS)]))
+            rec["kind"] = capi.LAUNCH_KINDS[rec["kind"]]
+            out.append(rec)
+        return out
+
     def sync(self):
         capi.check(self._lib.fx_sync(self._h))
 

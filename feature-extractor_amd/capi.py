@@ -35,6 +35,11 @@ EXPORTS = ["fx_create", "fx_destroy", "fx_reset_state", "fx_set_sample_rate", "f
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
 MAX_UNITS = 24
+# fx_last_launches_internal (csrc/fx_kernels.h, tests only): struct fx_launch_record, field by field, and FX_LAUNCH_* by number
+LAUNCH_FIELDS = ["kind", "window", "analysers", "T", "direct_state", "block_mode", "num_chunks", "ch_per_wg", "waves_per_ch", "hop_pairs",
+                 "ep_T", "out_stride", "ep_form", "reblock"]
+LAUNCH_KINDS = {1: "frame", 2: "frame_tail", 3: "hop", 4: "hop_pair", 5: "pair", 6: "epilogue", 7: "reblock", 8: "osc"}
+LAUNCH_RECORD_CAP = 8
 
 
 class OscSenderStats(ctypes.Structure):

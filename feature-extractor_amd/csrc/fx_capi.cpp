@@ -230,6 +230,15 @@ extern "C" fx_status fx_set_tuning_internal(fx_context* c, unsigned test_hooks)
     return FX_OK;
 }
 
+// tests only (csrc/fx_kernels.h; not in include/fx.h)
+extern "C" int fx_last_launches_internal(fx_context* c, fx_launch_record* out, int cap)
+{
+    if (!c) return 0;
+    const int kept = c->num_launches < FX_LAUNCH_RECORD_CAP ? c->num_launches : FX_LAUNCH_RECORD_CAP;
+    for (int i = 0; i < kept && i < cap && out; i++) out[i] = c->launches[i];
+    return c->num_launches;
+}
+
 // A frame-kernel work unit that gave up waiting for its predecessor's flux state stores 1 to c->h_err (pinned host
 // memory).  Sticky: every synchronising entry point reports it until fx_reset_state.
 fx_status fx_check_device_error(fx_context* c)
@@ -252,8 +261,36 @@ struct Step {
     bool hop_pairs = false; // a one-frame call through fx_hop_pair_kernel (six wavefronts per channel) instead of fx_hop_kernel (three)
 };
 
-hipError_t launch_frames(const fx_context* c, const Step& st)
+// The launch record (fx_last_launches_internal): a handful of host stores per launch; each entry point that launches starts it anew.
+void begin_launches(fx_context* c) { if (c) c->num_launches = 0; }
+fx_launch_record* note_launch(fx_context* c, int kind, int analysers)
 {
+    const int i = c->num_launches++;
+    if (i >= FX_LAUNCH_RECORD_CAP) return nullptr;
+    fx_launch_record& r = c->launches[i];
+    r = fx_launch_record{};
+    r.kind = kind;
+    r.window = c->N;
+    r.analysers = analysers;
+    return &r;
+}
+void note_step(fx_context* c, int kind, const Step& st)
+{
+    fx_launch_record* r = note_launch(c, kind, st.analysers);
+    if (!r) return;
+    const bool hop = kind == FX_LAUNCH_HOP || kind == FX_LAUNCH_HOP_PAIR;
+    if (kind != FX_LAUNCH_EPILOGUE) {
+        r->T = st.fp.T; r->direct_state = st.fp.direct_state; r->block_mode = st.fp.block_mode;
+        if (!hop) { r->num_chunks = st.fp.num_chunks; r->ch_per_wg = st.fp.ch_per_wg; r->waves_per_ch = st.fp.waves_per_ch; }
+        else r->hop_pairs = st.hop_pairs ? 1 : 0;
+    }
+    if (kind != FX_LAUNCH_FRAME && kind != FX_LAUNCH_PAIR) { r->ep_T = st.ep.T; r->out_stride = st.ep.out_stride; }
+    if (kind == FX_LAUNCH_EPILOGUE) r->ep_form = fxk::epilogue_form(st.ep);
+}
+
+hipError_t launch_frames(fx_context* c, const Step& st)
+{
+    note_step(c, st.pair ? FX_LAUNCH_PAIR : FX_LAUNCH_FRAME, st);
     return st.pair ? fxk::launch_pair_kernel(c->N, st.fp, c->stream) : fxk::launch_frame_kernel(c->N, st.fp, st.analysers, c->stream);
 }
 
@@ -536,6 +573,7 @@ fx_status run(fx_context* c, const void* in, int T, int sample_format, int in_ki
         if (one_hop) {
             const fxk::HopSignal none = {nullptr, nullptr, 0u, 0u, nullptr};
             if (first) FX_EV(e0);
+            note_step(c, step.hop_pairs ? FX_LAUNCH_HOP_PAIR : FX_LAUNCH_HOP, step);
             HIP_TRY(fxk::launch_hop_kernel(c->N, step.fp, step.ep, none, c->stream, step.hop_pairs));
             if (last) { FX_EV(e1); FX_EV(e2); }
         } else {
@@ -551,11 +589,13 @@ fx_status run(fx_context* c, const void* in, int T, int sample_format, int in_ki
             const bool one_launch = step.fp.direct_state && fxk::frame_tail_kernel_available(c->N) &&
                                     ((c->test_hooks & FX_HOOK_TAIL_ALWAYS_FUSED) || (!(c->test_hooks & FX_HOOK_TAIL_NEVER_FUSED) && groups <= one_round));
             if (one_launch) {
+                note_step(c, FX_LAUNCH_FRAME_TAIL, step);
                 HIP_TRY(fxk::launch_frame_tail_kernel(c->N, step.fp, step.ep, c->stream));
                 if (last) FX_EV(e1);
             } else {
                 HIP_TRY(launch_frames(c, step));
                 if (last) FX_EV(e1);
+                note_step(c, FX_LAUNCH_EPILOGUE, step);
                 HIP_TRY(fxk::launch_epilogue_kernels(step.ep, c->stream));
             }
             if (last) FX_EV(e2);
@@ -747,6 +787,7 @@ fx_status fx_set_gain(fx_context* c, float gain)
 fx_status fx_push_hops(fx_context* c, const void* hops, int num_hops, int sample_format, int mem_kind,
                        float* out_raw, float* out_smoothed)
 {
+    begin_launches(c);
     if (c && c->carry_count > 0)
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d samples per channel are pending from fx_push_samples; whole hops would overtake them "
                                                 "(finish the stream with fx_push_samples, or fx_reset_state)", c->carry_count);
@@ -769,6 +810,7 @@ fx_status fx_push_samples(fx_context* c, const void* samples, int num_samples, i
 {
     if (frames_out) *frames_out = 0;
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    begin_launches(c);
     if (num_samples < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative sample count");
     if (!known_format(sample_format)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown sample format %d", sample_format);
     if (mem_kind != FX_MEM_HOST && mem_kind != FX_MEM_DEVICE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", mem_kind);
@@ -835,6 +877,7 @@ fx_status fx_push_samples(fx_context* c, const void* samples, int num_samples, i
     rp.carry_bytes = (int) ((size_t) c->carry_count * esz);
     rp.carry_row_bytes = H * 4;
     rp.C = c->C;
+    if (fx_launch_record* r = note_launch(c, FX_LAUNCH_REBLOCK, 0)) r->reblock = fxk::reblock_form(rp);
     HIP_TRY(fxk::launch_reblock_kernel(rp, c->stream));
     // the stream holds the new carry whatever happens to the analysis below
     c->carry_cur ^= 1;
@@ -853,6 +896,7 @@ fx_status fx_push_samples(fx_context* c, const void* samples, int num_samples, i
 fx_status fx_process_frames(fx_context* c, const void* frames, int num_frames, int sample_format, int mem_kind,
                             float* out_raw, float* out_smoothed)
 {
+    begin_launches(c);
     if (c && c->carry_count > 0)
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d samples per channel are pending from fx_push_samples (finish the stream with fx_push_samples, or fx_reset_state)", c->carry_count);
     return run(c, frames, num_frames, sample_format, mem_kind, mem_kind, 0, out_raw, out_smoothed);
@@ -894,6 +938,8 @@ fx_status fx_get_osc_datagrams(fx_context* c, const char* prefix, int first_chan
     p.first_channel = first_channel;
     p.prefix_len = (int) strlen(prefix);
     memcpy(p.prefix, prefix, (size_t) p.prefix_len);
+    begin_launches(c);
+    note_launch(c, FX_LAUNCH_OSC, 0);
     HIP_TRY(fxk::launch_osc_kernel(p, c->stream));
     if (lengths) for (int i = 0; i < c->C; i++) lengths[i] = fx_osc_message_bytes(prefix, first_channel + i);
     if (mem_kind == FX_MEM_HOST) {
@@ -1113,6 +1159,8 @@ struct fx_stream {
         fxk::DynParams* h_dyn = nullptr;  // pinned: what changes from call to call
         fxk::DynParams* d_dyn = nullptr;
         hipGraphExec_t  exec[2] = {nullptr, nullptr};     // per parity of the context's ping-pong buffers
+        fx_launch_record launches[2][FX_LAUNCH_RECORD_CAP];   // the launch record each of them made at capture (fx_last_launches_internal)
+        int       num_launches[2] = {0, 0};
     };
     std::vector<Slot> ring;
     int head = 0;        // next slot to acquire
@@ -1238,6 +1286,7 @@ fx_status fx_stream_submit(fx_stream* s)
     if (!s) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null stream");
     if (!s->acquired) return fx_fail(FX_ERR_INVALID_ARGUMENT, "no slot acquired");
     fx_context* c = s->ctx;
+    begin_launches(c);
     HIP_TRY_OR(hipSetDevice(c->device), s->acquired = false);
     fx_stream::Slot& sl = s->ring[(size_t) s->head];
     { const fx_status es = fx_check_device_error(c); if (es != FX_OK) { s->acquired = false; return es; } }
@@ -1264,6 +1313,7 @@ fx_status fx_stream_submit(fx_stream* s)
         if (++s->next_seq == 0) s->next_seq = 1;            // 0 = "nothing completed yet"
         sl.seq = s->next_seq;
         const fxk::HopSignal sig = {s->d_arrivals, flag_dev, sl.seq, 0u, s->d_stage};
+        note_step(c, step.hop_pairs ? FX_LAUNCH_HOP_PAIR : FX_LAUNCH_HOP, step);
         const hipError_t e = fxk::launch_hop_kernel(c->N, step.fp, step.ep, sig, c->stream, step.hop_pairs);
         if (e != hipSuccess) { s->acquired = false; return fx_fail(FX_ERR_HIP, "launching the hop kernel failed: %s", hipGetErrorString(e)); }
         c->ev_valid = false;
@@ -1304,7 +1354,7 @@ fx_status fx_stream_submit(fx_stream* s)
                 if (e == hipSuccess) e = hipMemcpyAsync(sl.d_dyn, sl.h_dyn, sizeof(fxk::DynParams), hipMemcpyHostToDevice, c->stream);
             }
             if (e == hipSuccess) e = launch_frames(c, step);
-            if (e == hipSuccess) e = fxk::launch_epilogue_kernels(step.ep, c->stream);
+            if (e == hipSuccess) { note_step(c, FX_LAUNCH_EPILOGUE, step); e = fxk::launch_epilogue_kernels(step.ep, c->stream); }
             if (!zero_copy) {
                 if (e == hipSuccess) e = hipMemcpyAsync(sl.h_raw, sl.d_raw, s->out_bytes, hipMemcpyDeviceToHost, c->stream);
                 if (e == hipSuccess) e = hipMemcpyAsync(sl.h_sm, sl.d_sm, s->out_bytes, hipMemcpyDeviceToHost, c->stream);
@@ -1318,6 +1368,11 @@ fx_status fx_stream_submit(fx_stream* s)
                 s->acquired = false;
                 return fx_fail(FX_ERR_HIP, "capturing the streaming step failed: %s", hipGetErrorString(e));
             }
+            sl.num_launches[par] = c->num_launches;          // what the graph launches each time it is replayed
+            memcpy(sl.launches[par], c->launches, sizeof c->launches);
+        } else {
+            c->num_launches = sl.num_launches[par];
+            memcpy(c->launches, sl.launches[par], sizeof c->launches);
         }
         SUB_TRY(hipGraphLaunch(sl.exec[par], c->stream));
         // the step is enqueued: the context has moved on whatever happens to the bookkeeping event below
@@ -1339,6 +1394,7 @@ fx_status fx_stream_submit_samples(fx_stream* s, int num_samples)
     if (!s) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null stream");
     if (!s->acquired) return fx_fail(FX_ERR_INVALID_ARGUMENT, "no slot acquired");
     fx_context* c = s->ctx;
+    begin_launches(c);
     if (num_samples < 0 || (long long) num_samples > (long long) s->hops * (c->N / 2)) {
         s->acquired = false;
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "a slot holds 0 .. %lld samples per channel, got %d", (long long) s->hops * (c->N / 2), num_samples);

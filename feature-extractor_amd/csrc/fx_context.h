@@ -50,6 +50,8 @@ struct fx_context {
     float* d_latest = nullptr;    // [C][12]
     int    cur = 0;
     unsigned test_hooks = 0;      // fx_set_tuning_internal (fx_kernels.h): tests only
+    fx_launch_record launches[FX_LAUNCH_RECORD_CAP];    // fx_last_launches_internal (fx_kernels.h): what the last call launched
+    int      num_launches = 0;                          // (may exceed the cap: those beyond it are counted, not kept)
     fx_tuning tuning;             // launch-shape knobs: taken from the environment ONCE, in fx_create (fx_set_tuning replaces them)
     unsigned* h_err = nullptr;    // pinned, coherent: a kernel stores 1 here when a work unit gave up waiting for its predecessor (sticky)
     unsigned* d_err = nullptr;    // device view of h_err

@@ -173,6 +173,14 @@ struct ReblockParams {
     int                  carry_bytes, carry_row_bytes;
     int                  C;
 };
+constexpr int REBLOCK_THREADS = 256;
+// which kernel launch_reblock_kernel runs for p: 0 = fx_reblock_rows_kernel (rows shorter than a workgroup of 16-byte pieces), else the
+// pieces per thread of fx_reblock_kernel<1 / 2 / 4>
+inline int reblock_form(const ReblockParams& p)
+{
+    const long long pieces = ((long long) p.carry_bytes + p.in_row_bytes + 15) / 16;
+    return pieces < REBLOCK_THREADS ? 0 : (pieces >= 4 * REBLOCK_THREADS ? 4 : (pieces >= 2 * REBLOCK_THREADS ? 2 : 1));
+}
 hipError_t launch_reblock_kernel(const ReblockParams& p, hipStream_t stream);
 hipError_t clear_carry(unsigned char* carry, size_t bytes, hipStream_t stream);
 
@@ -216,6 +224,9 @@ __host__ __device__ inline void epilogue_constants(EpilogueParams& p)
     p.inv_bins = 1.0 / bins;
     p.bin_std = sqrt(p.bin_var);
 }
+// which kernels launch_epilogue_kernels runs for p: 1 = fx_tail_fused_kernel, 2 = fx_finalise_kernel + fx_epilogue_kernel + fx_history_kernel
+inline int epilogue_form(const EpilogueParams& p) { return p.T <= FUSED_TAIL_MAX_FRAMES ? 1 : 2; }
+// p.out_stride != 0 (the frame of a one-frame launch inside a longer call) is honoured by the one-frame tail only: other T are refused
 hipError_t launch_epilogue_kernels(const EpilogueParams& p, hipStream_t stream);
 // launch_frame_kernel (p.direct_state: one frame per channel, one wavefront each) and launch_epilogue_kernels in ONE launch: the
 // workgroup's first wavefronts finish its channels' hops when the frames are done (fx_frame_tail_kernel)
@@ -255,4 +266,23 @@ hipError_t launch_hop_kernel(int window_size, const FrameParams& p, const Epilog
 #define FX_HOOK_NO_BLOCK_FEED    16u
 #define FX_HOOK_NO_TWO_LAUNCHES  32u
 extern "C" fx_status fx_set_tuning_internal(fx_context* ctx, unsigned test_hooks);
+
+// Launch record, NOT part of the public ABI (tests only): the launches the context's last call made -- fx_push_hops, fx_process_frames,
+// fx_push_samples, fx_stream_submit(_samples), fx_get_osc_datagrams each start a new one; a captured ring step replays the record it made
+// at capture.  Fields that do not apply to a launcher are 0.
+enum { FX_LAUNCH_FRAME = 1, FX_LAUNCH_FRAME_TAIL, FX_LAUNCH_HOP, FX_LAUNCH_HOP_PAIR, FX_LAUNCH_PAIR, FX_LAUNCH_EPILOGUE, FX_LAUNCH_REBLOCK,
+       FX_LAUNCH_OSC };
+struct fx_launch_record {
+    int kind;               // FX_LAUNCH_*
+    int window, analysers;  // window size, analysers mask (bit 0 spectral, bit 1 harmonic)
+    // frame, frame_tail, pair, hop, hop_pair: the FrameParams fields that choose the kernel's form (hop launches: one workgroup per channel,
+    // ch_per_wg / waves_per_ch / num_chunks are not read and recorded as 0)
+    int T, direct_state, block_mode, num_chunks, ch_per_wg, waves_per_ch, hop_pairs;
+    int ep_T, out_stride;   // frame_tail, hop, hop_pair, epilogue: EpilogueParams::T, ::out_stride
+    int ep_form;            // epilogue: fxk::epilogue_form
+    int reblock;            // reblock: fxk::reblock_form
+};
+constexpr int FX_LAUNCH_RECORD_CAP = 8;
+// copies up to `cap` records of the last call to `out`; returns how many launches that call made (more than cap: the rest were not kept)
+extern "C" int fx_last_launches_internal(fx_context* ctx, fx_launch_record* out, int cap);
 #endif

@@ -410,6 +410,7 @@ hipError_t launch_frame_tail_kernel(int n, const FrameParams& p, const EpilogueP
 {
     if (p.C <= 0) return hipSuccess;
     if (!frame_tail_kernel_available(n)) return hipErrorInvalidValue;
+    if (ep.out_stride != 0 && ep.T != 1) return hipErrorInvalidValue;      // (only the one-frame tail writes frame out_t0 of out_stride)
     if (p.ch_per_wg < 1 || p.ch_per_wg > frame_kernel_max_waves(n)) return hipErrorInvalidValue;
     switch (n) {
         case 256:  return launch_tail_t<256>(p, ep, stream);
@@ -424,7 +425,8 @@ hipError_t launch_frame_tail_kernel(int n, const FrameParams& p, const EpilogueP
 hipError_t launch_epilogue_kernels(const EpilogueParams& p, hipStream_t stream)
 {
     if (p.C <= 0 || p.T <= 0) return hipSuccess;
-    if (p.T <= FUSED_TAIL_MAX_FRAMES) {
+    if (p.out_stride != 0 && p.T != 1) return hipErrorInvalidValue;        // the frame-per-lane forms write [C][T][12]: the rows would be wrong
+    if (epilogue_form(p) == 1) {
         hipLaunchKernelGGL(fx_tail_fused_kernel, dim3((unsigned) ((p.C + TAIL_CHANNELS - 1) / TAIL_CHANNELS)), dim3(64), 0, stream, p);
         return hipGetLastError();
     }

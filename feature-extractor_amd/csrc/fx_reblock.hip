@@ -19,7 +19,7 @@ namespace fxk {
 
 namespace {
 
-constexpr int RB_THREADS = 256;
+constexpr int RB_THREADS = REBLOCK_THREADS;    // (fx_kernels.h: reblock_form chooses the kernel by it)
 
 // PIECES pieces per thread, a workgroup's span apart (every access of a wavefront is 1 KB of consecutive bytes): the loads of all
 // pieces are issued before the first store, so a lane keeps PIECES x 20 bytes in flight.
@@ -77,13 +77,13 @@ hipError_t launch_reblock_kernel(const ReblockParams& p, hipStream_t stream)
         total - p.out_row_bytes > p.carry_row_bytes)
         return hipErrorInvalidValue;
     const long long pieces = (total + 15) / 16;         // (of 16 bytes)
-    if (pieces < RB_THREADS) {
+    const int per_thread = reblock_form(p);
+    if (per_thread == 0) {
         const unsigned long long all = (unsigned long long) p.C * (unsigned long long) pieces;
         hipLaunchKernelGGL(fx_reblock_rows_kernel, dim3((unsigned) ((all + RB_THREADS - 1) / RB_THREADS)), dim3(RB_THREADS), 0, stream, p, (unsigned) pieces);
         return hipGetLastError();
     }
-    // rows shorter than a workgroup's span of four pieces per thread (16 KB) would leave most of such a workgroup idle
-    const int per_thread = pieces >= 4 * RB_THREADS ? 4 : (pieces >= 2 * RB_THREADS ? 2 : 1);
+    // (per_thread: rows shorter than a workgroup's span of four pieces per thread (16 KB) would leave most of such a workgroup idle)
     const unsigned gx = (unsigned) ((pieces + (long long) per_thread * RB_THREADS - 1) / ((long long) per_thread * RB_THREADS));
     // grid.y is limited to 65535: more channels than that go in slices (a context of 65 536 channels is configs[3])
     for (int c0 = 0; c0 < p.C; c0 += 65535) {

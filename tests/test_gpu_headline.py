@@ -188,7 +188,9 @@ def test_one_frame_calls_run_the_hop_kernel_and_equal_the_batch_kernels(gpu_fx, 
             got.append((r.cpu().numpy(), s.cpu().numpy()))
         else:
             got.append(hop_k.push_hops(hops[:, t:t + 1]))
+        assert [l["kind"] for l in hop_k.last_launches()] == ["hop"], t
         want.append(batch_k.push_hops(hops[:, t:t + 1]))
+        assert [l["kind"] for l in batch_k.last_launches()] == ["frame_tail"], t          # (one round of workgroups: frames and tails in one launch)
     for k in (0, 1):
         assert np.array_equal(np.concatenate([g[k] for g in got], 1), np.concatenate([w[k] for w in want], 1), equal_nan=True), k
     assert np.array_equal(hop_k.get_features(), batch_k.get_features(), equal_nan=True)
@@ -205,9 +207,10 @@ def test_one_frame_calls_run_the_hop_kernel_and_equal_the_batch_kernels(gpu_fx, 
         assert np.array_equal(ga[0], gb[0], equal_nan=True) and np.array_equal(ga[1], gb[1], equal_nan=True), t
 
 
-@pytest.mark.parametrize("N,C,onset", [(1024, 1100, (8, 2)), (4096, 1100, (5, 1))])
+@pytest.mark.parametrize("N,C,onset", [(1024, 4100, (8, 2)), (4096, 2100, (5, 1))])
 def test_large_one_frame_calls_take_the_batch_kernels_and_equal_the_hop_kernel(gpu_fx, oracle, N, C, onset):
-    """Above 2^20 samples per call (2^22 at 4096 points) a one-frame call runs as the frame kernel + fx_tail_fused_kernel, whose one-frame form gives every
+    """Above 2^20 samples per call (2^22 at 4096 points) a one-frame call takes the batch kernels, and beyond one round of workgroups (513 of eight
+    channels at 1024 points, 263 of eight at 4096) it runs as the frame kernel + fx_tail_fused_kernel, whose one-frame form gives every
     smoothed slot a lane, evaluates the onset detector's candidates side by side and takes the scalar tail's logarithms in five lanes:
     bit for bit what fx_hop_kernel (forced) gives, and the oracle's values -- onsets included, over enough hops to fill every history."""
     assert C * N > ((1 << 22) if N == 4096 else (1 << 20))
@@ -217,8 +220,13 @@ def test_large_one_frame_calls_take_the_batch_kernels_and_equal_the_hop_kernel(g
     hop_k.set_tuning(one_hop_kernel=1)
     for an in (auto, hop_k):
         an.set_onset_window_length(onset[0]); an.set_onset_detection_type(onset[1]); an.set_onset_detection_sensitivity(0.3)
-    got = [auto.push_hops(hops[:, t:t + 1]) for t in range(T)]
-    want = [hop_k.push_hops(hops[:, t:t + 1]) for t in range(T)]
+    got, want = [], []
+    for t in range(T):
+        got.append(auto.push_hops(hops[:, t:t + 1]))
+        launched = auto.last_launches()
+        assert [(l["kind"], l["direct_state"], l["ep_T"]) for l in launched] == [("frame", 1, 0), ("epilogue", 0, 1)], launched
+        want.append(hop_k.push_hops(hops[:, t:t + 1]))
+        assert [l["kind"] for l in hop_k.last_launches()] == ["hop"]
     for k in (0, 1):
         assert np.array_equal(np.concatenate([g[k] for g in got], 1), np.concatenate([w[k] for w in want], 1), equal_nan=True), k
     assert np.array_equal(auto.get_features(), hop_k.get_features(), equal_nan=True)

@@ -124,6 +124,7 @@ def test_one_hop_calls_on_pairs_equal_the_pair_kernel_bitwise(gpu_fx, oracle, N,
     for b in range(nb):
         settings(ref, b)
         want.append(ref.push_hops(hops[:, b:b + 1]))
+        assert [(l["kind"], l["ep_T"]) for l in ref.last_launches()] == [("pair", 0), ("epilogue", 1)]
     want = tuple(np.concatenate([x[k] for x in want], 1) for k in (0, 1))
 
     direct = gpu_fx.BatchAnalyser(C, N)
@@ -132,6 +133,7 @@ def test_one_hop_calls_on_pairs_equal_the_pair_kernel_bitwise(gpu_fx, oracle, N,
     for b in range(nb):
         settings(direct, b)
         got.append(direct.push_hops(hops[:, b:b + 1]))
+        assert [l["kind"] for l in direct.last_launches()] == ["hop_pair"]
     for k in (0, 1):
         assert np.array_equal(np.concatenate([g[k] for g in got], 1), want[k], equal_nan=True), k
 
@@ -144,6 +146,7 @@ def test_one_hop_calls_on_pairs_equal_the_pair_kernel_bitwise(gpu_fx, oracle, N,
         if st.in_flight() == 2:
             got.append(st.collect())
         st.push(hops[:, b:b + 1])
+        assert [l["kind"] for l in an.last_launches()] == ["hop_pair"]
     while st.in_flight():
         got.append(st.collect())
     st.close()

@@ -381,8 +381,9 @@ def test_one_hop_per_call_kernel_equals_push_hops_bitwise(gpu_fx, monkeypatch, N
     for b in range(nb):
         settings(ref, b)
         want.append(ref.push_hops(hops[:, b:b + 1]))
+        assert [l["kind"] for l in ref.last_launches()] == ["frame_tail"]          # (one round of workgroups: frames and tails in one launch)
 
-    def through_ring(depth):
+    def through_ring(depth, kinds=("hop",)):
         an = gpu_fx.BatchAnalyser(C, N, order=order)
         st = gpu_fx.HopStream(an, 1, slots=3)
         got = []
@@ -391,6 +392,7 @@ def test_one_hop_per_call_kernel_equals_push_hops_bitwise(gpu_fx, monkeypatch, N
             if st.in_flight() == depth:
                 got.append(st.collect())
             st.push(hops[:, b:b + 1])
+            assert [l["kind"] for l in an.last_launches()] == list(kinds), b
         while st.in_flight():
             got.append(st.collect())
         feats = an.get_features()
@@ -403,7 +405,7 @@ def test_one_hop_per_call_kernel_equals_push_hops_bitwise(gpu_fx, monkeypatch, N
             assert np.array_equal(np.concatenate([g[k] for g in got], 1), np.concatenate([w[k] for w in want], 1), equal_nan=True), (depth, k)
         assert np.array_equal(feats, ref.get_features(), equal_nan=True)
     monkeypatch.setenv("FX_STREAM_HOP_KERNEL", "0")
-    got, feats = through_ring(2)
+    got, feats = through_ring(2, ("frame", "epilogue"))      # the captured step
     for k in (0, 1):
         assert np.array_equal(np.concatenate([g[k] for g in got], 1), np.concatenate([w[k] for w in want], 1), equal_nan=True)
 

@@ -294,11 +294,13 @@ def test_block_feed_of_every_one_frame_kernel_equals_the_reblocked_path_bitwise(
         lengths.append(n)
         at += n
 
-    def feed(an, device):
+    def feed(an, device, launches=None):
         raws, sms, at = [], [], 0
         for n in lengths:
             piece = np.ascontiguousarray(stream[:, per * at:per * (at + n)])
             r, s = an.push_samples(torch.from_numpy(piece).cuda() if device else piece, sample_format=sf)
+            if launches is not None:
+                launches.append((r.shape[1], an.last_launches()))
             if hasattr(r, "cpu"):
                 r, s = r.cpu().numpy(), s.cpu().numpy()
             raws.append(r); sms.append(s)
@@ -308,20 +310,27 @@ def test_block_feed_of_every_one_frame_kernel_equals_the_reblocked_path_bitwise(
     ref = gpu_fx.BatchAnalyser(C, N)
     ref.set_gain(0.5)
     ref.set_test_hooks(16)                      # never feed blocks to the kernels
-    want = feed(ref, False)
+    launches = []
+    want = feed(ref, False, launches)
+    assert all(rec[0]["kind"] == "reblock" for f, rec in launches if f), launches
     assert want[0].shape[1] == total // H
     more = np.ascontiguousarray(stream[:, :per * (H - total % H)])       # the pending samples themselves: this block completes a hop out of them
     want_more = ref.push_samples(more, sample_format=sf)
     assert want_more[0].shape == (C, 1, 12)
     ref.close()
     shapes = {"hop kernel": dict(one_hop_kernel=1), "frames + tails in one launch": dict(one_hop_kernel=0, hooks=8), "frame kernel, then the tail kernel": dict(one_hop_kernel=0, hooks=4)}
+    per_hop = {"hop kernel": ["hop"], "frames + tails in one launch": ["frame_tail"], "frame kernel, then the tail kernel": ["frame", "epilogue"]}
     for name, knobs in shapes.items():
         for device in ((False, True) if fmt != "s24" else (False,)):
             an = gpu_fx.BatchAnalyser(C, N)
             an.set_gain(0.5)
             an.set_tuning(one_hop_kernel=knobs["one_hop_kernel"])
             an.set_test_hooks(knobs.get("hooks", 0))
-            got = feed(an, device)
+            launches = []
+            got = feed(an, device, launches)
+            for f, rec in launches:          # every call that completes hops: the named kernels, reading the block themselves
+                assert f == 0 or ([l["kind"] for l in rec] == per_hop[name] * f and rec[0]["block_mode"] == 1), (name, f, rec)
+            assert any(f for f, _ in launches)
             assert got[2] == want[2] == total % H
             assert same(got[0], want[0]) and same(got[1], want[1]) and same(got[3], want[3]), (N, fmt, name, device)
             got_more = an.push_samples(more, sample_format=sf)
@@ -355,11 +364,13 @@ def test_long_blocks_through_the_batch_kernels_block_fed_form_equal_the_reblocke
         stream, per = x, 1
     sf = "s24" if fmt == "s24" else None
 
-    def feed(an, device):
+    def feed(an, device, launches=None):
         raws, sms, at = [], [], 0
         for n in lengths:
             piece = np.ascontiguousarray(stream[:, per * at:per * (at + n)])
             r, s = an.push_samples(torch.from_numpy(piece).cuda() if device else piece, sample_format=sf)
+            if launches is not None:
+                launches.append((r.shape[1], an.last_launches()))
             if hasattr(r, "cpu"):
                 r, s = r.cpu().numpy(), s.cpu().numpy()
             raws.append(r); sms.append(s)
@@ -369,14 +380,21 @@ def test_long_blocks_through_the_batch_kernels_block_fed_form_equal_the_reblocke
     ref = gpu_fx.BatchAnalyser(C, N)
     ref.set_gain(0.75)
     ref.set_test_hooks(16)
-    want = feed(ref, False)
+    launches = []
+    want = feed(ref, False, launches)
     ref.close()
+    assert all(rec[0]["kind"] == "reblock" for f, rec in launches if f), launches
     assert want[0].shape[1] == total // H
     for device in ((False, True) if fmt != "s24" else (False,)):
         an = gpu_fx.BatchAnalyser(C, N)
         an.set_gain(0.75)
-        got = feed(an, device)
+        launches = []
+        got = feed(an, device, launches)
         an.close()
+        for f, rec in launches:              # more than two hops: ONE launch of the block-fed batch form, no re-blocking
+            if f > 2:
+                assert [(l["kind"], l["block_mode"], l["T"]) for l in rec] == [("frame", 1, f), ("epilogue", 0, 0)], (f, rec)
+        assert sum(f > 2 for f, _ in launches) >= 6, launches
         assert got[2] == want[2] == total % H
         assert same(got[0], want[0]) and same(got[1], want[1]) and same(got[3], want[3]), (fmt, device)
 
@@ -428,16 +446,18 @@ def test_two_hop_calls_as_two_one_frame_launches_equal_the_batch_form_bitwise(gp
         n = min(int(rng.integers(H + H // 2, 2 * H + H // 2)), total - at)
         lengths.append(n); at += n
 
-    def feed_blocks_(an, device):
+    def feed_blocks_(an, device, launches=None):
         raws, at = [], 0
         for n in lengths:
             piece = np.ascontiguousarray(stream[:, per * at:per * (at + n)])
             r, s = an.push_samples(torch.from_numpy(piece).cuda() if device else piece, sample_format=sf)
+            if launches is not None:
+                launches.append((r.shape[1], an.last_launches()))
             raws.append((r.cpu().numpy(), s.cpu().numpy()) if hasattr(r, "cpu") else (r, s))
             at += n
         return np.concatenate([r for r, _ in raws], 1), np.concatenate([s for _, s in raws], 1), an.pending_samples(), an.get_features()
 
-    def feed_pairs(an, device):
+    def feed_pairs(an, device, launches=None):
         hops = np.ascontiguousarray(stream[:, :per * 12 * H]).reshape(C, 12, per * H)
         if fmt == "s24":
             hops = gpu_fx.pack_s24(np.clip(np.round(x[:, :12 * H].reshape(C, 12, H) * 8388608.0), -2 ** 23, 2 ** 23 - 1).astype(np.int32))
@@ -445,24 +465,37 @@ def test_two_hop_calls_as_two_one_frame_launches_equal_the_batch_form_bitwise(gp
         for t in range(0, 12, 2):
             piece = hops[:, t:t + 2]
             r, s = an.push_hops(torch.from_numpy(np.ascontiguousarray(piece)).cuda() if (device and fmt != "s24") else piece)
+            if launches is not None:
+                launches.append(an.last_launches())
             out.append((r.cpu().numpy(), s.cpu().numpy()) if hasattr(r, "cpu") else (r, s))
         return np.concatenate([r for r, _ in out], 1), np.concatenate([s for _, s in out], 1), an.get_features()
 
     ref = gpu_fx.BatchAnalyser(C, N); ref.set_gain(1.5); ref.set_test_hooks(16 | 32)
     want_blocks = feed_blocks_(ref, False); ref.close()
     ref = gpu_fx.BatchAnalyser(C, N); ref.set_gain(1.5); ref.set_test_hooks(32)
-    want_pairs = feed_pairs(ref, False); ref.close()
+    launches = []
+    want_pairs = feed_pairs(ref, False, launches); ref.close()
+    assert all([(l["kind"], l["T"], l["ep_T"]) for l in rec] == [("frame", 2, 0), ("epilogue", 0, 2)] for rec in launches), launches
     assert same(want_pairs[0], want_blocks[0][:, :12])            # the same stream either way
+    per_hop = {"hop kernel": ["hop"], "frames + tails in one launch": ["frame_tail"], "frame kernel, then the tail kernel": ["frame", "epilogue"]}
     for name, knobs in {"hop kernel": dict(one_hop_kernel=1), "frames + tails in one launch": dict(one_hop_kernel=0, hooks=8),
                         "frame kernel, then the tail kernel": dict(one_hop_kernel=0, hooks=4)}.items():
         for device in ((False, True) if fmt != "s24" else (False,)):
             an = gpu_fx.BatchAnalyser(C, N); an.set_gain(1.5)
             an.set_tuning(one_hop_kernel=knobs["one_hop_kernel"]); an.set_test_hooks(knobs.get("hooks", 0))
-            got = feed_blocks_(an, device)
+            launches = []
+            got = feed_blocks_(an, device, launches)
+            for f, rec in launches:          # one or two hops: that many one-frame launches of the named kernels, reading the block
+                if f in (1, 2):
+                    assert [l["kind"] for l in rec] == per_hop[name] * f and rec[0]["block_mode"] == 1, (name, f, rec)
+            assert any(f == 2 for f, _ in launches)
             assert got[2] == want_blocks[2] and all(same(g, w) for g, w in zip((got[0], got[1], got[3]), (want_blocks[0], want_blocks[1], want_blocks[3]))), (N, fmt, name, device, "blocks")
             an.close()
             an = gpu_fx.BatchAnalyser(C, N); an.set_gain(1.5)
             an.set_tuning(one_hop_kernel=knobs["one_hop_kernel"]); an.set_test_hooks(knobs.get("hooks", 0))
-            got = feed_pairs(an, device)
+            launches = []
+            got = feed_pairs(an, device, launches)
+            assert all([(l["kind"], l["out_stride"]) for l in rec if l["kind"] != "frame"] == [(k, 2) for k in per_hop[name] if k != "frame"] * 2
+                       for rec in launches), (name, launches)
             assert all(same(g, w) for g, w in zip(got, want_pairs)), (N, fmt, name, device, "two hops per call")
             an.close()
