@@ -107,7 +107,7 @@ class BatchAnalyser:
 
     def last_launches(self):
         """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
-        (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc)."""
+        (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps)."""
         fn = self._lib.fx_last_launches_internal
         fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int], ctypes.c_int
         cap = capi.LAUNCH_RECORD_CAP
@@ -124,6 +124,25 @@ class BatchAnalyser:
 
     def sync(self):
         capi.check(self._lib.fx_sync(self._h))
+
+    # ---- analysis taps: the reference's display buffers (include/fx.h, fx_request_taps) ----
+    def request_taps(self, channels):
+        """Arm the display buffers of these channels: the next analysis call that analyses a frame captures its first frame's."""
+        ch = np.ascontiguousarray(np.atleast_1d(np.asarray(channels, dtype=np.int32)))
+        capi.check(self._lib.fx_request_taps(self._h, ch.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(ch.size)))
+
+    def taps(self, channel):
+        """The latest capture of `channel`: window [N], spectrum [2N], pitch_spectrum [2N], autocorrelation [N], cnd [N],
+        lag_position [2] (float32 arrays) and frame_index (int)."""
+        N = self.window_size
+        out = {"window": np.empty(N, np.float32), "spectrum": np.empty(2 * N, np.float32), "pitch_spectrum": np.empty(2 * N, np.float32),
+               "autocorrelation": np.empty(N, np.float32), "cnd": np.empty(N, np.float32), "lag_position": np.empty(2, np.float32)}
+        frame = ctypes.c_longlong()
+        ptr = {k: v.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for k, v in out.items()}
+        capi.check(self._lib.fx_get_taps(self._h, int(channel), ptr["window"], ptr["spectrum"], ptr["pitch_spectrum"],
+                                         ptr["autocorrelation"], ptr["cnd"], ptr["lag_position"], ctypes.byref(frame)))
+        out["frame_index"] = frame.value
+        return out
 
     def last_kernel_ms(self):
         a, b = ctypes.c_float(), ctypes.c_float()

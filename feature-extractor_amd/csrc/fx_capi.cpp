@@ -457,7 +457,7 @@ bool blocks_feed_kernels(const fx_context* c)
 // in_kind / out_kind: where the caller's samples and result buffers live (fx_push_samples hands over hops it has assembled in device
 // memory with results that may go to the host)
 fx_status run(fx_context* c, const void* in, int T, int sample_format, int in_kind, int out_kind, int hop_mode,
-              float* out_raw, float* out_smoothed, const BlockFeed* blocks = nullptr)
+              float* out_raw, float* out_smoothed, const BlockFeed* blocks = nullptr, bool taps = false)
 {
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
     if (T < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative frame count");
@@ -509,6 +509,12 @@ fx_status run(fx_context* c, const void* in, int T, int sample_format, int in_ki
             return fx_fail(FX_ERR_INVALID_ARGUMENT, "device input must be %d-byte aligned", blocks ? 4 : 16);
     }
     if (blocks && (T < 1 || T > 4096 || !hop_mode || in_kind != FX_MEM_DEVICE)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "a block feed is 1 .. 4096 hops per channel from device memory");
+    // armed taps (fx_request_taps): their launch reads this call's first frame before any launch of the call changes the context's state
+    if (taps && c->taps_armed && c->taps_launch) {
+        const fx_tap_source src = {d_in, sample_format, hop_mode, blocks ? blocks->in_row_bytes : (long long) (T * per_frame * esz),
+                                   blocks ? blocks->carry_in : nullptr, blocks ? blocks->carry_bytes : 0, blocks ? blocks->carry_row_bytes : 0};
+        if ((st = c->taps_launch(c, src)) != FX_OK) return st;
+    }
 
     // A call of TWO hops per channel (a 1024-sample device buffer against a 1024-point window, 960-sample blocks every other call ...) runs
     // as two one-frame launches over the same buffers -- the second reads hop 1 and writes frame 1 (FrameParams::in_hop_stride / in_hop0,
@@ -723,6 +729,7 @@ fx_status fx_destroy(fx_context* c)
     (void) hipSetDevice(c->device);
     fx_comm_release(c);
     if (c->stream) (void) hipStreamSynchronize(c->stream);
+    if (c->taps_release) c->taps_release(c);
     void* bufs[] = {c->d_tw, c->d_prev, c->d_tail[0], c->d_tail[1], c->d_hist, c->d_latest,
                     c->d_raw, c->d_part, c->d_in, c->d_out_raw, c->d_queue, c->d_carry[0], c->d_carry[1], c->d_hops, c->d_osc};
     for (void* b : bufs) if (b) (void) hipFree(b);
@@ -740,6 +747,7 @@ fx_status fx_reset_state(fx_context* c)
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->h_err) *c->h_err = 0;
+    if (c->taps_release) c->taps_release(c);
     return zero_state(c);
 }
 
@@ -791,7 +799,7 @@ fx_status fx_push_hops(fx_context* c, const void* hops, int num_hops, int sample
     if (c && c->carry_count > 0)
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d samples per channel are pending from fx_push_samples; whole hops would overtake them "
                                                 "(finish the stream with fx_push_samples, or fx_reset_state)", c->carry_count);
-    return run(c, hops, num_hops, sample_format, mem_kind, mem_kind, 1, out_raw, out_smoothed);
+    return run(c, hops, num_hops, sample_format, mem_kind, mem_kind, 1, out_raw, out_smoothed, nullptr, true);
 }
 
 // ---- the collector's real interface: device blocks of any length (ref AudioDataCollector.h:36-94) ----
@@ -805,8 +813,9 @@ fx_status fx_clear_pending(fx_context* c)
     return FX_OK;
 }
 
-fx_status fx_push_samples(fx_context* c, const void* samples, int num_samples, int sample_format, int mem_kind,
-                          float* out_raw, float* out_smoothed, int* frames_out)
+// fx_push_samples; `taps`: whether the call serves armed taps (the ring's submissions do not, include/fx.h)
+static fx_status push_samples(fx_context* c, const void* samples, int num_samples, int sample_format, int mem_kind,
+                              float* out_raw, float* out_smoothed, int* frames_out, bool taps)
 {
     if (frames_out) *frames_out = 0;
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
@@ -830,13 +839,13 @@ fx_status fx_push_samples(fx_context* c, const void* samples, int num_samples, i
 
     // whole hops from an aligned device buffer and nothing pending: the block IS the hop buffer
     if (mem_kind == FX_MEM_DEVICE && c->carry_count == 0 && rest == 0 && reinterpret_cast<uintptr_t>(samples) % 16 == 0) {
-        const fx_status st = run(c, samples, hops, sample_format, FX_MEM_DEVICE, FX_MEM_DEVICE, 1, out_raw, out_smoothed);
+        const fx_status st = run(c, samples, hops, sample_format, FX_MEM_DEVICE, FX_MEM_DEVICE, 1, out_raw, out_smoothed, nullptr, taps);
         if (st == FX_OK && frames_out) *frames_out = hops;
         return st;
     }
     // ... and so is a host block of whole hops (512-sample callbacks against a 1024-point window): one copy in, no re-blocking
     if (mem_kind == FX_MEM_HOST && c->carry_count == 0 && rest == 0) {
-        const fx_status st = run(c, samples, hops, sample_format, FX_MEM_HOST, FX_MEM_HOST, 1, out_raw, out_smoothed);
+        const fx_status st = run(c, samples, hops, sample_format, FX_MEM_HOST, FX_MEM_HOST, 1, out_raw, out_smoothed, nullptr, taps);
         if (st == FX_OK && frames_out) *frames_out = hops;
         return st;
     }
@@ -857,7 +866,7 @@ fx_status fx_push_samples(fx_context* c, const void* samples, int num_samples, i
         // analysis.  (Windows of 2048 / 4096 points re-block calls of more than two hops: measured faster there, fx_kernels.hip launch_t.)
         const BlockFeed feed = {c->d_carry[c->carry_cur], c->d_carry[c->carry_cur ^ 1], (int) ((size_t) c->carry_count * esz), H * 4,
                                 (long long) num_samples * (long long) esz};
-        st = run(c, d_block, hops, sample_format, FX_MEM_DEVICE, mem_kind, 1, out_raw, out_smoothed, &feed);
+        st = run(c, d_block, hops, sample_format, FX_MEM_DEVICE, mem_kind, 1, out_raw, out_smoothed, &feed, taps);
         if (st != FX_OK) return st;             // (the stream is no longer the caller's: fx_reset_state, as the contract says)
         c->carry_cur ^= 1;
         c->carry_count = rest;
@@ -877,6 +886,11 @@ fx_status fx_push_samples(fx_context* c, const void* samples, int num_samples, i
     rp.carry_bytes = (int) ((size_t) c->carry_count * esz);
     rp.carry_row_bytes = H * 4;
     rp.C = c->C;
+    // armed taps read the first hop from [pending | block] before the re-blocking kernel moves the pending samples on
+    if (taps && hops > 0 && c->taps_armed && c->taps_launch) {
+        const fx_tap_source src = {d_block, sample_format, 1, rp.in_row_bytes, rp.carry_in, rp.carry_bytes, rp.carry_row_bytes};
+        if ((st = c->taps_launch(c, src)) != FX_OK) return st;
+    }
     if (fx_launch_record* r = note_launch(c, FX_LAUNCH_REBLOCK, 0)) r->reblock = fxk::reblock_form(rp);
     HIP_TRY(fxk::launch_reblock_kernel(rp, c->stream));
     // the stream holds the new carry whatever happens to the analysis below
@@ -893,13 +907,19 @@ fx_status fx_push_samples(fx_context* c, const void* samples, int num_samples, i
     return FX_OK;
 }
 
+fx_status fx_push_samples(fx_context* c, const void* samples, int num_samples, int sample_format, int mem_kind,
+                          float* out_raw, float* out_smoothed, int* frames_out)
+{
+    return push_samples(c, samples, num_samples, sample_format, mem_kind, out_raw, out_smoothed, frames_out, true);
+}
+
 fx_status fx_process_frames(fx_context* c, const void* frames, int num_frames, int sample_format, int mem_kind,
                             float* out_raw, float* out_smoothed)
 {
     begin_launches(c);
     if (c && c->carry_count > 0)
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d samples per channel are pending from fx_push_samples (finish the stream with fx_push_samples, or fx_reset_state)", c->carry_count);
-    return run(c, frames, num_frames, sample_format, mem_kind, mem_kind, 0, out_raw, out_smoothed);
+    return run(c, frames, num_frames, sample_format, mem_kind, mem_kind, 0, out_raw, out_smoothed, nullptr, true);
 }
 
 fx_status fx_get_smoothed(fx_context* c, float* out, int mem_kind)
@@ -1421,7 +1441,7 @@ static fx_status submit_large(fx_stream* s, fx_stream::Slot& sl, size_t in_bytes
     LG_TRY(hipStreamWaitEvent(c->stream, sl.copied, 0), (void) hipStreamSynchronize(s->copy));
     int frames = s->hops;
     const fx_status st = num_samples < 0 ? run(c, sl.d_in, s->hops, s->fmt, FX_MEM_DEVICE, FX_MEM_DEVICE, 1, sl.d_raw, sl.d_sm)
-                                         : fx_push_samples(c, sl.d_in, num_samples, s->fmt, FX_MEM_DEVICE, sl.d_raw, sl.d_sm, &frames);
+                                         : push_samples(c, sl.d_in, num_samples, s->fmt, FX_MEM_DEVICE, sl.d_raw, sl.d_sm, &frames, false);
     if (st != FX_OK) {
         // The copy is already enqueued, and fx_push_samples may have launched its re-blocking kernel on the context's stream before it failed: both
         // read the slot, so let both finish before the slot is handed back.  The ring stays usable; the STREAM of a samples submit does not:

@@ -23,6 +23,21 @@ struct fx_comm;     // fx_comm.cpp
 void fx_comm_release(fx_context* ctx);   // called by fx_destroy
 fx_status fx_check_device_error(fx_context* ctx);   // after a synchronisation: FX_ERR_HIP if a kernel reported a failed hand-over
 
+// Analysis taps (fx_request_taps / fx_get_taps, include/fx.h) live in fx_taps.hip; this file only carries their state and the two hooks
+// fx_request_taps installs, so that the rest of the library refers to no symbol of that unit.
+struct fx_taps;
+// Where an analysis call reads its FIRST frame, as the kernels read it: `in` (device) holds rows of in_row_bytes per channel; hop_mode 1:
+// hops of N/2 samples, the window is [the channel's tail | hop 0 x gain]; 0: whole frames, frame 0 as given.  carry != null: the hop is
+// the first N/2 samples of [pending | block] (fx_blocks.hip.h, BlockStream), the pending row of the channel at carry + c * carry_row_bytes.
+struct fx_tap_source {
+    const void*          in;
+    int                  sample_format;
+    int                  hop_mode;
+    long long            in_row_bytes;
+    const unsigned char* carry;
+    int                  carry_bytes, carry_row_bytes;
+};
+
 struct fx_context {
     int      device = 0;
     int      C = 0, N = 0;
@@ -85,6 +100,12 @@ struct fx_context {
     int    compute_units = 256;         // of this context's device (MI355X: 256)
 
     fx_comm* comm = nullptr;      // fx_comm_create (fx_comm.cpp); null for a single-GPU context
+
+    // taps (fx_taps.hip): null until the first fx_request_taps, which installs the hooks.  taps_armed: channels waiting for a capture.
+    fx_taps* taps = nullptr;
+    int      taps_armed = 0;
+    fx_status (*taps_launch)(fx_context*, const fx_tap_source&) = nullptr;   // capture the call's first frame; clears the request
+    void      (*taps_release)(fx_context*) = nullptr;                         // drop request, capture and memory (reset, destroy)
 };
 
 #endif

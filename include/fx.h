@@ -190,6 +190,41 @@ fx_status fx_get_stream(fx_context* ctx, void** stream);
  * by default calls made of one-frame launches do not (fx_tuning::call_timing). */
 fx_status fx_last_kernel_ms(fx_context* ctx, float* frame_kernel_ms, float* epilogue_kernel_ms);
 
+/* ---- analysis taps: the analysers' display buffers, what PitchEstimationVisualiser.h draws ----
+ * The reference hands a host what its analysers saw through one-shot flags: each enable...NeedsUpdating call makes the next frame
+ * analysed copy one buffer, and clears the flag (RealTimeAudioAnalysis.h:221-232, :268-283; PitchAnalyser.h:30-53,66-72,187).
+ * Here one request arms all five of them for a set of channels:
+ *   - requests accumulate: channels armed by calls before an analysis call are served together by that call; arming a channel that
+ *     is already armed changes nothing.  More than FX_MAX_TAP_CHANNELS distinct armed channels, a channel outside [0, num_channels)
+ *     or a null context is FX_ERR_INVALID_ARGUMENT, before any device use.
+ *   - the first later fx_push_hops, fx_process_frames or fx_push_samples call that analyses at least one frame serves every armed
+ *     channel: it captures the FIRST frame it analyses (the reference's one-shot flag), and the request is cleared.  A fx_push_samples
+ *     call that completes no hop leaves the request armed, and so do the fx_stream_* ring submissions (their captured steps are not
+ *     changed by taps).
+ *   - the capture is made by one extra launch on the context's stream, enqueued before anything of the call that changes the
+ *     context's state; if it fails the call returns the error with the context untouched and the request still armed.  With nothing
+ *     armed an analysis call makes exactly the launches it makes without taps.
+ *   - one capture at a time: a new capture replaces the old one whole.  fx_reset_state drops the request and the capture.
+ *   - every buffer is formed whatever analysers the context runs (FX_SPECTRAL_ONLY, FX_HARMONIC_ONLY, FX_LOW_LATENCY): the buffers
+ *     depend on the window alone, and each is bit for bit what the reference's arithmetic makes of that window. */
+#define FX_MAX_TAP_CHANNELS 64
+/* Arm the display buffers of these channels (the reference's enable...NeedsUpdating calls, all five at once). */
+fx_status fx_request_taps(fx_context* ctx, const int* channels, int num_channels);
+/* Host copies of the latest capture for `channel`; any pointer may be NULL.  FX_ERR_INVALID_ARGUMENT if the latest capture does
+ * not hold `channel` (or there is none).  May synchronise the context's stream.
+ *   window          [N]   the overlapped window of the captured frame, RealTimeAudioDataOverlapper::getBufferToDraw: the channel's
+ *                         carried second half, then the first new hop times the gain (fx_push_hops; fx_push_samples: the first N/2
+ *                         samples of [pending | block]), or the frame as given, without gain (fx_process_frames); not windowed
+ *   spectrum        [2N]  (re, im) pairs of the Bartlett-windowed window's transform: the spectral analyser's getFFTBufferToDraw
+ *   pitch_spectrum  [2N]  the same of the low-passed, windowed window: the harmonic analyser's getFFTBufferToDraw
+ *                         (its first getFrequencyData, RealTimeAnalyser.h:160)
+ *   autocorrelation [N]   getAutoCorrelationBufferToDraw: v[s] = d[s] * d[s] * s of the inverse transform d of the squared real parts
+ *   cnd             [N]   getCumulativeDifferenceBufferToDraw: the cumulative normalised difference of v
+ *   lag_position    [2]   getNormalisedLagPosition: (lag / 2N, cnd[lag]), or (-1 / 2N, 100) when no value fell below the threshold
+ *   frame_index     which frame of the channel's stream was captured: frames analysed since fx_create / fx_reset_state, 0-based */
+fx_status fx_get_taps(fx_context* ctx, int channel, float* window, float* spectrum, float* pitch_spectrum,
+                      float* autocorrelation, float* cnd, float* lag_position, long long* frame_index);
+
 /* ---- streaming ingest: replaces AudioDataCollector's ring + busy-wait reader ----
  * (AudioDataCollector.h:24,36-94: audio thread writes a 4096-sample ring, the analysis thread spins
  * until a hop is available.)  Here the producer owns a ring of `slots` PINNED host batches, each

@@ -124,6 +124,38 @@ public:
     void setGain (float g)                                     { check (fx_set_gain (ctx, g)); }                  // AudioDataCollector.h:124
     void reset()                                               { check (fx_reset_state (ctx)); }
 
+    // The analysers' display buffers (fx_request_taps / fx_get_taps): what RealTimeAudioDataOverlapper, both FFTAnalysers and the
+    // PitchAnalyser hand out after their enable...NeedsUpdating flags (RealTimeAudioAnalysis.h:221-232,268-283, PitchAnalyser.h:30-72).
+    // requestDisplayBuffers arms every flag of these channels; the next analysis call that analyses a frame captures its first frame.
+    struct DisplayBuffers
+    {
+        std::vector<float> bufferToDraw;                      // [N]  getBufferToDraw
+        std::vector<float> fftBufferToDraw;                   // [2N] the spectral analyser's getFFTBufferToDraw
+        std::vector<float> pitchFFTBufferToDraw;              // [2N] the harmonic analyser's getFFTBufferToDraw
+        std::vector<float> autoCorrelationBufferToDraw;       // [N]  getAutoCorrelationBufferToDraw
+        std::vector<float> cumulativeDifferenceBufferToDraw;  // [N]  getCumulativeDifferenceBufferToDraw
+        float normalisedLagPosition[2];                       // getNormalisedLagPosition (x, y)
+        long long frameIndex;                                 // which frame of the channel's stream was captured
+    };
+    void requestDisplayBuffers (std::vector<int> channelsToArm)
+    {
+        check (fx_request_taps (ctx, channelsToArm.data(), (int) channelsToArm.size()));
+    }
+    DisplayBuffers getDisplayBuffers (int channel)
+    {
+        DisplayBuffers b;
+        b.bufferToDraw.resize ((size_t) window);
+        b.fftBufferToDraw.resize (2 * (size_t) window);
+        b.pitchFFTBufferToDraw.resize (2 * (size_t) window);
+        b.autoCorrelationBufferToDraw.resize ((size_t) window);
+        b.cumulativeDifferenceBufferToDraw.resize ((size_t) window);
+        b.frameIndex = -1;
+        check (fx_get_taps (ctx, channel, b.bufferToDraw.data(), b.fftBufferToDraw.data(), b.pitchFFTBufferToDraw.data(),
+                            b.autoCorrelationBufferToDraw.data(), b.cumulativeDifferenceBufferToDraw.data(), b.normalisedLagPosition,
+                            &b.frameIndex));
+        return b;
+    }
+
     // hops [channels][numHops][window/2] host floats -> raw / smoothed [channels][numHops][12]
     void pushHops (const float* hops, int numHops, float* raw, float* smoothed)
     {
