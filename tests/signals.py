@@ -129,3 +129,27 @@ def assert_features_close(got, want, rtol=1e-5, names=None, what=""):
         raise AssertionError("%s: %d values beyond rtol=%g; first: row %d slot %d (%s): got %r want %r"
                              % (what, len(bad), rtol, r, f, names[f] if names else f, got.reshape(-1, 12)[r, f], want.reshape(-1, 12)[r, f]))
     return float(err.max()) if err.size else 0.0
+
+
+# ---- ulp budgets (the table and the distance live in oracle/ulp.py, which tools/stress_parity.py judges by too) ----
+from oracle.ulp import SLOTS, ULP_BUDGET, ULP_INFINITE, ulp_budget, ulp_distance  # noqa: E402,F401
+
+
+def assert_features_within(got, want, budget, names=SLOTS, what=""):
+    """every slot within its ulp budget (a 12-vector, ulp_budget()); onset (slot 0) bit-exact; NaN == NaN, inf == inf.
+    Returns the largest distance seen per slot."""
+    got = np.asarray(got, np.float32)
+    want = np.asarray(want, np.float32)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    budget = np.asarray(budget, np.int64)
+    assert budget.shape == (12,) and budget[0] == 0, budget
+    g = got.reshape(-1, 12)
+    w = want.reshape(-1, 12)
+    assert np.array_equal(g[:, 0], w[:, 0], equal_nan=True), "%s onset column differs at rows %s" % (what, np.nonzero(g[:, 0] != w[:, 0])[0][:8])
+    d = ulp_distance(g, w)
+    bad = np.argwhere(d > budget[None, :])
+    if bad.size:
+        r, f = bad[0]
+        raise AssertionError("%s: %d values beyond their ulp budget; first: row %d slot %d (%s): got %r want %r, %d ulp > %d"
+                             % (what, len(bad), r, f, names[f] if names else f, g[r, f], w[r, f], d[r, f], budget[f]))
+    return d.max(axis=0) if d.size else np.zeros(12, np.int64)

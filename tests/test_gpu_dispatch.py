@@ -1,8 +1,10 @@
 """Every analysis dispatch path of tests/dispatch_paths.py on the device: a stream of calls through the row's entry point and configuration,
 long enough (more than HLEN = 48 hops, at least three calls) that the smoothing ring, an onset window of 21 and the flux state are carried
 across calls.  For each call: (a) the launches it made (fx_last_launches_internal) are the row's; (b) its raw and smoothed vectors are the
-oracle's -- onsets exactly, the other slots within 1e-5; (c) they are, bit for bit, what one fx_push_hops call over all of the stream's
-frames gives with default tuning (fx_process_frames for rows of pre-assembled windows).  Across the table: no epilogue is asked to write
+oracle's -- onsets exactly, the other slots within the default family's ulp budget (oracle/ulp.py; FX_LOW_LATENCY rows: that family's);
+(c) they are, bit for bit, what one fx_push_hops call over all of the stream's frames gives with default tuning (fx_process_frames for rows
+of pre-assembled windows); (d) the smoothed vectors and the onset column are, bit for bit, what the reference's tail makes of the raw
+stream (tests/tail_model.py), every channel.  Across the table: no epilogue is asked to write
 strided rows for more than one frame, and fx_last_kernel_ms answers as include/fx.h says (every call with call_timing = 1; by default
 exactly the calls whose launches analyse more than one frame each).  Ring steps are outside fx_last_kernel_ms' contract."""
 import numpy as np
@@ -10,6 +12,7 @@ import pytest
 
 import dispatch_paths as dp
 import signals
+import tail_model
 
 pytestmark = pytest.mark.gpu
 
@@ -154,8 +157,11 @@ def test_dispatch_path(gpu_fx, oracle, cus, r):
     x = _floats(hops[sel], r.fmt)
     settings = dict(onset_window=ONSET_WINDOW, analysers=MASKS[r.analysers])
     oraw, osm = oracle.process_frames(_windows(x), r.N, **settings) if r.entry == "frames" else oracle.push_hops(x, r.N, **settings)
-    signals.assert_features_close(raw[sel], oraw, 1e-5, oracle.FEATURE_NAMES, r.id + " raw")
-    signals.assert_features_close(sm[sel], osm, 1e-5, oracle.FEATURE_NAMES, r.id + " smoothed")
+    budget = signals.ulp_budget("low_latency" if r.low_latency else "default")
+    signals.assert_features_within(raw[sel], oraw, budget, oracle.FEATURE_NAMES, r.id + " raw")
+    signals.assert_features_within(sm[sel], osm, budget, oracle.FEATURE_NAMES, r.id + " smoothed")
+    # (d) the tail, exactly
+    tail_model.assert_tail_exact(raw, sm, [(0, "onset_window", ONSET_WINDOW)], analysers=MASKS[r.analysers], what=r.id)
     if timed is None:
         return
     # fx_last_kernel_ms: by default exactly the calls include/fx.h names; with call_timing = 1 every call that analysed frames

@@ -7,12 +7,12 @@ import signals
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-5
+BUDGET = signals.ulp_budget("low_latency")          # per-slot ulp budget of the family (oracle/ulp.py)
 
 
 def close(got, want, what):
     from oracle import fx_oracle as fo
-    return signals.assert_features_close(got, want, RTOL, fo.FEATURE_NAMES, what)
+    return signals.assert_features_within(got, want, BUDGET, fo.FEATURE_NAMES, what)
 
 
 def analysers(gpu_fx, C, N, **kw):

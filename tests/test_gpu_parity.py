@@ -1,6 +1,7 @@
 """GPU parity tests: the HIP path, called through the C ABI (include/fx.h), against the CPU oracle
-on the same inputs.  Bar: onset bit-exact; every other slot within 1e-5 relative (BASELINE.json
-north_star); NaN/inf must match exactly.  All tests here need a real MI355X."""
+on the same inputs.  Bar: onset and f0 bit-exact; every other slot within its per-slot ulp budget (oracle/ulp.py
+ULP_BUDGET, measured in profiles/r07_ulp_stress.txt; a regression guard far inside BASELINE.json's north star of 1e-5
+relative); NaN/inf must match exactly.  The tail is held to tests/tail_model.py bit for bit.  All tests here need a real MI355X."""
 import glob
 import os
 
@@ -8,17 +9,18 @@ import numpy as np
 import pytest
 
 import signals
+import tail_model
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-5
+BUDGET = signals.ulp_budget("default")            # per-slot ulp budget (oracle/ulp.py)
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz")))
 SIZES = [256, 512, 1024, 2048, 4096]
 
 
 def close(got, want, what):
     from oracle import fx_oracle as fo
-    return signals.assert_features_close(got, want, RTOL, fo.FEATURE_NAMES, what)
+    return signals.assert_features_within(got, want, BUDGET, fo.FEATURE_NAMES, what)
 
 
 @pytest.mark.parametrize("N", SIZES)
@@ -118,6 +120,9 @@ def test_settings_changed_mid_stream(gpu_fx, oracle):
     for (raw, sm), w in zip(got, want):
         close(raw, np.stack([x[0] for x in w]), "mid-stream raw")
         close(sm, np.stack([x[1] for x in w]), "mid-stream smoothed")
+    # the tail, exactly: what the reference's tail makes of the device's raw stream, the same setter calls in between
+    events = [(11, "onset_window", 4), (11, "gain", 0.5), (23, "onset_type", 0), (23, "sample_rate", 44100.0)]
+    tail_model.assert_tail_exact(np.concatenate([g[0] for g in got], 1), np.concatenate([g[1] for g in got], 1), events, what="mid-stream")
 
 
 @pytest.mark.parametrize("N", [1024, 4096])
@@ -352,6 +357,8 @@ def test_hop_stream_settings_change_mid_stream(gpu_fx, monkeypatch, graph):
         assert np.array_equal(np.concatenate([g[k] for g in got], 1), np.concatenate([w[k] for w in want], 1), equal_nan=True)
     assert np.array_equal(an.get_features(), ref.get_features(), equal_nan=True)
     st.close()
+    events = [(3 * B, "onset_window", 4), (6 * B, "onset_type", 2), (6 * B, "sensitivity", 0.2), (10 * B, "reset")]
+    tail_model.assert_tail_exact(np.concatenate([g[0] for g in got], 1), np.concatenate([g[1] for g in got], 1), events, what="ring, graph=" + graph)
 
 
 @pytest.mark.parametrize("N,C,order", [(1024, 5, 0), (2048, 3, 0), (4096, 1, 0), (4096, 4, 0), (1024, 70, 1), (2048, 2, 2)])

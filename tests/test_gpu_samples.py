@@ -65,8 +65,8 @@ def test_blocks_of_any_length_equal_push_hops_bitwise(gpu_fx, oracle, N, block, 
     # and the oracle, on the floats the kernels widen the samples to
     floats = hops.astype(np.float32) / np.float32(32768.0) if fmt == "s16" else hops
     oraw, osm = oracle.push_hops(floats, N, gain=0.75)
-    signals.assert_features_close(want[0], oraw, 1e-5, oracle.FEATURE_NAMES, "raw")
-    signals.assert_features_close(want[1], osm, 1e-5, oracle.FEATURE_NAMES, "smoothed")
+    signals.assert_features_within(want[0], oraw, signals.ulp_budget(), oracle.FEATURE_NAMES, "raw")
+    signals.assert_features_within(want[1], osm, signals.ulp_budget(), oracle.FEATURE_NAMES, "smoothed")
 
 
 @pytest.mark.parametrize("name,block", [("tone_2048", 480), ("bursts_1024_harmfirst", 441)])
@@ -79,8 +79,8 @@ def test_committed_fixtures_through_device_blocks(gpu_fx, name, block):
     raw, sm = feed_blocks(an, hops.reshape(C, -1), block)
     assert raw.shape == (C, T, 12)
     from oracle import fx_oracle as fo
-    signals.assert_features_close(raw, g["raw"], 1e-5, fo.FEATURE_NAMES, "golden raw")
-    signals.assert_features_close(sm, g["smoothed"], 1e-5, fo.FEATURE_NAMES, "golden smoothed")
+    signals.assert_features_within(raw, g["raw"], signals.ulp_budget(), fo.FEATURE_NAMES, "golden raw")
+    signals.assert_features_within(sm, g["smoothed"], signals.ulp_budget(), fo.FEATURE_NAMES, "golden smoothed")
 
 
 def test_the_reference_collectors_own_vectors(gpu_fx):
@@ -108,8 +108,8 @@ def test_the_reference_collectors_own_vectors(gpu_fx):
 
             got = replay(stream, N, block, events, push_block, an.set_gain, an.clear_buffer, control)
             raw, sm = np.concatenate([x[0] for x in got], axis=1), np.concatenate([x[1] for x in got], axis=1)
-            signals.assert_features_close(raw, g[name + "_raw"], 1e-5, fo.FEATURE_NAMES, name + " raw")
-            signals.assert_features_close(sm, g[name + "_smoothed"], 1e-5, fo.FEATURE_NAMES, name + " smoothed")
+            signals.assert_features_within(raw, g[name + "_raw"], signals.ulp_budget(), fo.FEATURE_NAMES, name + " raw")
+            signals.assert_features_within(sm, g[name + "_smoothed"], signals.ulp_budget(), fo.FEATURE_NAMES, name + " smoothed")
             assert an.pending_samples() == stream.shape[1] % (N // 2)
             an.close()
 
@@ -416,8 +416,8 @@ def test_the_applications_own_stepping_replayed_hop_by_hop(gpu_fx):
         an = gpu_fx.BatchAnalyser(C, N, order=order)
         parts = [an.push_hops(hops[:, t:t + 1]) for t in range(hops.shape[1])]          # one hop per call, as the app analyses them
         raw, sm = np.concatenate([p[0] for p in parts], 1), np.concatenate([p[1] for p in parts], 1)
-        signals.assert_features_close(raw, g[name + "_raw"], 1e-5, fo.FEATURE_NAMES, name + " raw")
-        signals.assert_features_close(sm, g[name + "_smoothed"], 1e-5, fo.FEATURE_NAMES, name + " smoothed")
+        signals.assert_features_within(raw, g[name + "_raw"], signals.ulp_budget(), fo.FEATURE_NAMES, name + " raw")
+        signals.assert_features_within(sm, g[name + "_smoothed"], signals.ulp_budget(), fo.FEATURE_NAMES, name + " smoothed")
         an.close()
 
 

@@ -60,4 +60,4 @@ def test_live_soak_drops_nothing_and_matches_the_oracle(gpu_fx, oracle, tmp_path
     for k, c in enumerate(sample):
         ch = oracle.Channel(N)
         _, osm = ch.push_hops(hops[k])
-        signals.assert_features_close(smoothed[c][None, None], osm[-1][None, None], 1e-5, oracle.FEATURE_NAMES, "channel %d after %d hops" % (c, hops.shape[1]))
+        signals.assert_features_within(smoothed[c][None, None], osm[-1][None, None], signals.ulp_budget(), oracle.FEATURE_NAMES, "channel %d after %d hops" % (c, hops.shape[1]))

@@ -1,5 +1,7 @@
 """Randomised parity stress: HIP path (through the C ABI) vs the CPU oracle over random signal mixes,
-levels, window sizes, batch shapes and settings.  Prints every mismatch beyond 1e-5 (onset: any)."""
+levels, window sizes, batch shapes and settings.  Judges every value against the per-slot ulp budget of its kernel family
+(oracle/ulp.py ULP_BUDGET; onset and f0 exact), prints every case beyond it, and reports per family, per slot the largest
+ulp distance and a histogram of the distances, for raw and smoothed values."""
 import importlib
 import os
 import sys
@@ -18,15 +20,50 @@ THREADS = usable_cores()
 
 
 from stress_signals import make_signal  # noqa: E402
+from oracle.ulp import ulp_budget, ulp_distance  # noqa: E402
+
+FAMILIES = ("default", "low_latency")
+KINDS = ("raw", "smoothed")
+BUCKETS = (0, 1, 2, 3, 4, 8, 16)            # histogram edges: 0, 1, 2, 3, 4, 5-8, 9-16, >16 ulp
 
 
-def run(seconds=60.0, seed=0, max_cases=None, save_failures=True, verbose=True, windows=(256, 512, 1024, 1024, 2048, 2048, 4096), block_share=0.15):
-    """Returns (cases, frames, mismatching cases, worst finite relative error)."""
+def _bucket_counts(d):
+    """d [...][12] ulp distances -> [12][len(BUCKETS) + 1] counts"""
+    edges = np.array(BUCKETS, np.int64)
+    idx = np.searchsorted(edges, d.reshape(-1, 12), side="left")
+    out = np.zeros((12, len(BUCKETS) + 1), np.int64)
+    for f in range(12):
+        out[f] = np.bincount(idx[:, f], minlength=len(BUCKETS) + 1)
+    return out
+
+
+def report(ulp):
+    """the per-family, per-slot table of stats["ulp"]"""
+    labels = ["0", "1", "2", "3", "4", "5-8", "9-16", ">16"]
+    lines = []
+    for fam in FAMILIES:
+        for kind in KINDS:
+            st = ulp[fam][kind]
+            lines.append("%s %s (%d values per slot): max ulp per slot, then histogram %s" % (fam, kind, int(st["hist"][0].sum()), " / ".join(labels)))
+            for f in range(12):
+                h = st["hist"][f]
+                nz = " ".join("%s:%d" % (labels[i], int(n)) for i, n in enumerate(h) if n and i)
+                lines.append("  %-9s max %-3d %s%s" % (fx.FEATURE_NAMES[f], int(st["max"][f]), nz or "all exact",
+                                                      ("   worst: " + st["where"][f]) if st["where"][f] else ""))
+    return "\n".join(lines)
+
+
+def run(seconds=60.0, seed=0, max_cases=None, save_failures=True, verbose=True, windows=(256, 512, 1024, 1024, 2048, 2048, 4096), block_share=0.15,
+        stats=None):
+    """Returns (cases, frames, mismatching cases, worst finite relative error); a dict passed as `stats` receives the ulp
+    statistics under "ulp"."""
     rng = np.random.default_rng(seed)
     t_end = time.time() + seconds
     cases = frames = bad_cases = 0
     worst = 0.0
-    inexact = np.zeros(12, np.int64)      # values that are within tolerance but not bit-identical, per slot
+    inexact = np.zeros(12, np.int64)      # raw values that are within budget but not bit-identical, per slot
+    ulp = dict((fam, dict((k, {"max": np.zeros(12, np.int64), "hist": np.zeros((12, len(BUCKETS) + 1), np.int64), "where": [""] * 12})
+                          for k in KINDS)) for fam in FAMILIES)
     ring_cases = [0]
     pair_cases = [0]
     hop_cases = [0]
@@ -66,9 +103,11 @@ def run(seconds=60.0, seed=0, max_cases=None, save_failures=True, verbose=True, 
         an = fx.BatchAnalyser(C, N, order=order, analysers=which)
         an.set_onset_detection_type(otype); an.set_onset_window_length(owin)
         an.set_onset_detection_sensitivity(sens); an.set_gain(gain)
+        family = "default"
         if which == "both" and N >= 2048 and rng.random() < 0.5:
             # one frame across a PAIR of wavefronts: fx_pair_kernel for the batch calls, fx_hop_pair_kernel for one-hop calls
             an.set_tuning(waves_per_frame=2)
+            family = "low_latency"
             pair_cases[0] += 1
         split = int(rng.integers(0, T + 1))
         ring = which == "both" and N >= 1024 and T <= 24 and rng.random() < 0.25
@@ -152,8 +191,16 @@ def run(seconds=60.0, seed=0, max_cases=None, save_failures=True, verbose=True, 
             with np.errstate(invalid="ignore", divide="ignore"):
                 err = np.where(same, 0.0, np.abs(g64 - w64) / np.abs(w64))
             err = np.where(np.isnan(err), np.inf, err)
-            tol = np.full(12, 1e-5); tol[0] = 0.0
-            bad = np.argwhere(err > tol)
+            d = ulp_distance(g, w)
+            us = ulp[family][name]
+            us["hist"] += _bucket_counts(d)
+            dmax = d.reshape(-1, 12).max(axis=0)
+            for f in np.nonzero(dmax > us["max"])[0]:
+                c, t = np.unravel_index(int(np.argmax(d[..., f])), d.shape[:2])
+                us["max"][f] = dmax[f]
+                us["where"][f] = "N=%d C=%d T=%d order=%d analysers=%s otype=%d owin=%d seed=%d case=%d c=%d t=%d gpu=%r oracle=%r" % (
+                    N, C, T, order, which, otype, owin, seed, cases - 1, c, t, float(g[c, t, f]), float(w[c, t, f]))
+            bad = np.argwhere(d > ulp_budget(family)[None, None, :])
             worst = max(worst, float(np.max(np.where(np.isfinite(err), err, 0))))
             if name == "raw":
                 inexact += np.count_nonzero(~same, axis=(0, 1))
@@ -165,8 +212,8 @@ def run(seconds=60.0, seed=0, max_cases=None, save_failures=True, verbose=True, 
                                         otype=otype, owin=owin, sens=sens, gain=gain, split=split, gpu_raw=raw, oracle_raw=oraw, which=name)
                 c, t, f = bad[0]
                 if verbose:
-                    print("MISMATCH %s N=%d C=%d T=%d order=%d otype=%d owin=%d: %d values; first c=%d t=%d %s gpu=%r oracle=%r"
-                          % (name, N, C, T, order, otype, owin, len(bad), c, t, fx.FEATURE_NAMES[f], g[c, t, f], w[c, t, f]), flush=True)
+                    print("MISMATCH %s %s N=%d C=%d T=%d order=%d otype=%d owin=%d: %d values beyond budget; first c=%d t=%d %s gpu=%r oracle=%r (%d ulp)"
+                          % (family, name, N, C, T, order, otype, owin, len(bad), c, t, fx.FEATURE_NAMES[f], g[c, t, f], w[c, t, f], d[c, t, f]), flush=True)
     if verbose:
         print("cases run one hop per call through the ring (fx_hop_kernel / fx_hop_pair_kernel): %d; cases on wavefront pairs (fx_pair_kernel): %d; "
               "cases hop by hop through fx_push_hops (half of them on the batch kernels + one-frame fused tail): %d; cases fed as 16- or 24-bit PCM: %d; "
@@ -174,7 +221,11 @@ def run(seconds=60.0, seed=0, max_cases=None, save_failures=True, verbose=True, 
               "where a call completes one hop and the one-frame kernels read the block themselves)"
               % (ring_cases[0], pair_cases[0], hop_cases[0], pcm_cases[0], block_cases[0], block_frames[0], fed_cases[0]), flush=True)
     if verbose and inexact.any():
-        print("raw values not bit-identical (within tolerance), per slot:", dict((fx.FEATURE_NAMES[i], int(n)) for i, n in enumerate(inexact) if n), flush=True)
+        print("raw values not bit-identical (within budget), per slot:", dict((fx.FEATURE_NAMES[i], int(n)) for i, n in enumerate(inexact) if n), flush=True)
+    if verbose:
+        print(report(ulp), flush=True)
+    if stats is not None:
+        stats["ulp"] = ulp
     return cases, frames, bad_cases, worst
 
 
