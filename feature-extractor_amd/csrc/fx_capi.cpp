@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -249,20 +250,7 @@ fx_status fx_check_device_error(fx_context* c)
     return FX_OK;
 }
 
-namespace {
-
-// Everything one analysis step launches: kernel arguments and the wavefront count of the frame kernel.
-struct Step {
-    fxk::FrameParams    fp;
-    fxk::EpilogueParams ep;
-    int analysers = 3;
-    int waves = 1;
-    bool pair = false;      // fx_pair_kernel: one frame across two wavefronts (fp.waves_per_ch counts pairs)
-    bool hop_pairs = false; // a one-frame call through fx_hop_pair_kernel (six wavefronts per channel) instead of fx_hop_kernel (three)
-};
-
 // The launch record (fx_last_launches_internal): a handful of host stores per launch; each entry point that launches starts it anew.
-void begin_launches(fx_context* c) { if (c) c->num_launches = 0; }
 fx_launch_record* note_launch(fx_context* c, int kind, int analysers)
 {
     const int i = c->num_launches++;
@@ -274,41 +262,78 @@ fx_launch_record* note_launch(fx_context* c, int kind, int analysers)
     r.analysers = analysers;
     return &r;
 }
-void note_step(fx_context* c, int kind, const Step& st)
-{
-    fx_launch_record* r = note_launch(c, kind, st.analysers);
-    if (!r) return;
-    const bool hop = kind == FX_LAUNCH_HOP || kind == FX_LAUNCH_HOP_PAIR;
-    if (kind != FX_LAUNCH_EPILOGUE) {
-        r->T = st.fp.T; r->direct_state = st.fp.direct_state; r->block_mode = st.fp.block_mode;
-        if (!hop) { r->num_chunks = st.fp.num_chunks; r->ch_per_wg = st.fp.ch_per_wg; r->waves_per_ch = st.fp.waves_per_ch; }
-        else r->hop_pairs = st.hop_pairs ? 1 : 0;
-    }
-    if (kind != FX_LAUNCH_FRAME && kind != FX_LAUNCH_PAIR) { r->ep_T = st.ep.T; r->out_stride = st.ep.out_stride; }
-    if (kind == FX_LAUNCH_EPILOGUE) r->ep_form = fxk::epilogue_form(st.ep);
-}
 
-hipError_t launch_frames(fx_context* c, const Step& st)
-{
-    note_step(c, st.pair ? FX_LAUNCH_PAIR : FX_LAUNCH_FRAME, st);
-    return st.pair ? fxk::launch_pair_kernel(c->N, st.fp, c->stream) : fxk::launch_frame_kernel(c->N, st.fp, st.analysers, c->stream);
-}
+namespace {
 
-// Fill the kernel arguments of a step over T frames per channel from the context's current state.  `part` / `raw`
-// default to the context's own (growable) scratch; a captured step passes buffers it owns, because a graph keeps the
-// addresses it was captured with.
-fx_status prepare_step(fx_context* c, const void* d_in, int T, int sample_format, int hop_mode, float* d_or, float* d_os,
-                       fxk::FramePart* part, float* raw, const fxk::DynParams* dyn, Step* st)
+void begin_launches(fx_context* c) { if (c) c->num_launches = 0; }
+
+// One launch of an analysis call: which launcher (FX_LAUNCH_*: frame, pair, frame_tail, hop, hop_pair, epilogue) and its arguments.
+struct Launch {
+    int kind = 0;
+    fxk::FrameParams    fp;
+    fxk::EpilogueParams ep;
+    int analysers = 3;
+};
+// Everything one analysis call launches, in order, and whether fx_last_kernel_ms times it.  Built whole before anything is enqueued.
+struct Plan {
+    Launch launch[4];
+    int n = 0;
+    int parts = 1;          // steps of the context's state: a call cut into one-frame launches takes one per frame, others one
+    bool timed = false;
+};
+// route: the library picks the kernels (run()), or a ring step fixes them: the one-launch hop kernel, or the captured step (frame or
+// pair kernel + epilogue, never cut in time or in frames: a graph replays what it was captured with)
+enum Route { ROUTE_AUTO, ROUTE_RING_HOP, ROUTE_RING_CAPTURED };
+
+// fx_push_samples' call that completes exactly one hop, without the re-blocking pass: `in` of run() is then the device BLOCK of every
+// channel (rows of in_row_bytes) and the one-frame kernels read the hop from [pending samples | block] themselves and write the new
+// pending samples (FrameParams::block_mode, csrc/fx_blocks.hip.h)
+struct BlockFeed {
+    const unsigned char* carry_in;
+    unsigned char*       carry_out;
+    int                  carry_bytes, carry_row_bytes;
+    long long            in_row_bytes;
+};
+
+// Plan the launches of a call of T frames per channel from the context's current state: no HIP call, no change to the context.  `part` /
+// `raw` are the epilogue's scratch (the context's own for run(); a captured step passes buffers it owns, because a graph keeps the
+// addresses it was captured with); `dyn`: the per-call scalars a captured step reads from memory.
+fx_status plan_call(const fx_context* c, const void* d_in, int T, int sample_format, int hop_mode, float* d_or, float* d_os,
+                    const BlockFeed* blocks, const fxk::DynParams* dyn, fxk::FramePart* part, float* raw, Route route, Plan* plan)
 {
-    fxk::FrameParams& fp = st->fp;
+    const int analysers = (c->flags & FX_SPECTRAL_ONLY) ? 1 : ((c->flags & FX_HARMONIC_ONLY) ? 2 : 3);
+    // The low-latency family (opt-in: FX_LOW_LATENCY, or fx_tuning::waves_per_frame = 2): windows of 2048 / 4096 points with both
+    // analysers run one frame across a PAIR of wavefronts -- fx_pair_kernel for calls of several frames, fx_hop_pair_kernel for
+    // one frame per call.  The default family keeps a frame in one wavefront at every size (DESIGN.md 3.3, profiles/NOTEBOOK_design_r1-r5.md: pairs are the faster
+    // path for one hop, not for throughput).
+    const bool pair = uses_pairs(c, c->tuning.waves_per_frame);
+
+    // A call of TWO hops per channel (a 1024-sample device buffer against a 1024-point window, 960-sample blocks every other call ...) runs
+    // as two one-frame launches over the same buffers -- the second reads hop 1 and writes frame 1 (FrameParams::in_hop_stride / in_hop0,
+    // EpilogueParams::out_stride / out_t0) -- and, like a one-frame call, records no timing events unless asked to.  Measured
+    // (tools/device_blocks.py, us per call of two hops: batch form with its events / batch form without / two one-frame launches):
+    // 8192 channels x 1024 points 144 / 136.6 / 133.8; 1024 x 1024 52 / 42.6 / 39.7; 4096 x 2048 165 / 154.9 / 157.1; 512 x 2048 - / 50.4 / 46.3;
+    // 1024 x 4096 137 / 127.1 / 123.4; 256 x 4096 - / 66.7 / 57.1.  Most of what a two-hop call cost over two one-hop calls was the three event
+    // records (barrier packets); the launches themselves are worth 0 - 14 %.  What this form really buys is the block feed: a block that
+    // completes two hops is read by the kernels directly (1000-sample blocks at 8192 channels: 177 -> 132 us per call).
+    const bool in_two = hop_mode && T == 2 && analysers == 3 && c->N >= 1024 && !pair && !(c->test_hooks & FX_HOOK_NO_TWO_LAUNCHES);
+    const bool split = route == ROUTE_AUTO && (in_two || (blocks && T <= 2));   // (a block feed of more hops is ONE launch of the batch kernel's block-fed form)
+    plan->parts = split ? T : 1;
+    const int part_T = split ? 1 : T;
+    // The three events fx_last_kernel_ms() reads.  Each is a barrier packet between launches, which a call of milliseconds does not
+    // notice and a one-frame call does (back to back 27 us per call with them, 14.6 without): those record none unless asked to.
+    // (a call made of one-frame launches is a live call: no events by default, like a one-frame call; a ring step records none)
+    plan->timed = route == ROUTE_AUTO && (c->profiling || c->tuning.call_timing == 1 || (c->tuning.call_timing < 0 && part_T > 1));
+
+    Launch base;
+    base.analysers = analysers;
+    fxk::FrameParams& fp = base.fp;
     fp.in = d_in;
     fp.sample_format = sample_format;
     fp.hop_mode = hop_mode;
-    fp.T = T;
+    fp.T = part_T;
     fp.C = c->C;
     fp.gain = c->gain;
-    fp.tail_in = c->d_tail[c->cur];
-    fp.tail_out = c->d_tail[c->cur ^ 1];
     fp.prev_re = c->d_prev;
     fp.tw = c->d_tw;
     fp.tw_image = c->d_tw + 2 * (size_t) c->N;
@@ -329,68 +354,60 @@ fx_status prepare_step(fx_context* c, const void* d_in, int T, int sample_format
     // context has fewer or the LDS holds fewer (one twiddle table per workgroup, one flux state per channel, one
     // transform buffer per wave).  fx_tuning overrides for experiments.
     const size_t lds_cu = 160 * 1024;
-    st->analysers = (c->flags & FX_SPECTRAL_ONLY) ? 1 : ((c->flags & FX_HARMONIC_ONLY) ? 2 : 3);
-    // The low-latency family (opt-in: FX_LOW_LATENCY, or fx_tuning::waves_per_frame = 2): windows of 2048 / 4096 points with both
-    // analysers run one frame across a PAIR of wavefronts -- fx_pair_kernel for calls of several frames, fx_hop_pair_kernel for
-    // one frame per call.  The default family keeps a frame in one wavefront at every size (DESIGN.md 3.3, profiles/NOTEBOOK_design_r1-r5.md: pairs are the faster
-    // path for one hop, not for throughput).
-    st->pair = st->hop_pairs = uses_pairs(c, c->tuning.waves_per_frame);
-    {
-        const int kcap = st->pair ? fxk::pair_kernel_max_pairs(c->N) : fxk::frame_kernel_max_waves(c->N);
-        // one frame per call through the batch kernels (both analysers): the flux state stays in global memory (FrameParams::direct_state)
-        const bool direct = T == 1 && !st->pair && st->analysers == 3;
-        fp.direct_state = direct ? 1 : 0;
-        auto lds_bytes = [&](int ch_, int k_) { return st->pair ? fxk::pair_kernel_lds_bytes(c->N, ch_, k_) : fxk::frame_kernel_lds_bytes(c->N, ch_, k_, direct); };
-        int ch = 1, k = 1;
-        if (st->pair) { ch = 1; k = kcap; }
-        else fxk::frame_kernel_preferred_shape(c->N, &ch, &k);
-        if (c->tuning.waves_per_channel >= 1) k = c->tuning.waves_per_channel;
-        if (c->tuning.channels_per_workgroup >= 1) ch = c->tuning.channels_per_workgroup;
-        if (k > T) k = T;
-        if (k > kcap) k = kcap;
-        // one frame per call through the batch kernels: one wavefront per channel, so channels share a workgroup's twiddle table.
-        // With the flux state in global memory (direct), up to 1024 points as many as a workgroup may hold (1024 points: 8 channels =
-        // 76 KB, two workgroups and 16 wavefronts per CU -- what the LDS holds of the batch shape too); at the split sizes the registers
-        // allow 8 wavefronts per CU whatever the shape, and a CU does better with two workgroups of four (staggered) than with one of
-        // eight in lockstep (2048 points), or with one workgroup of eight from the channel count at which every CU has one (4096 points,
-        // whose eight wavefronts are all a CU holds).  Measured, us per call of one hop per channel, channels per workgroup 4 / 8 --
-        // profiles/r04_live_cadence.txt:
-        //   1024 points  4096 ch 43.4 / 39.1   8192 ch 66.6 / 63.3   16384 ch 116.8 / 111.1
-        //   2048 points  2048 ch 44.8 / 43.2   4096 ch 72.0 / 73.0    8192 ch 125.4 / 133.6
-        //   4096 points  1024 ch 61.7 / 71.0   2048 ch 108.7 / 75.7   4096 ch 205.4 / 139.6
-        // Without the direct form (one analyser only): four (2048 points, 4096 channels x 1 hop 152 us against 193 us with one).
-        if (T == 1 && !st->pair && c->tuning.channels_per_workgroup < 1)
-            ch = !direct ? 4 : (c->N <= 1024 ? kcap : (c->N == 2048 ? 4 : (c->C >= 2048 ? kcap : 4)));
-        // Two frames per call (a 1024-sample device block against a 1024-point window: the live cadence of hosts with larger buffers): two channels
-        // per workgroup share the twiddle table.  Measured (tools/device_blocks.py, us per call of two hops, channels per workgroup 1 / 2 / 4):
-        // 8192 channels x 1024 points 164.8 / 144.4 / 183.3; 4096 channels x 2048 points 169.8 / 163.5 / 172.9.  Four frames per call: one.
-        if (T == 2 && !st->pair && c->N <= 2048 && c->tuning.channels_per_workgroup < 1) ch = 2;
-        if (ch > c->C) ch = c->C;
-        while (ch > 1 && (ch * k > kcap || lds_bytes(ch, k) > lds_cu)) ch--;
-        while (k > 1 && lds_bytes(ch, k) > lds_cu) k--;
-        if (lds_bytes(ch, k) > lds_cu)
-            return fx_fail(FX_ERR_UNSUPPORTED, "window size %d does not fit the LDS", c->N);
-        fp.ch_per_wg = ch;
-        fp.waves_per_ch = k;
-        st->waves = ch * k * (st->pair ? 2 : 1);
-        fp.num_chunks = 1;
-        fp.queue = nullptr;
-        fp.err = c->d_err;
-        fp.spin_limit = c->tuning.handover_spin_limit > 0 ? (unsigned) c->tuning.handover_spin_limit : (1u << 22);
-        fp.debug_flags = c->test_hooks;
-        for (int i = 0; i <= fxk::FX_MAX_CHUNKS; i++) fp.chunk_begin[i] = 0;
-        if (!dyn && c->d_queue) {
-            int sizes[fxk::FX_MAX_CHUNKS];
-            const int n = fx_plan_units(c->N, c->flags, k, T, &c->tuning, sizes, fxk::FX_MAX_CHUNKS);
-            if (n >= 2) {
-                fp.num_chunks = n;
-                fp.queue = c->d_queue;
-                for (int i = 0; i < n; i++) fp.chunk_begin[i + 1] = fp.chunk_begin[i] + sizes[i];
-            }
+    const int kcap = pair ? fxk::pair_kernel_max_pairs(c->N) : fxk::frame_kernel_max_waves(c->N);
+    // one frame per call through the batch kernels (both analysers): the flux state stays in global memory (FrameParams::direct_state)
+    const bool direct = part_T == 1 && !pair && analysers == 3;
+    fp.direct_state = direct ? 1 : 0;
+    auto lds_bytes = [&](int ch_, int k_) { return pair ? fxk::pair_kernel_lds_bytes(c->N, ch_, k_) : fxk::frame_kernel_lds_bytes(c->N, ch_, k_, direct); };
+    int ch = 1, k = 1;
+    if (pair) { ch = 1; k = kcap; }
+    else fxk::frame_kernel_preferred_shape(c->N, &ch, &k);
+    if (c->tuning.waves_per_channel >= 1) k = c->tuning.waves_per_channel;
+    if (c->tuning.channels_per_workgroup >= 1) ch = c->tuning.channels_per_workgroup;
+    if (k > part_T) k = part_T;
+    if (k > kcap) k = kcap;
+    // one frame per call through the batch kernels: one wavefront per channel, so channels share a workgroup's twiddle table.
+    // With the flux state in global memory (direct), up to 1024 points as many as a workgroup may hold (1024 points: 8 channels =
+    // 76 KB, two workgroups and 16 wavefronts per CU -- what the LDS holds of the batch shape too); at the split sizes the registers
+    // allow 8 wavefronts per CU whatever the shape, and a CU does better with two workgroups of four (staggered) than with one of
+    // eight in lockstep (2048 points), or with one workgroup of eight from the channel count at which every CU has one (4096 points,
+    // whose eight wavefronts are all a CU holds).  Measured, us per call of one hop per channel, channels per workgroup 4 / 8 --
+    // profiles/r04_live_cadence.txt:
+    //   1024 points  4096 ch 43.4 / 39.1   8192 ch 66.6 / 63.3   16384 ch 116.8 / 111.1
+    //   2048 points  2048 ch 44.8 / 43.2   4096 ch 72.0 / 73.0    8192 ch 125.4 / 133.6
+    //   4096 points  1024 ch 61.7 / 71.0   2048 ch 108.7 / 75.7   4096 ch 205.4 / 139.6
+    // Without the direct form (one analyser only): four (2048 points, 4096 channels x 1 hop 152 us against 193 us with one).
+    if (part_T == 1 && !pair && c->tuning.channels_per_workgroup < 1)
+        ch = !direct ? 4 : (c->N <= 1024 ? kcap : (c->N == 2048 ? 4 : (c->C >= 2048 ? kcap : 4)));
+    // Two frames per call (a 1024-sample device block against a 1024-point window: the live cadence of hosts with larger buffers): two channels
+    // per workgroup share the twiddle table.  Measured (tools/device_blocks.py, us per call of two hops, channels per workgroup 1 / 2 / 4):
+    // 8192 channels x 1024 points 164.8 / 144.4 / 183.3; 4096 channels x 2048 points 169.8 / 163.5 / 172.9.  Four frames per call: one.
+    if (part_T == 2 && !pair && c->N <= 2048 && c->tuning.channels_per_workgroup < 1) ch = 2;
+    if (ch > c->C) ch = c->C;
+    while (ch > 1 && (ch * k > kcap || lds_bytes(ch, k) > lds_cu)) ch--;
+    while (k > 1 && lds_bytes(ch, k) > lds_cu) k--;
+    if (lds_bytes(ch, k) > lds_cu)
+        return fx_fail(FX_ERR_UNSUPPORTED, "window size %d does not fit the LDS", c->N);
+    if (blocks && (pair || analysers != 3)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "this context's kernels do not read blocks");
+    fp.ch_per_wg = ch;
+    fp.waves_per_ch = k;
+    fp.num_chunks = 1;
+    fp.queue = nullptr;
+    fp.err = c->d_err;
+    fp.spin_limit = c->tuning.handover_spin_limit > 0 ? (unsigned) c->tuning.handover_spin_limit : (1u << 22);
+    fp.debug_flags = c->test_hooks;
+    for (int i = 0; i <= fxk::FX_MAX_CHUNKS; i++) fp.chunk_begin[i] = 0;
+    if (route != ROUTE_RING_CAPTURED) {
+        int sizes[fxk::FX_MAX_CHUNKS];
+        const int n = fx_plan_units(c->N, c->flags, k, part_T, &c->tuning, sizes, fxk::FX_MAX_CHUNKS);
+        if (n >= 2) {
+            fp.num_chunks = n;
+            fp.queue = c->d_queue;
+            for (int i = 0; i < n; i++) fp.chunk_begin[i + 1] = fp.chunk_begin[i] + sizes[i];
         }
     }
 
-    fxk::EpilogueParams& ep = st->ep;
+    fxk::EpilogueParams& ep = base.ep;
     ep.part = part;
     ep.raw = raw;
     ep.nyquist = c->sample_rate / 2.0;
@@ -398,24 +415,106 @@ fx_status prepare_step(fx_context* c, const void* d_in, int T, int sample_format
     ep.window = c->N;
     fxk::epilogue_constants(ep);
     ep.hist = c->d_hist;
-    ep.hist_base = (int) (c->frames_seen % fxk::HLEN);
     ep.out_raw = d_or;
     ep.out_smoothed = d_os;
     ep.out_stride = 0; ep.out_t0 = 0;
     ep.latest = c->d_latest;
     ep.C = c->C;
-    ep.T = T;
-    ep.frames_before = c->frames_seen;
+    ep.T = part_T;
     ep.onset_reset_frame = c->onset_reset_frame;
     ep.onset_window = c->onset_window;
     ep.onset_type = c->onset_type;
     ep.onset_multiplier = c->onset_multiplier;
     ep.order_mode = (int) (c->flags & FX_ORDER_MASK);
-    ep.analysers = st->analysers;
+    ep.analysers = analysers;
     ep.dyn = dyn;
     ep.clear_queue = fp.num_chunks > 1 ? c->d_queue : nullptr;
     ep.clear_count = 1 + c->C;
+
+    // ONE frame per channel -- the reference's own cadence, an analysis per hop as it arrives (AudioDataCollector.h:66-94,
+    // RealTimeAnalyser.h:201-234) -- is one launch of fx_hop_kernel: three wavefronts per channel (pitch / spectral /
+    // harmonic) and the hop's tail, instead of one wavefront per channel and a second launch.
+    // (measured, tools/live_cadence.py, profiles/r04_live_cadence.txt: once the call holds more than the chip takes in one round of
+    // workgroups -- 1024 channels of 1024 points, 512 of 2048, and 1024 of 4096 since a 4096-point workgroup is 80 KB and a CU holds two --
+    // the batch kernels take over: one wavefront per channel with the flux state left in global memory (direct_state above), then the fused
+    // tail on a quarter wavefront per channel: 63 against 120 us at 8192 channels x 1024-pt, 76 against 186 us at 2048 channels x 4096-pt;
+    // below it the hop kernel wins, 19.9 against 22.9 us at 1024 x 1024-pt, 58.7 against 61.8 us at 1024 x 4096-pt.  The pair family's
+    // hop kernel -- six wavefronts and 100 KB per channel -- keeps 2^20 at every size)
+    const bool one_hop = route == ROUTE_RING_HOP ||
+                         (route == ROUTE_AUTO && part_T == 1 && analysers == 3 && fxk::hop_kernel_available(c->N) &&
+                          (c->tuning.one_hop_kernel == 1 || (c->tuning.one_hop_kernel < 0 && (long long) c->C * c->N <= ((c->N == 4096 && !pair) ? (1ll << 22) : (1ll << 20)))));
+    // One frame per channel through the batch kernels: frames and tails in ONE launch (fx_frame_tail_kernel) while the chip holds all
+    // of the call's workgroups at once -- two per CU at these sizes, one of eight channels at 4096 points.  Beyond that a workgroup whose
+    // first wavefronts are finishing its hops keeps the LDS the next workgroup is waiting for, and the tail is better off as a launch
+    // of its own.  Measured (us per call, one launch / two; profiles/r04_live_cadence.txt): 1024 points 2048 channels 26.8 / 28.6, 4096
+    // channels 41.0 / 41.7, 8192 channels 70.2 / 68.2; 2048 points 2048 channels 44.9 / 45.7, 4096 channels 77.5 / 73.8; windows of 512
+    // points and fewer lose either way (4096 channels 34.7 / 33.2): their frames are no longer than the tail.
+    const long long groups = ((long long) c->C + ch - 1) / ch;
+    const long long one_round = (long long) c->compute_units * ((c->N == 4096 && ch > 4) ? 1 : 2);
+    const bool one_launch = route == ROUTE_AUTO && direct && fxk::frame_tail_kernel_available(c->N) &&
+                            ((c->test_hooks & FX_HOOK_TAIL_ALWAYS_FUSED) || (!(c->test_hooks & FX_HOOK_TAIL_NEVER_FUSED) && groups <= one_round));
+    const int frames_kind = one_hop ? (pair ? FX_LAUNCH_HOP_PAIR : FX_LAUNCH_HOP) : (one_launch ? FX_LAUNCH_FRAME_TAIL : (pair ? FX_LAUNCH_PAIR : FX_LAUNCH_FRAME));
+
+    plan->n = 0;
+    for (int p = 0; p < plan->parts; p++) {
+        // part p runs on the state as parts 0 .. p-1 leave it
+        Launch l = base;
+        l.fp.tail_in = c->d_tail[c->cur ^ (p & 1)];
+        l.fp.tail_out = c->d_tail[c->cur ^ (p & 1) ^ 1];
+        l.ep.frames_before = c->frames_seen + p;
+        l.ep.hist_base = (int) ((c->frames_seen + p) % fxk::HLEN);
+        if (plan->parts > 1) {
+            l.fp.in_hop_stride = T; l.fp.in_hop0 = p;
+            l.ep.out_stride = T;    l.ep.out_t0 = p;
+        }
+        if (blocks) {
+            l.fp.block_mode = 1;
+            l.fp.blk_hop0 = p;
+            l.fp.blk_keep_rest = p == plan->parts - 1 ? 1 : 0;
+            l.fp.blk_carry_in = blocks->carry_in;
+            l.fp.blk_carry_out = blocks->carry_out;
+            l.fp.blk_carry_bytes = blocks->carry_bytes;
+            l.fp.blk_carry_row_bytes = blocks->carry_row_bytes;
+            l.fp.blk_in_row_bytes = blocks->in_row_bytes;
+        }
+        l.kind = frames_kind;
+        plan->launch[plan->n++] = l;
+        if (frames_kind == FX_LAUNCH_FRAME || frames_kind == FX_LAUNCH_PAIR) {
+            l.kind = FX_LAUNCH_EPILOGUE;
+            plan->launch[plan->n++] = l;
+        }
+    }
     return FX_OK;
+}
+
+// The launch record entry of a planned launch (a captured ring step writes these again each time its graph is replayed)
+void note_planned(fx_context* c, const Launch& l)
+{
+    fx_launch_record* r = note_launch(c, l.kind, l.analysers);
+    if (!r) return;
+    const bool hop = l.kind == FX_LAUNCH_HOP || l.kind == FX_LAUNCH_HOP_PAIR;
+    if (l.kind != FX_LAUNCH_EPILOGUE) {
+        r->T = l.fp.T; r->direct_state = l.fp.direct_state; r->block_mode = l.fp.block_mode;
+        if (!hop) { r->num_chunks = l.fp.num_chunks; r->ch_per_wg = l.fp.ch_per_wg; r->waves_per_ch = l.fp.waves_per_ch; }
+        else r->hop_pairs = l.kind == FX_LAUNCH_HOP_PAIR ? 1 : 0;
+    }
+    if (l.kind != FX_LAUNCH_FRAME && l.kind != FX_LAUNCH_PAIR) { r->ep_T = l.ep.T; r->out_stride = l.ep.out_stride; }
+    if (l.kind == FX_LAUNCH_EPILOGUE) r->ep_form = fxk::epilogue_form(l.ep);
+}
+
+// Enqueue one planned launch on the context's stream, and record it.  `sig`: the ring's hop kernel signals its slot.
+hipError_t enqueue(fx_context* c, const Launch& l, const fxk::HopSignal& sig = {})
+{
+    note_planned(c, l);
+    switch (l.kind) {
+    case FX_LAUNCH_FRAME:      return fxk::launch_frame_kernel(c->N, l.fp, l.analysers, c->stream);
+    case FX_LAUNCH_PAIR:       return fxk::launch_pair_kernel(c->N, l.fp, c->stream);
+    case FX_LAUNCH_FRAME_TAIL: return fxk::launch_frame_tail_kernel(c->N, l.fp, l.ep, c->stream);
+    case FX_LAUNCH_EPILOGUE:   return fxk::launch_epilogue_kernels(l.ep, c->stream);
+    case FX_LAUNCH_HOP:
+    case FX_LAUNCH_HOP_PAIR:   return fxk::launch_hop_kernel(c->N, l.fp, l.ep, sig, c->stream, l.kind == FX_LAUNCH_HOP_PAIR);
+    default:                   return hipErrorInvalidValue;       // (a kind plan_call does not make)
+    }
 }
 
 void fill_dyn(const fx_context* c, fxk::DynParams* d)
@@ -430,21 +529,12 @@ void fill_dyn(const fx_context* c, fxk::DynParams* d)
     d->onset_type = c->onset_type;
 }
 
+// once a part's launches are enqueued: the state they leave
 void advance(fx_context* c, int T)
 {
     c->cur ^= 1;
     c->frames_seen += T;
 }
-
-// fx_push_samples' call that completes exactly one hop, without the re-blocking pass: `in` of run() is then the device BLOCK of every
-// channel (rows of in_row_bytes) and the one-frame kernels read the hop from [pending samples | block] themselves and write the new
-// pending samples (FrameParams::block_mode, csrc/fx_blocks.hip.h)
-struct BlockFeed {
-    const unsigned char* carry_in;
-    unsigned char*       carry_out;
-    int                  carry_bytes, carry_row_bytes;
-    long long            in_row_bytes;
-};
 
 // Whether this context's one-hop calls can take blocks directly: windows from 1024 points, both analysers, the default kernel family
 // (the pair family and the single-analyser forms read hops: those calls go through fx_reblock_kernel).
@@ -509,6 +599,8 @@ fx_status run(fx_context* c, const void* in, int T, int sample_format, int in_ki
             return fx_fail(FX_ERR_INVALID_ARGUMENT, "device input must be %d-byte aligned", blocks ? 4 : 16);
     }
     if (blocks && (T < 1 || T > 4096 || !hop_mode || in_kind != FX_MEM_DEVICE)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "a block feed is 1 .. 4096 hops per channel from device memory");
+    Plan plan;
+    if ((st = plan_call(c, d_in, T, sample_format, hop_mode, d_or, d_os, blocks, nullptr, c->d_part, c->d_raw, ROUTE_AUTO, &plan)) != FX_OK) return st;
     // armed taps (fx_request_taps): their launch reads this call's first frame before any launch of the call changes the context's state
     if (taps && c->taps_armed && c->taps_launch) {
         const fx_tap_source src = {d_in, sample_format, hop_mode, blocks ? blocks->in_row_bytes : (long long) (T * per_frame * esz),
@@ -516,26 +608,10 @@ fx_status run(fx_context* c, const void* in, int T, int sample_format, int in_ki
         if ((st = c->taps_launch(c, src)) != FX_OK) return st;
     }
 
-    // A call of TWO hops per channel (a 1024-sample device buffer against a 1024-point window, 960-sample blocks every other call ...) runs
-    // as two one-frame launches over the same buffers -- the second reads hop 1 and writes frame 1 (FrameParams::in_hop_stride / in_hop0,
-    // EpilogueParams::out_stride / out_t0) -- and, like a one-frame call, records no timing events unless asked to.  Measured
-    // (tools/device_blocks.py, us per call of two hops: batch form with its events / batch form without / two one-frame launches):
-    // 8192 channels x 1024 points 144 / 136.6 / 133.8; 1024 x 1024 52 / 42.6 / 39.7; 4096 x 2048 165 / 154.9 / 157.1; 512 x 2048 - / 50.4 / 46.3;
-    // 1024 x 4096 137 / 127.1 / 123.4; 256 x 4096 - / 66.7 / 57.1.  Most of what a two-hop call cost over two one-hop calls was the three event
-    // records (barrier packets); the launches themselves are worth 0 - 14 %.  What this form really buys is the block feed: a block that
-    // completes two hops is read by the kernels directly (1000-sample blocks at 8192 channels: 177 -> 132 us per call).
-    const bool both = !(c->flags & (FX_SPECTRAL_ONLY | FX_HARMONIC_ONLY));
-    const bool in_two = hop_mode && T == 2 && both && c->N >= 1024 && !uses_pairs(c, c->tuning.waves_per_frame) && !(c->test_hooks & FX_HOOK_NO_TWO_LAUNCHES);
-    const bool one_frame_launches = in_two || (blocks && T <= 2);        // (a block feed of more hops is ONE launch of the batch kernel's block-fed form)
-    const int parts = one_frame_launches ? T : 1, part_T = one_frame_launches ? 1 : T;
-
-    // The three events fx_last_kernel_ms() reads.  Each is a barrier packet between launches, which a call of milliseconds does not
-    // notice and a one-frame call does (back to back 27 us per call with them, 14.6 without): those record none unless asked to.
-    // (a call made of one-frame launches is a live call: no events by default, like a one-frame call)
-    const bool timed = c->profiling || c->tuning.call_timing == 1 || (c->tuning.call_timing < 0 && part_T > 1);
-#define FX_EV(e) do { if (timed) HIP_TRY(hipEventRecord(e, c->stream)); } while (0)
+    // timed: e0 before the first launch, e1 after the last launch that analyses frames, e2 after the last launch (frame-kernel time is
+    // only split out of calls of one part)
     hipEvent_t e0 = c->ev[0], e1 = c->ev[1], e2 = c->ev[2];
-    bool last_valid = timed;
+    bool last_valid = plan.timed;
     if (c->profiling && c->prof_used + 3 <= 3 * 4096) {
         while (c->prof_events.size() < c->prof_used + 3) {
             hipEvent_t e;
@@ -546,69 +622,17 @@ fx_status run(fx_context* c, const void* in, int T, int sample_format, int in_ki
         c->prof_used += 3;
         last_valid = false;
     }
-    for (int part = 0; part < parts; part++) {
-        const bool first = part == 0, last = part == parts - 1;       // (the events bracket the whole call: frame-kernel time is only split out of one-part calls)
-        Step step;
-        if ((st = prepare_step(c, d_in, part_T, sample_format, hop_mode, d_or, d_os, c->d_part, c->d_raw, nullptr, &step)) != FX_OK) return st;
-        if (parts > 1) {
-            step.fp.in_hop_stride = T; step.fp.in_hop0 = part;
-            step.ep.out_stride = T;    step.ep.out_t0 = part;
-        }
-        if (blocks) {
-            step.fp.block_mode = 1;
-            step.fp.blk_hop0 = one_frame_launches ? part : 0;
-            step.fp.blk_keep_rest = last ? 1 : 0;
-            step.fp.blk_carry_in = blocks->carry_in;
-            step.fp.blk_carry_out = blocks->carry_out;
-            step.fp.blk_carry_bytes = blocks->carry_bytes;
-            step.fp.blk_carry_row_bytes = blocks->carry_row_bytes;
-            step.fp.blk_in_row_bytes = blocks->in_row_bytes;
-            if (step.pair || step.analysers != 3) return fx_fail(FX_ERR_INVALID_ARGUMENT, "this context's kernels do not read blocks");
-        }
-        // ONE frame per channel -- the reference's own cadence, an analysis per hop as it arrives (AudioDataCollector.h:66-94,
-        // RealTimeAnalyser.h:201-234) -- is one launch of fx_hop_kernel: three wavefronts per channel (pitch / spectral /
-        // harmonic) and the hop's tail, instead of one wavefront per channel and a second launch.
-        // (measured, tools/live_cadence.py, profiles/r04_live_cadence.txt: once the call holds more than the chip takes in one round of
-        // workgroups -- 1024 channels of 1024 points, 512 of 2048, and 1024 of 4096 since a 4096-point workgroup is 80 KB and a CU holds two --
-        // the batch kernels take over: one wavefront per channel with the flux state left in global memory (prepare_step), then the fused
-        // tail on a quarter wavefront per channel: 63 against 120 us at 8192 channels x 1024-pt, 76 against 186 us at 2048 channels x 4096-pt;
-        // below it the hop kernel wins, 19.9 against 22.9 us at 1024 x 1024-pt, 58.7 against 61.8 us at 1024 x 4096-pt.  The pair family's
-        // hop kernel -- six wavefronts and 100 KB per channel -- keeps 2^20 at every size)
-        const bool one_hop = part_T == 1 && step.analysers == 3 && fxk::hop_kernel_available(c->N) &&
-                             (c->tuning.one_hop_kernel == 1 || (c->tuning.one_hop_kernel < 0 && (long long) c->C * c->N <= ((c->N == 4096 && !step.hop_pairs) ? (1ll << 22) : (1ll << 20))));
-        if (one_hop) {
-            const fxk::HopSignal none = {nullptr, nullptr, 0u, 0u, nullptr};
-            if (first) FX_EV(e0);
-            note_step(c, step.hop_pairs ? FX_LAUNCH_HOP_PAIR : FX_LAUNCH_HOP, step);
-            HIP_TRY(fxk::launch_hop_kernel(c->N, step.fp, step.ep, none, c->stream, step.hop_pairs));
-            if (last) { FX_EV(e1); FX_EV(e2); }
-        } else {
-            if (first) FX_EV(e0);
-            // One frame per channel through the batch kernels: frames and tails in ONE launch (fx_frame_tail_kernel) while the chip holds all
-            // of the call's workgroups at once -- two per CU at these sizes, one of eight channels at 4096 points.  Beyond that a workgroup whose
-            // first wavefronts are finishing its hops keeps the LDS the next workgroup is waiting for, and the tail is better off as a launch
-            // of its own.  Measured (us per call, one launch / two; profiles/r04_live_cadence.txt): 1024 points 2048 channels 26.8 / 28.6, 4096
-            // channels 41.0 / 41.7, 8192 channels 70.2 / 68.2; 2048 points 2048 channels 44.9 / 45.7, 4096 channels 77.5 / 73.8; windows of 512
-            // points and fewer lose either way (4096 channels 34.7 / 33.2): their frames are no longer than the tail.
-            const long long groups = ((long long) c->C + step.fp.ch_per_wg - 1) / step.fp.ch_per_wg;
-            const long long one_round = (long long) c->compute_units * ((c->N == 4096 && step.fp.ch_per_wg > 4) ? 1 : 2);
-            const bool one_launch = step.fp.direct_state && fxk::frame_tail_kernel_available(c->N) &&
-                                    ((c->test_hooks & FX_HOOK_TAIL_ALWAYS_FUSED) || (!(c->test_hooks & FX_HOOK_TAIL_NEVER_FUSED) && groups <= one_round));
-            if (one_launch) {
-                note_step(c, FX_LAUNCH_FRAME_TAIL, step);
-                HIP_TRY(fxk::launch_frame_tail_kernel(c->N, step.fp, step.ep, c->stream));
-                if (last) FX_EV(e1);
-            } else {
-                HIP_TRY(launch_frames(c, step));
-                if (last) FX_EV(e1);
-                note_step(c, FX_LAUNCH_EPILOGUE, step);
-                HIP_TRY(fxk::launch_epilogue_kernels(step.ep, c->stream));
-            }
-            if (last) FX_EV(e2);
-        }
-        advance(c, part_T);
+    auto mark = [&](hipEvent_t e) { return plan.timed ? hipEventRecord(e, c->stream) : hipSuccess; };
+    int last_frames = plan.n - 1;
+    while (plan.launch[last_frames].kind == FX_LAUNCH_EPILOGUE) last_frames--;
+    HIP_TRY(mark(e0));
+    for (int i = 0; i < plan.n; i++) {
+        HIP_TRY(enqueue(c, plan.launch[i]));
+        if (i == last_frames) HIP_TRY(mark(e1));
+        // a part's launches are enqueued: the context holds the state they leave, whatever happens to the rest of the call
+        if (i + 1 == plan.n || plan.launch[i + 1].kind != FX_LAUNCH_EPILOGUE) advance(c, T / plan.parts);
     }
-#undef FX_EV
+    HIP_TRY(mark(e2));
     c->ev_valid = last_valid;
 
     if (out_kind == FX_MEM_HOST) {
@@ -653,6 +677,7 @@ fx_status fx_create(fx_context** out, int device_id, int num_channels, int windo
 
     fx_context* c = new (std::nothrow) fx_context();
     if (!c) return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    std::unique_ptr<fx_context, fx_status (*)(fx_context*)> half_built(c, fx_destroy);    // destroyed on every return but the last
     if (prop.multiProcessorCount > 0) c->compute_units = prop.multiProcessorCount;
     c->device = device_id;
     c->C = num_channels;
@@ -662,27 +687,25 @@ fx_status fx_create(fx_context** out, int device_id, int num_channels, int windo
     fx_tuning_from_env(&c->tuning);          // once; nothing on the analysis path reads the environment
 
     fx_status st = FX_OK;
-    auto cleanup = [&](fx_status s) { fx_destroy(c); return s; };
     {
         hipError_t e = fxk::prepare_kernels(window_size);
         if (e == hipSuccess) e = fxk::prepare_hop_kernel(window_size);
         if (e == hipSuccess) e = fxk::prepare_pair_kernel(window_size);
-        if (e != hipSuccess) return cleanup(fx_fail(FX_ERR_HIP, "kernel preparation failed: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fx_fail(FX_ERR_HIP, "kernel preparation failed: %s", hipGetErrorString(e));
     }
-#define TRY_OR_CLEAN(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return cleanup(fx_fail(e_ == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); } while (0)
-    TRY_OR_CLEAN(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    for (int i = 0; i < 3; i++) TRY_OR_CLEAN(hipEventCreate(&c->ev[i]));
+    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreate(&c->ev[i]));
     const size_t half = (size_t) num_channels * (window_size / 2);
-    TRY_OR_CLEAN(hipMalloc((void**) &c->d_tw, sizeof(float) * 4 * window_size));      // the pass-ordered table, then the frame kernel's LDS image of it
-    TRY_OR_CLEAN(hipMalloc((void**) &c->d_prev, sizeof(float) * half));
-    for (int i = 0; i < 2; i++) TRY_OR_CLEAN(hipMalloc((void**) &c->d_tail[i], sizeof(float) * half));
-    TRY_OR_CLEAN(hipMalloc((void**) &c->d_hist, sizeof(float) * (size_t) num_channels * fxk::HLEN * FX_NUM_FEATURES));
-    TRY_OR_CLEAN(hipMalloc((void**) &c->d_latest, sizeof(float) * (size_t) num_channels * FX_NUM_FEATURES));
-    TRY_OR_CLEAN(hipMalloc((void**) &c->d_queue, sizeof(unsigned) * (1 + (size_t) num_channels)));
-    for (int i = 0; i < 2; i++) TRY_OR_CLEAN(hipMalloc((void**) &c->d_carry[i], half * 4));
-    TRY_OR_CLEAN(hipHostMalloc((void**) &c->h_err, 64, hipHostMallocCoherent));
+    HIP_TRY(hipMalloc((void**) &c->d_tw, sizeof(float) * 4 * window_size));      // the pass-ordered table, then the frame kernel's LDS image of it
+    HIP_TRY(hipMalloc((void**) &c->d_prev, sizeof(float) * half));
+    for (int i = 0; i < 2; i++) HIP_TRY(hipMalloc((void**) &c->d_tail[i], sizeof(float) * half));
+    HIP_TRY(hipMalloc((void**) &c->d_hist, sizeof(float) * (size_t) num_channels * fxk::HLEN * FX_NUM_FEATURES));
+    HIP_TRY(hipMalloc((void**) &c->d_latest, sizeof(float) * (size_t) num_channels * FX_NUM_FEATURES));
+    HIP_TRY(hipMalloc((void**) &c->d_queue, sizeof(unsigned) * (1 + (size_t) num_channels)));
+    for (int i = 0; i < 2; i++) HIP_TRY(hipMalloc((void**) &c->d_carry[i], half * 4));
+    HIP_TRY(hipHostMalloc((void**) &c->h_err, 64, hipHostMallocCoherent));
     *c->h_err = 0;
-    { void* q = nullptr; TRY_OR_CLEAN(hipHostGetDevicePointer(&q, c->h_err, 0)); c->d_err = static_cast<unsigned*>(q); }
+    { void* q = nullptr; HIP_TRY(hipHostGetDevicePointer(&q, c->h_err, 0)); c->d_err = static_cast<unsigned*>(q); }
 
     // Twiddle table exactly as the reference's FFT builds it (JUCE 4.2 FFT::FFTConfig, SURVEY.md
     // App. A.1): phase in double, entries rounded to float.  The inverse table is its conjugate.
@@ -692,13 +715,13 @@ fx_status fx_create(fx_context** out, int device_id, int num_channels, int windo
         fxk::build_pass_twiddles(window_size, tw.data(), ordered.data());    // same values, pass access order
         fxk::fill_first_pass_twiddles(window_size, ordered.data(), c->first_tw);
         if (!fxk::first_pass_twiddles_hermitian(window_size, c->first_tw))
-            return cleanup(fx_fail(FX_ERR_UNSUPPORTED, "this host's cos/sin produce a twiddle table without the mirror symmetry the kernels rely on"));
+            return fx_fail(FX_ERR_UNSUPPORTED, "this host's cos/sin produce a twiddle table without the mirror symmetry the kernels rely on");
         c->tw_quarter_turn = fxk::twiddles_have_quarter_turn(window_size, tw.data());
         c->tw_at_quarter[0] = tw[2 * (size_t) (window_size / 4)]; c->tw_at_quarter[1] = tw[2 * (size_t) (window_size / 4) + 1];     // (false only costs the 4096-point kernel two global reads per item)
-        TRY_OR_CLEAN(hipMemcpy(c->d_tw, ordered.data(), ordered.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_tw, ordered.data(), ordered.size() * sizeof(float), hipMemcpyHostToDevice));
         std::vector<float> image(ordered.size(), 0.0f);
         fxk::build_twiddle_image(window_size, ordered.data(), image.data());
-        TRY_OR_CLEAN(hipMemcpy(c->d_tw + ordered.size(), image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_tw + ordered.size(), image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     // ref SpectralCharacteristics.h:180-189: binVar does not depend on the signal
     {
@@ -716,10 +739,9 @@ fx_status fx_create(fx_context** out, int device_id, int num_channels, int windo
         c->lpf_a = float_pi / 2.0f;
         c->lpf_b = std::exp(-float_pi / 2.0f);
     }
-    if ((st = zero_state(c)) != FX_OK) return cleanup(st);
-    TRY_OR_CLEAN(hipStreamSynchronize(c->stream));
-#undef TRY_OR_CLEAN
-    *out = c;
+    if ((st = zero_state(c)) != FX_OK) return st;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out = half_built.release();
     return FX_OK;
 }
 
@@ -837,15 +859,10 @@ static fx_status push_samples(fx_context* c, const void* samples, int num_sample
     HIP_TRY(hipSetDevice(c->device));
     { const fx_status es = fx_check_device_error(c); if (es != FX_OK) return es; }
 
-    // whole hops from an aligned device buffer and nothing pending: the block IS the hop buffer
-    if (mem_kind == FX_MEM_DEVICE && c->carry_count == 0 && rest == 0 && reinterpret_cast<uintptr_t>(samples) % 16 == 0) {
-        const fx_status st = run(c, samples, hops, sample_format, FX_MEM_DEVICE, FX_MEM_DEVICE, 1, out_raw, out_smoothed, nullptr, taps);
-        if (st == FX_OK && frames_out) *frames_out = hops;
-        return st;
-    }
-    // ... and so is a host block of whole hops (512-sample callbacks against a 1024-point window): one copy in, no re-blocking
-    if (mem_kind == FX_MEM_HOST && c->carry_count == 0 && rest == 0) {
-        const fx_status st = run(c, samples, hops, sample_format, FX_MEM_HOST, FX_MEM_HOST, 1, out_raw, out_smoothed, nullptr, taps);
+    // whole hops and nothing pending: the block IS the hop buffer -- from an aligned device buffer, or a host block (512-sample callbacks
+    // against a 1024-point window: one copy in, no re-blocking)
+    if (c->carry_count == 0 && rest == 0 && (mem_kind == FX_MEM_HOST || reinterpret_cast<uintptr_t>(samples) % 16 == 0)) {
+        const fx_status st = run(c, samples, hops, sample_format, mem_kind, mem_kind, 1, out_raw, out_smoothed, nullptr, taps);
         if (st == FX_OK && frames_out) *frames_out = hops;
         return st;
     }
@@ -1179,8 +1196,7 @@ struct fx_stream {
         fxk::DynParams* h_dyn = nullptr;  // pinned: what changes from call to call
         fxk::DynParams* d_dyn = nullptr;
         hipGraphExec_t  exec[2] = {nullptr, nullptr};     // per parity of the context's ping-pong buffers
-        fx_launch_record launches[2][FX_LAUNCH_RECORD_CAP];   // the launch record each of them made at capture (fx_last_launches_internal)
-        int       num_launches[2] = {0, 0};
+        Plan      captured[2];            // what each of them launches (noted in the launch record at every replay)
     };
     std::vector<Slot> ring;
     int head = 0;        // next slot to acquire
@@ -1190,9 +1206,20 @@ struct fx_stream {
     int since_release = 0;   // batches of the three-queue path collected since the streams were last synchronised (fx_stream_collect_samples)
 };
 
-static fx_status submit_large(fx_stream* s, fx_stream::Slot& sl, size_t in_bytes, int num_samples);
-#define HIP_TRY_OR(expr, after) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { after; \
-        return fx_fail(e_ == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
+// A submit holds the acquired slot: every return hands it back (the caller may fill and submit it again: the ring never wedges on "a
+// slot is already acquired").  A failed one first waits for the streams it has given work that reads the slot.
+struct SlotGuard {
+    fx_stream* s;
+    hipStream_t readers[2] = {nullptr, nullptr};
+    bool ok = false;
+    ~SlotGuard()
+    {
+        if (!ok) for (hipStream_t q : readers) if (q) (void) hipStreamSynchronize(q);
+        s->acquired = false;
+    }
+};
+
+static fx_status submit_large(fx_stream* s, SlotGuard& g, fx_stream::Slot& sl, size_t in_bytes, int num_samples);
 
 extern "C" {
 
@@ -1237,14 +1264,14 @@ fx_status fx_stream_create(fx_context* c, int hops_per_batch, int slots, int sam
     HIP_TRY(hipSetDevice(c->device));
     fx_stream* s = new (std::nothrow) fx_stream();
     if (!s) return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    std::unique_ptr<fx_stream, fx_status (*)(fx_stream*)> half_built(s, fx_stream_destroy);    // destroyed on every return but the last
     s->ctx = c; s->hops = hops_per_batch; s->slots = slots; s->fmt = sample_format;
     s->fill.streaming = c->tuning.stream_fill_streaming != 0;
     s->in_bytes = (size_t) c->C * hops_per_batch * (c->N / 2) * sample_size(sample_format);
     s->out_bytes = (size_t) c->C * hops_per_batch * FX_NUM_FEATURES * sizeof(float);
     s->ring.resize((size_t) slots);
-#define S_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { fx_status st_ = fx_fail(e_ == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); fx_stream_destroy(s); return st_; } } while (0)
-    S_TRY(hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
-    S_TRY(hipStreamCreateWithFlags(&s->back, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&s->back, hipStreamNonBlocking));
     // which of the equivalent paths runs: by batch size, unless the context's tuning forces one (experiments, tests)
     s->use_graph = c->tuning.stream_graph >= 0 ? c->tuning.stream_graph != 0 : (size_t) c->C * hops_per_batch <= 4096;
     // (up to 1 MiB of hops per call: the kernel reads each hop out of the pinned slot exactly once, 16 bytes per lane)
@@ -1253,37 +1280,36 @@ fx_status fx_stream_create(fx_context* c, int hops_per_batch, int slots, int sam
     if (s->use_hop_kernel) s->use_graph = false;
     s->zero_copy = c->tuning.stream_zero_copy >= 0 ? c->tuning.stream_zero_copy != 0 : s->in_bytes <= 64 * 1024;
     if (s->use_hop_kernel) {
-        S_TRY(hipMalloc((void**) &s->d_arrivals, sizeof(unsigned)));
-        S_TRY(hipMemsetAsync(s->d_arrivals, 0, sizeof(unsigned), c->stream));
-        S_TRY(hipMalloc(&s->d_stage, s->in_bytes));
+        HIP_TRY(hipMalloc((void**) &s->d_arrivals, sizeof(unsigned)));
+        HIP_TRY(hipMemsetAsync(s->d_arrivals, 0, sizeof(unsigned), c->stream));
+        HIP_TRY(hipMalloc(&s->d_stage, s->in_bytes));
     }
     // the hop kernel's results and flag are read by the host while the kernel may still be running: coherent (fine-grained) memory
     const unsigned host_flags = s->use_hop_kernel ? hipHostMallocCoherent : hipHostMallocDefault;
     if (s->use_graph) {
-        S_TRY(hipMalloc((void**) &s->g_part, (size_t) c->C * hops_per_batch * sizeof(fxk::FramePart)));
-        S_TRY(hipMalloc((void**) &s->g_raw, s->out_bytes));
+        HIP_TRY(hipMalloc((void**) &s->g_part, (size_t) c->C * hops_per_batch * sizeof(fxk::FramePart)));
+        HIP_TRY(hipMalloc((void**) &s->g_raw, s->out_bytes));
     }
     for (auto& sl : s->ring) {
         if (s->use_graph) {
-            S_TRY(hipHostMalloc((void**) &sl.h_dyn, sizeof(fxk::DynParams), hipHostMallocDefault));
-            S_TRY(hipMalloc((void**) &sl.d_dyn, sizeof(fxk::DynParams)));
+            HIP_TRY(hipHostMalloc((void**) &sl.h_dyn, sizeof(fxk::DynParams), hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void**) &sl.d_dyn, sizeof(fxk::DynParams)));
         }
         if (s->use_hop_kernel) {
-            S_TRY(hipHostMalloc((void**) &sl.h_flag, 64, hipHostMallocCoherent));
+            HIP_TRY(hipHostMalloc((void**) &sl.h_flag, 64, hipHostMallocCoherent));
             *sl.h_flag = 0;
         }
-        S_TRY(hipHostMalloc(&sl.h_in, s->in_bytes, host_flags));
-        S_TRY(hipHostMalloc((void**) &sl.h_raw, s->out_bytes, host_flags));
-        S_TRY(hipHostMalloc((void**) &sl.h_sm, s->out_bytes, host_flags));
-        S_TRY(hipMalloc(&sl.d_in, s->in_bytes));
-        S_TRY(hipMalloc((void**) &sl.d_raw, s->out_bytes));
-        S_TRY(hipMalloc((void**) &sl.d_sm, s->out_bytes));
-        S_TRY(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
-        S_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-        S_TRY(hipEventCreateWithFlags(&sl.out, hipEventDisableTiming));
+        HIP_TRY(hipHostMalloc(&sl.h_in, s->in_bytes, host_flags));
+        HIP_TRY(hipHostMalloc((void**) &sl.h_raw, s->out_bytes, host_flags));
+        HIP_TRY(hipHostMalloc((void**) &sl.h_sm, s->out_bytes, host_flags));
+        HIP_TRY(hipMalloc(&sl.d_in, s->in_bytes));
+        HIP_TRY(hipMalloc((void**) &sl.d_raw, s->out_bytes));
+        HIP_TRY(hipMalloc((void**) &sl.d_sm, s->out_bytes));
+        HIP_TRY(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&sl.out, hipEventDisableTiming));
     }
-#undef S_TRY
-    *out = s;
+    *out = half_built.release();
     return FX_OK;
 }
 
@@ -1305,43 +1331,35 @@ fx_status fx_stream_submit(fx_stream* s)
 {
     if (!s) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null stream");
     if (!s->acquired) return fx_fail(FX_ERR_INVALID_ARGUMENT, "no slot acquired");
+    SlotGuard g{s};
     fx_context* c = s->ctx;
     begin_launches(c);
-    HIP_TRY_OR(hipSetDevice(c->device), s->acquired = false);
+    HIP_TRY(hipSetDevice(c->device));
     fx_stream::Slot& sl = s->ring[(size_t) s->head];
-    { const fx_status es = fx_check_device_error(c); if (es != FX_OK) { s->acquired = false; return es; } }
-    if (c->carry_count > 0) {
-        s->acquired = false;
+    fx_status st;
+    if ((st = fx_check_device_error(c)) != FX_OK) return st;
+    if (c->carry_count > 0)
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d samples per channel are pending from fx_stream_submit_samples / fx_push_samples; whole hops would overtake them", c->carry_count);
-    }
-    // Any failure below hands the slot back (the caller may fill and submit it again): the ring never wedges on
-    // "a slot is already acquired".
-#define SUB_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { s->acquired = false; \
-        return fx_fail(e_ == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
     if (s->use_hop_kernel) {
         if (!sl.dev_flag) {
             void* q = nullptr;
-            SUB_TRY(hipHostGetDevicePointer(&q, sl.h_in, 0));   sl.dev_in = q;
-            SUB_TRY(hipHostGetDevicePointer(&q, sl.h_raw, 0));  sl.dev_raw = static_cast<float*>(q);
-            SUB_TRY(hipHostGetDevicePointer(&q, sl.h_sm, 0));   sl.dev_sm = static_cast<float*>(q);
-            SUB_TRY(hipHostGetDevicePointer(&q, sl.h_flag, 0)); sl.dev_flag = static_cast<unsigned*>(q);
+            HIP_TRY(hipHostGetDevicePointer(&q, sl.h_in, 0));   sl.dev_in = q;
+            HIP_TRY(hipHostGetDevicePointer(&q, sl.h_raw, 0));  sl.dev_raw = static_cast<float*>(q);
+            HIP_TRY(hipHostGetDevicePointer(&q, sl.h_sm, 0));   sl.dev_sm = static_cast<float*>(q);
+            HIP_TRY(hipHostGetDevicePointer(&q, sl.h_flag, 0)); sl.dev_flag = static_cast<unsigned*>(q);
         }
-        unsigned* flag_dev = sl.dev_flag;
-        Step step;
-        fx_status st0 = prepare_step(c, sl.dev_in, 1, s->fmt, 1, sl.dev_raw, sl.dev_sm, nullptr, nullptr, nullptr, &step);
-        if (st0 != FX_OK) { s->acquired = false; return st0; }
+        Plan plan;
+        if ((st = plan_call(c, sl.dev_in, 1, s->fmt, 1, sl.dev_raw, sl.dev_sm, nullptr, nullptr, nullptr, nullptr, ROUTE_RING_HOP, &plan)) != FX_OK) return st;
         if (++s->next_seq == 0) s->next_seq = 1;            // 0 = "nothing completed yet"
         sl.seq = s->next_seq;
-        const fxk::HopSignal sig = {s->d_arrivals, flag_dev, sl.seq, 0u, s->d_stage};
-        note_step(c, step.hop_pairs ? FX_LAUNCH_HOP_PAIR : FX_LAUNCH_HOP, step);
-        const hipError_t e = fxk::launch_hop_kernel(c->N, step.fp, step.ep, sig, c->stream, step.hop_pairs);
-        if (e != hipSuccess) { s->acquired = false; return fx_fail(FX_ERR_HIP, "launching the hop kernel failed: %s", hipGetErrorString(e)); }
+        const fxk::HopSignal sig = {s->d_arrivals, sl.dev_flag, sl.seq, 0u, s->d_stage};
+        const hipError_t e = enqueue(c, plan.launch[0], sig);
+        if (e != hipSuccess) return fx_fail(FX_ERR_HIP, "launching the hop kernel failed: %s", hipGetErrorString(e));
         c->ev_valid = false;
         advance(c, 1);
         sl.frames = 1; sl.by_event = false;
         s->head = (s->head + 1) % s->slots;
         s->in_flight++;
-        s->acquired = false;
         return FX_OK;
     }
     if (s->use_graph) {
@@ -1358,23 +1376,21 @@ fx_status fx_stream_submit(fx_stream* s)
             const fxk::DynParams* dyn_dev = sl.d_dyn;
             if (zero_copy) {
                 void* q = nullptr;
-                SUB_TRY(hipHostGetDevicePointer(&q, sl.h_in, 0));  in_dev = q;
-                SUB_TRY(hipHostGetDevicePointer(&q, sl.h_raw, 0)); raw_dev = static_cast<float*>(q);
-                SUB_TRY(hipHostGetDevicePointer(&q, sl.h_sm, 0));  sm_dev = static_cast<float*>(q);
-                SUB_TRY(hipHostGetDevicePointer(&q, sl.h_dyn, 0)); dyn_dev = static_cast<const fxk::DynParams*>(q);
+                HIP_TRY(hipHostGetDevicePointer(&q, sl.h_in, 0));  in_dev = q;
+                HIP_TRY(hipHostGetDevicePointer(&q, sl.h_raw, 0)); raw_dev = static_cast<float*>(q);
+                HIP_TRY(hipHostGetDevicePointer(&q, sl.h_sm, 0));  sm_dev = static_cast<float*>(q);
+                HIP_TRY(hipHostGetDevicePointer(&q, sl.h_dyn, 0)); dyn_dev = static_cast<const fxk::DynParams*>(q);
             }
-            Step step;
-            fx_status st0 = prepare_step(c, in_dev, s->hops, s->fmt, 1, raw_dev, sm_dev, s->g_part, s->g_raw, dyn_dev, &step);
-            if (st0 != FX_OK) { s->acquired = false; return st0; }
+            Plan plan;
+            if ((st = plan_call(c, in_dev, s->hops, s->fmt, 1, raw_dev, sm_dev, nullptr, dyn_dev, s->g_part, s->g_raw, ROUTE_RING_CAPTURED, &plan)) != FX_OK) return st;
             hipGraph_t graph = nullptr;
-            SUB_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+            HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
             hipError_t e = hipSuccess;
             if (!zero_copy) {
                 e = hipMemcpyAsync(sl.d_in, sl.h_in, s->in_bytes, hipMemcpyHostToDevice, c->stream);
                 if (e == hipSuccess) e = hipMemcpyAsync(sl.d_dyn, sl.h_dyn, sizeof(fxk::DynParams), hipMemcpyHostToDevice, c->stream);
             }
-            if (e == hipSuccess) e = launch_frames(c, step);
-            if (e == hipSuccess) { note_step(c, FX_LAUNCH_EPILOGUE, step); e = fxk::launch_epilogue_kernels(step.ep, c->stream); }
+            for (int i = 0; i < plan.n && e == hipSuccess; i++) e = enqueue(c, plan.launch[i]);
             if (!zero_copy) {
                 if (e == hipSuccess) e = hipMemcpyAsync(sl.h_raw, sl.d_raw, s->out_bytes, hipMemcpyDeviceToHost, c->stream);
                 if (e == hipSuccess) e = hipMemcpyAsync(sl.h_sm, sl.d_sm, s->out_bytes, hipMemcpyDeviceToHost, c->stream);
@@ -1385,16 +1401,13 @@ fx_status fx_stream_submit(fx_stream* s)
             if (graph) (void) hipGraphDestroy(graph);
             if (e != hipSuccess) {
                 sl.exec[par] = nullptr;
-                s->acquired = false;
                 return fx_fail(FX_ERR_HIP, "capturing the streaming step failed: %s", hipGetErrorString(e));
             }
-            sl.num_launches[par] = c->num_launches;          // what the graph launches each time it is replayed
-            memcpy(sl.launches[par], c->launches, sizeof c->launches);
+            sl.captured[par] = plan;        // (kept with the graph only: a capture that failed is planned afresh when it is tried again)
         } else {
-            c->num_launches = sl.num_launches[par];
-            memcpy(c->launches, sl.launches[par], sizeof c->launches);
+            for (int i = 0; i < sl.captured[par].n; i++) note_planned(c, sl.captured[par].launch[i]);     // what the graph launches each time it is replayed
         }
-        SUB_TRY(hipGraphLaunch(sl.exec[par], c->stream));
+        HIP_TRY(hipGraphLaunch(sl.exec[par], c->stream));
         // the step is enqueued: the context has moved on whatever happens to the bookkeeping event below
         c->ev_valid = false;
         advance(c, s->hops);
@@ -1402,26 +1415,24 @@ fx_status fx_stream_submit(fx_stream* s)
         sl.frames = s->hops; sl.by_event = true;
         s->head = (s->head + 1) % s->slots;
         s->in_flight++;
-        s->acquired = false;
         if (er != hipSuccess) return fx_fail(FX_ERR_HIP, "hipEventRecord failed: %s", hipGetErrorString(er));
         return FX_OK;
     }
-    return submit_large(s, sl, s->in_bytes, -1);
+    return submit_large(s, g, sl, s->in_bytes, -1);
 }
 
 fx_status fx_stream_submit_samples(fx_stream* s, int num_samples)
 {
     if (!s) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null stream");
     if (!s->acquired) return fx_fail(FX_ERR_INVALID_ARGUMENT, "no slot acquired");
+    SlotGuard g{s};
     fx_context* c = s->ctx;
     begin_launches(c);
-    if (num_samples < 0 || (long long) num_samples > (long long) s->hops * (c->N / 2)) {
-        s->acquired = false;
+    if (num_samples < 0 || (long long) num_samples > (long long) s->hops * (c->N / 2))
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "a slot holds 0 .. %lld samples per channel, got %d", (long long) s->hops * (c->N / 2), num_samples);
-    }
-    HIP_TRY_OR(hipSetDevice(c->device), s->acquired = false);
-    { const fx_status es = fx_check_device_error(c); if (es != FX_OK) { s->acquired = false; return es; } }
-    return submit_large(s, s->ring[(size_t) s->head], (size_t) c->C * (size_t) num_samples * sample_size(s->fmt), num_samples);
+    HIP_TRY(hipSetDevice(c->device));
+    { const fx_status es = fx_check_device_error(c); if (es != FX_OK) return es; }
+    return submit_large(s, g, s->ring[(size_t) s->head], (size_t) c->C * (size_t) num_samples * sample_size(s->fmt), num_samples);
 }
 
 } // extern "C"
@@ -1429,43 +1440,36 @@ fx_status fx_stream_submit_samples(fx_stream* s, int num_samples)
 // The large-batch form of a submit: samples in on `copy`, analysis on the context's stream behind an event, vectors back on `back`.
 // num_samples < 0: the slot holds hops_per_batch whole hops per channel; else a block of num_samples samples per channel
 // ([C][num_samples], rows back to back), which fx_push_samples cuts into hops with the context's pending samples.
-// Any failure hands the slot back (acquired = false) so the ring never wedges on "a slot is already acquired": before the
-// analysis is enqueued nothing has happened; after it the context has moved on and the batch's results are lost with the error.
-static fx_status submit_large(fx_stream* s, fx_stream::Slot& sl, size_t in_bytes, int num_samples)
+// A failure before the analysis is enqueued loses nothing; after it the context has moved on and the batch's results are lost with the
+// error.  Either way the streams named in g.readers are waited for before the slot is handed back.
+static fx_status submit_large(fx_stream* s, SlotGuard& g, fx_stream::Slot& sl, size_t in_bytes, int num_samples)
 {
     fx_context* c = s->ctx;
-#define LG_TRY(expr, after) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { after; s->acquired = false; \
-        return fx_fail(e_ == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
-    if (in_bytes) LG_TRY(hipMemcpyAsync(sl.d_in, sl.h_in, in_bytes, hipMemcpyHostToDevice, s->copy), (void) 0);
-    LG_TRY(hipEventRecord(sl.copied, s->copy), (void) hipStreamSynchronize(s->copy));
-    LG_TRY(hipStreamWaitEvent(c->stream, sl.copied, 0), (void) hipStreamSynchronize(s->copy));
+    if (in_bytes) HIP_TRY(hipMemcpyAsync(sl.d_in, sl.h_in, in_bytes, hipMemcpyHostToDevice, s->copy));
+    g.readers[0] = s->copy;
+    HIP_TRY(hipEventRecord(sl.copied, s->copy));
+    HIP_TRY(hipStreamWaitEvent(c->stream, sl.copied, 0));
+    // fx_push_samples may launch its re-blocking kernel on the context's stream and then fail: that kernel reads the slot too.  The ring
+    // stays usable; the STREAM of a samples submit does not: the pending samples have moved on without the hops this block completed
+    // (fx_push_samples' contract) -- fx_reset_state, not a re-submit of the same block.
+    if (num_samples >= 0) g.readers[1] = c->stream;
     int frames = s->hops;
     const fx_status st = num_samples < 0 ? run(c, sl.d_in, s->hops, s->fmt, FX_MEM_DEVICE, FX_MEM_DEVICE, 1, sl.d_raw, sl.d_sm)
                                          : push_samples(c, sl.d_in, num_samples, s->fmt, FX_MEM_DEVICE, sl.d_raw, sl.d_sm, &frames, false);
-    if (st != FX_OK) {
-        // The copy is already enqueued, and fx_push_samples may have launched its re-blocking kernel on the context's stream before it failed: both
-        // read the slot, so let both finish before the slot is handed back.  The ring stays usable; the STREAM of a samples submit does not:
-        // the pending samples have moved on without the hops this block completed (fx_push_samples' contract) -- fx_reset_state, not a
-        // re-submit of the same block.
-        (void) hipStreamSynchronize(s->copy);
-        if (num_samples >= 0) (void) hipStreamSynchronize(c->stream);
-        s->acquired = false;
-        return st;
-    }
+    if (st != FX_OK) return st;
     const size_t out_bytes = (size_t) c->C * (size_t) frames * FX_NUM_FEATURES * sizeof(float);
-    // from here on the analysis is enqueued: a failure loses this batch's results, not the ring (wait for the kernels that read the slot)
-    LG_TRY(hipEventRecord(sl.done, c->stream), (void) hipStreamSynchronize(c->stream));
-    LG_TRY(hipStreamWaitEvent(s->back, sl.done, 0), (void) hipStreamSynchronize(c->stream));
-    if (out_bytes) {
-        LG_TRY(hipMemcpyAsync(sl.h_raw, sl.d_raw, out_bytes, hipMemcpyDeviceToHost, s->back), (void) hipStreamSynchronize(c->stream));
-        LG_TRY(hipMemcpyAsync(sl.h_sm, sl.d_sm, out_bytes, hipMemcpyDeviceToHost, s->back), ((void) hipStreamSynchronize(c->stream), (void) hipStreamSynchronize(s->back)));
-    }
-    LG_TRY(hipEventRecord(sl.out, s->back), ((void) hipStreamSynchronize(c->stream), (void) hipStreamSynchronize(s->back)));
-#undef LG_TRY
+    // from here on the analysis is enqueued behind the copy: the context's stream has all the work that reads the slot, then `back`
+    g.readers[0] = c->stream; g.readers[1] = nullptr;
+    HIP_TRY(hipEventRecord(sl.done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(s->back, sl.done, 0));
+    if (out_bytes) HIP_TRY(hipMemcpyAsync(sl.h_raw, sl.d_raw, out_bytes, hipMemcpyDeviceToHost, s->back));
+    g.readers[1] = s->back;
+    if (out_bytes) HIP_TRY(hipMemcpyAsync(sl.h_sm, sl.d_sm, out_bytes, hipMemcpyDeviceToHost, s->back));
+    HIP_TRY(hipEventRecord(sl.out, s->back));
     sl.frames = frames; sl.by_event = true;
     s->head = (s->head + 1) % s->slots;
     s->in_flight++;
-    s->acquired = false;
+    g.ok = true;
     return FX_OK;
 }
 

@@ -22,6 +22,9 @@ fx_status fx_fail(fx_status code, const char* fmt, ...) __attribute__((format(pr
 struct fx_comm;     // fx_comm.cpp
 void fx_comm_release(fx_context* ctx);   // called by fx_destroy
 fx_status fx_check_device_error(fx_context* ctx);   // after a synchronisation: FX_ERR_HIP if a kernel reported a failed hand-over
+// appends an entry of `kind` to the context's launch record (fx_last_launches_internal) and returns it for the launcher's own fields;
+// null beyond FX_LAUNCH_RECORD_CAP.  The only writer of fx_context::launches.
+fx_launch_record* note_launch(fx_context* ctx, int kind, int analysers);
 
 // Analysis taps (fx_request_taps / fx_get_taps, include/fx.h) live in fx_taps.hip; this file only carries their state and the two hooks
 // fx_request_taps installs, so that the rest of the library refers to no symbol of that unit.

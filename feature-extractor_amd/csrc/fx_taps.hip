@@ -301,18 +301,6 @@ void taps_release(fx_context* c)
     c->taps_armed = 0;
 }
 
-void note_taps_launch(fx_context* c, int channels, bool blocks)
-{
-    const int i = c->num_launches++;
-    if (i >= FX_LAUNCH_RECORD_CAP) return;
-    fx_launch_record& r = c->launches[i];
-    r = fx_launch_record{};
-    r.kind = FX_LAUNCH_TAPS;
-    r.window = c->N;
-    r.T = channels;
-    r.block_mode = blocks ? 1 : 0;
-}
-
 fx_status taps_launch(fx_context* c, const fx_tap_source& src)
 {
     fx_taps* t = c->taps;
@@ -345,7 +333,7 @@ fx_status taps_launch(fx_context* c, const fx_tap_source& src)
     p.out = t->d_store;
     p.num = k;
     for (int i = 0; i < FX_MAX_TAP_CHANNELS; i++) p.channels[i] = i < k ? t->armed[i] : 0;
-    note_taps_launch(c, k, src.carry != nullptr);
+    if (fx_launch_record* r = note_launch(c, FX_LAUNCH_TAPS, 0)) { r->T = k; r->block_mode = src.carry ? 1 : 0; }
     const dim3 grid((unsigned) k), block(fxk::TAP_THREADS);
     switch (n) {
         case 256:  hipLaunchKernelGGL(fxk::fx_taps_kernel<256>, grid, block, 0, c->stream, p); break;

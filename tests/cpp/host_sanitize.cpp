@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>        // the FAKE one (tests/cpp/fake_hip/hip)
 
 #include "fx.h"
+#include "fx_kernels.h"           // fx_last_launches_internal: the launch record
 #include "fx_realtime.hpp"        // fx::LiveAnalyser, fx::OSCBatchSender: the live engine's threads run under the sanitizers too
 
 namespace {
@@ -47,6 +48,19 @@ struct World {
     int ring_fmt = FX_SAMPLE_F32;
 };
 
+// A ring submit of whole hops launches its step once: one launch of the frames, then at most the epilogue (a capture tried again after
+// a failed one must capture the step afresh, not append to what the failed one planned)
+void check_ring_record(World& w)
+{
+    fx_launch_record r[FX_LAUNCH_RECORD_CAP];
+    const int n = fx_last_launches_internal(w.ctx, r, FX_LAUNCH_RECORD_CAP);
+    if (n < 1 || n > 2 || r[0].kind == FX_LAUNCH_EPILOGUE || (n == 2 && r[1].kind != FX_LAUNCH_EPILOGUE)) {
+        char buf[64];
+        std::snprintf(buf, sizeof buf, "%d launches, the first of kind %d", n, n > 0 ? r[0].kind : 0);
+        problem("a ring submit after the fault launched more than its step:", buf);
+    }
+}
+
 // With the fault gone: the context analyses, the ring cycles, everything can be destroyed and nothing stays allocated.
 void recover_and_destroy(World& w, bool after_failure)
 {
@@ -55,6 +69,14 @@ void recover_and_destroy(World& w, bool after_failure)
         // whatever is in flight can be collected; a slot can be acquired and submitted again
         while (fx_stream_in_flight(w.ring) > 0)
             if (fx_stream_collect_samples(w.ring, nullptr, nullptr, nullptr) != FX_OK) { problem("collect after the fault"); break; }
+        // the submit a caller tries again first, in the state the fault left (the same slot, the same parity of the context's buffers);
+        // it may be refused (samples pending), not wedge the ring or launch more than its step
+        void* slot = nullptr;
+        if (fx_stream_acquire(w.ring, &slot) != FX_OK) problem("the ring is wedged: acquire right after the fault");
+        else if (fx_stream_submit(w.ring) == FX_OK) {
+            check_ring_record(w);
+            if (fx_stream_collect(w.ring, nullptr, nullptr) != FX_OK) problem("collect of the submit right after the fault");
+        }
     }
     if (w.ctx) {
         if (fx_reset_state(w.ctx) != FX_OK) problem("fx_reset_state after the fault");

@@ -1,7 +1,7 @@
 """The table of analysis dispatch paths: each row is an entry point, a configuration and the launch sequence the library must make
-for it (fx_last_launches_internal, BatchAnalyser.last_launches()).  The rows are derived from csrc/fx_capi.cpp -- prepare_step (workgroup
-shape, work units), run (hop kernel, one launch or two, two-hop calls as one-frame launches), fx_push_samples (block feed or re-blocking)
-and fx_stream_submit (hop kernel, captured step, the three-queue path) -- and from the launchers of csrc/fx_kernels.hip, fx_hop_kernel.hip.h
+for it (fx_last_launches_internal, BatchAnalyser.last_launches()).  The rows are derived from csrc/fx_capi.cpp -- plan_call (workgroup
+shape, work units, hop kernel, one launch or two, two-hop calls as one-frame launches, the ring's fixed routes), fx_push_samples (block
+feed or re-blocking) and fx_stream_submit (hop kernel, captured step or the three-queue path) -- and from the launchers of csrc/fx_kernels.hip, fx_hop_kernel.hip.h
 and fx_reblock.hip.  The union of the rows covers every launch form those files build, at every window size where it exists
 (tests/test_dispatch_cpu.py holds it to that); tests/test_gpu_dispatch.py runs every row on the device.
 
@@ -62,7 +62,7 @@ def row(id, N, entry, per, calls, expect, C=5, analysers="both", low_latency=Fal
 
 
 def _ch1(N, C=5):
-    """channels per workgroup of a one-frame call through the direct batch form (prepare_step): a workgroup's worth up to 1024 points,
+    """channels per workgroup of a one-frame call through the direct batch form (plan_call): a workgroup's worth up to 1024 points,
     four at 2048, at 4096 eight from 2048 channels on"""
     return min(C, 8 if N <= 1024 else (4 if N == 2048 else (8 if C >= 2048 else 4)))
 
