@@ -15,8 +15,11 @@ Launch forms (both work, and both run the ranks in the same environment -- rank_
            --master-port P bench.py --gpus N ...                    (the driver's form)
 
 Prints ONE JSON line on rank 0: the headline and its roofline, kept to a few KB so that a reader of the tail of stdout
-can parse it.  The extra measurements of a --gpus 1 run (spectral-only, other windows, live cadence, ...) go to stderr as one
-line `bench.py extras: {...}`.
+can parse it.  A plain run does only what that line needs: set up, warm up, time the steps, dump the outputs if asked, print.
+
+--full adds, on a --gpus 1 run, what takes runs or minutes of its own: the frame kernel's hardware counters (rocprofv3 --pmc
+children, into `roofline`), the CPU baseline (`cpu_baseline`) and the extra measurements (spectral-only, other windows, live
+cadence, ...), which go to stderr as one line `bench.py extras: {...}`.
 
 --dump-outputs DIR writes what the timed path returned in its last timed step (raw and smoothed feature vectors) as
 DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
@@ -433,12 +436,15 @@ def build_parser():
                     help="consecutive frames per channel per step (SURVEY 8d: T >= 64); default 512 at --gpus 1, 128 at --gpus N>1 "
                          "(8192 channels x 128 frames = 4.3 GB of input per GPU)")
     ap.add_argument("--window", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra measurements (spectral-only, noise / silence, other windows, live cadence)")
-    ap.add_argument("--only-extra", default=None, help="comma-separated names: run only these extra measurements (e.g. osc_sink,sustained)")
+    ap.add_argument("--full", action="store_true",
+                    help="at --gpus 1, also read the frame kernel's hardware counters (rocprofv3 --pmc children), run the CPU baseline and the "
+                         "extra measurements (stderr); a run without it does only the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full only: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full only: skip the extra measurements (spectral-only, noise / silence, other windows, live cadence)")
+    ap.add_argument("--only-extra", default=None, help="--full only: comma-separated names: run only these extra measurements (e.g. osc_sink,sustained)")
     ap.add_argument("--sustained-seconds", type=float, default=12.0, help="length of the `sustained` extra's back-to-back run of the headline step")
-    ap.add_argument("--no-pmc", action="store_true", help="do not read hardware counters in this run (rocprofv3 --pmc children)")
-    ap.add_argument("--write-counters", action="store_true", help="also store this run's counters in profiles/counters.json (the labelled fallback)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full only: do not read hardware counters in this run (rocprofv3 --pmc children)")
+    ap.add_argument("--write-counters", action="store_true", help="--full only: also store this run's counters in profiles/counters.json (the labelled fallback)")
     ap.add_argument("--signal", default="synth", choices=["synth", "noise", "silence"],
                     help="synth = the BASELINE synthetic mix (default); noise / silence probe data-dependent paths")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -492,6 +498,8 @@ def main():
     args = build_parser().parse_args()
     if args.steps < 1:
         build_parser().error("--steps must be at least 1")
+    if not args.full and (args.only_extra or args.write_counters):
+        build_parser().error("--only-extra and --write-counters need --full")
     rank_environment()                      # before anything can start the HIP runtime (both launch forms)
     if args.pmc_child:
         return pmc_child(args)
@@ -537,7 +545,9 @@ def rank_main(args, engine, rank, world):
         host_frames = np.random.default_rng(first).normal(0, 0.1, host_frames.shape).astype(np.float32)
     elif args.signal == "silence":
         host_frames = np.zeros_like(host_frames)
-    want_pmc = (world == 1 and engine.name == "gpu" and not args.no_pmc and not args.debug_collective)
+    # everything beyond the headline is --full's, and only a single-GPU run on the product library does it
+    full = args.full and world == 1 and not args.debug_collective
+    want_pmc = full and engine.name == "gpu" and not args.no_pmc
     input_file = None
     if want_pmc:
         try:
@@ -696,7 +706,7 @@ def rank_main(args, engine, rank, world):
                                                           "avg_launch_ms_unprofiled": avg_launch_s * 1e3}
                     json.dump(allrec, open(path, "w"), indent=1, sort_keys=True)
         else:
-            roof["counters_source"] = "not requested (--no-pmc, N>1 or debug run)"
+            roof["counters_source"] = "not requested (a run without --full, --no-pmc, N>1 or debug run)"
         out = {
             "metric": "frames/sec (1024-pt FFT, 10-feature bundle)" if N == 1024 else "frames/sec (%d-pt FFT, 10-feature bundle)" % N,
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -717,7 +727,7 @@ def rank_main(args, engine, rank, world):
         if dumped is not None:
             out["dumped_outputs"] = dumped
         side = None
-        if world == 1 and not args.no_extra and not args.debug_collective and engine.name == "gpu":
+        if full and not args.no_extra and engine.name == "gpu":
             side = extras(out, args, engine, fx, an, frames, raw, sm, N, count, T, launch_bytes, avg_launch_s,
                           spectral_input=input_file if (want_pmc and not under_profiler()) else None)
         if input_file:
@@ -725,7 +735,7 @@ def rank_main(args, engine, rank, world):
                 os.unlink(input_file)
             except OSError:
                 pass
-        if not args.no_cpu_baseline and world == 1 and not args.debug_collective:
+        if full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(fx, N, T)
             except Exception as e:          # the headline line must come out whatever happens to a side measurement

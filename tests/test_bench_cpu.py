@@ -20,6 +20,61 @@ def test_help_and_defaults():
     assert out.returncode == 0 and "--frames" in out.stdout and "--channels-per-gpu" in out.stdout
     a = bench.build_parser().parse_args([])
     assert (a.gpus, a.window, a.channels_per_gpu, a.frames) == (1, 1024, None, None)       # rank_main: 1024 x 512 at one GPU
+    assert not a.full                                                                       # a plain run is the headline alone
+
+
+def _rank_main_recording(monkeypatch, argv):
+    """rank_main on CPU (the oracle standing in for the analyser, under the product engine's name) with the side measurements
+    replaced by recorders: which of them ran, and the line."""
+    from test_sharded_cpu import _OracleEngine
+
+    class Engine(_OracleEngine):
+        name = "gpu"
+
+    ran = []
+
+    def counters(window, channels, frames, input_file, **kw):
+        ran.append("counters")
+        assert np.load(input_file).shape == (channels, frames, window)                 # the same bytes as the timed region
+        return {"FETCH_SIZE": 1.0, "WRITE_SIZE": 1.0}, "recorded"
+
+    def extras(*a, **kw):
+        ran.append("extras")
+        return {"recorded": True}
+
+    def cpu_baseline(*a, **kw):
+        ran.append("cpu_baseline")
+        return {"value": 1.0}
+
+    monkeypatch.setattr(bench, "measure_counters", counters)
+    monkeypatch.setattr(bench, "extras", extras)
+    monkeypatch.setattr(bench, "cpu_baseline", cpu_baseline)
+    args = bench.build_parser().parse_args(["--channels-per-gpu", "2", "--frames", "3", "--steps", "2", "--warmup", "1"] + argv)
+    return bench.rank_main(args, Engine(), 0, 1), ran
+
+
+def test_a_plain_run_does_only_the_headline(monkeypatch, capsys):
+    """Without --full a run sets up, warms up, times its steps and prints: no counter passes, no extras, no CPU baseline."""
+    d, ran = _rank_main_recording(monkeypatch, [])
+    assert ran == []
+    assert d["cpu_baseline"] is None and "not requested" in d["roofline"]["counters_source"] and d["roofline"]["traffic"] is None
+    assert d["steps"] == 2 and d["roofline"]["launches_timed"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert "bench.py extras" not in capsys.readouterr().err
+
+
+def test_full_adds_counters_extras_and_the_cpu_baseline(monkeypatch, capsys):
+    d, ran = _rank_main_recording(monkeypatch, ["--full"])
+    assert sorted(ran) == ["counters", "cpu_baseline", "extras"]
+    assert d["cpu_baseline"] == {"value": 1.0} and d["roofline"]["counters_source"] == "recorded" and d["roofline"]["traffic"] == 3 * 1024.0
+    assert 'bench.py extras: {"recorded": true}' in capsys.readouterr().err
+    d, ran = _rank_main_recording(monkeypatch, ["--full", "--no-pmc", "--no-extra", "--no-cpu-baseline"])
+    assert ran == [] and d["cpu_baseline"] is None
+
+
+def test_options_of_full_runs_are_refused_without_it():
+    for flag in (["--only-extra", "osc_sink"], ["--write-counters"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + flag, capture_output=True, text=True)
+        assert p.returncode == 2 and "--full" in p.stderr, flag
 
 
 def test_committed_counters_are_never_reported_stale(tmp_path):

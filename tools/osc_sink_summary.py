@@ -1,5 +1,5 @@
 """profiles/rNN_osc_sink.txt from a bench line:  python tools/osc_sink_summary.py profiles/r06_bench.json > profiles/r06_osc_sink.txt
-(or from bench.py's stderr, where the extras line `bench.py extras: {...}` carries `osc_sink` since the result line was cut to the headline)"""
+(or from the stderr of `bench.py --full`, where the extras line `bench.py extras: {...}` carries `osc_sink` since the result line was cut to the headline)"""
 import json
 import sys
 

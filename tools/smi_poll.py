@@ -1,6 +1,6 @@
 """Poll a GPU's clocks, power and temperature while another process keeps it busy: one JSON line per sample on stdout.
 
-Started as a CHILD by bench.py's `sustained` extra and tools/live_soak (never exec'd from a process that has initialised the GPU, and it
+Started as a CHILD by the `sustained` extra of `bench.py --full` and tools/live_soak (never exec'd from a process that has initialised the GPU, and it
 never initialises one itself: it reads the amdgpu driver's sysfs files -- /sys/class/drm/card*/device/{pp_dpm_sclk, pp_dpm_mclk,
 gpu_busy_percent, hwmon/hwmon*/{freq1_input, power1_average | power1_input, temp*_input}} -- and, where those are not readable, asks
 `rocm-smi --json`, which talks to the same driver through librocm_smi, not through HIP).
