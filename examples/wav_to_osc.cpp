@@ -9,7 +9,13 @@
 //
 //   wav_to_osc in.wav [--window 1024] [--channel 0] [--gain 1.0] [--address /Audio/A0]
 //                     [--target 127.0.0.1:9000] [--dump out.bin] [--rate 0] [--batch 64] [--device 0] [--pcm16-direct | --pcm24-direct]
-//                     [--device-block n]
+//                     [--device-block n] [--all-channels]
+//
+// --all-channels: one track per channel of the file, as the reference builds one AnalyserTrackController per active input
+// (MainComponent.cpp:140-170); track k sends /Audio/A<k> (--address and --channel do not apply).  The file's data chunk goes to the
+// GPU as it is, interleaved (fx::AudioDataCollector::pushInterleaved: fx_push_interleaved de-interleaves it there), in blocks of
+// --batch hops or of --device-block samples; --pcm16-direct / --pcm24-direct as below.  Track k's datagrams are byte for byte those of
+// --channel k --address /Audio/A<k>.
 //
 // --device-block n: the file is played to the analysers the way an audio device would deliver it -- in blocks of n samples (441, 480, 512,
 // anything) through fx::AudioDataCollector::audioDeviceIOCallback (ref AudioDataCollector.h:36-70), which analyses the hops as they complete
@@ -35,7 +41,7 @@ int main (int argc, char** argv)
     int window = 1024, channel = 0, batch = 64, device = 0, deviceBlock = 0;
     double rate = 0.0;
     float gain = 1.0f;
-    bool pcm16Direct = false, pcm24Direct = false;
+    bool pcm16Direct = false, pcm24Direct = false, allChannels = false;
     for (int i = 1; i < argc; ++i)
     {
         const std::string a = argv[i];
@@ -52,6 +58,7 @@ int main (int argc, char** argv)
         else if (a == "--device-block") deviceBlock = std::atoi (next());
         else if (a == "--pcm16-direct") pcm16Direct = true;
         else if (a == "--pcm24-direct") pcm24Direct = true;
+        else if (a == "--all-channels") allChannels = true;
         else if (a[0] != '-')      path = a;
         else { std::fprintf (stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
@@ -87,9 +94,9 @@ int main (int argc, char** argv)
     if (! target.empty() && ! sender.connectToAddress (target)) { std::fprintf (stderr, "bad target %s\n", target.c_str()); return 1; }
 
     long sent = 0;
-    auto emit = [&] (const float* smoothed12)
+    auto emitTo = [&] (const std::string& to, const float* smoothed12)
     {
-        const std::string msg = fx::OSCFeatureMessage (address, smoothed12);
+        const std::string msg = fx::OSCFeatureMessage (to, smoothed12);
         if (out != nullptr)
         {
             const unsigned n = (unsigned) msg.size();
@@ -97,16 +104,70 @@ int main (int argc, char** argv)
             std::fwrite (len, 1, 4, out);
             std::fwrite (msg.data(), 1, msg.size(), out);
         }
-        if (! target.empty()) sender.send (address, smoothed12);
+        if (! target.empty()) sender.send (to, smoothed12);
         ++sent;
     };
+    auto emit = [&] (const float* smoothed12) { emitTo (address, smoothed12); };
+    // hop `index` (0-based) has completed: what --rate makes of it -- one message per hop, or one per tick of the timer that reads it
+    long tick = 1;                                                   // next timer tick (k / rate seconds)
+    auto ticksOf = [&] (long index) -> long
+    {
+        if (rate <= 0.0) return 1;
+        // hop `index` is complete at sample (index + 1) * hop; it is what every tick in [that time, completion of the next hop) reads
+        const double from = (double) (index + 1) * (double) hop / wav.sampleRate;
+        const double to   = (double) (index + 2) * (double) hop / wav.sampleRate;
+        while ((double) tick / rate < from) ++tick;                  // ticks before the first result read nothing
+        long k = 0;
+        while ((double) tick / rate < to) { ++k; ++tick; }
+        return k;
+    };
+
+    if (allChannels)
+    {
+        const int K = wav.numChannels;
+        const void* data = wav.interleaved.data();
+        int format = FX_SAMPLE_F32;
+        std::size_t bytes = sizeof (float);
+        if (pcm16Direct) { data = wav.pcm16.data(); format = FX_SAMPLE_S16; bytes = 2; }
+        if (pcm24Direct) { data = wav.pcm24.data(); format = FX_SAMPLE_S24; bytes = 3; }
+        const std::size_t frames = wav.numFrames(), step = deviceBlock > 0 ? (std::size_t) deviceBlock : (std::size_t) batch * hop;
+        try
+        {
+            fx::RealTimeBatchAnalyser analyser (K, window, (double) wav.sampleRate, device);
+            analyser.setGain (gain);
+            fx::AudioDataCollector collector (analyser);
+            long done = 0;
+            for (std::size_t at = 0; at < frames; at += step)
+            {
+                const int len = (int) (frames - at < step ? frames - at : step);
+                const int n = collector.pushInterleaved (static_cast<const unsigned char*> (data) + at * (std::size_t) K * bytes, K, len, format);
+                for (int t = 0; t < n; ++t)
+                {
+                    const long repeat = ticksOf (done + t);
+                    for (long r = 0; r < repeat; ++r)
+                        for (int k = 0; k < K; ++k)
+                            emitTo ("/Audio/A" + std::to_string (k), collector.smoothed() + ((std::size_t) k * (std::size_t) n + (std::size_t) t) * FX_NUM_FEATURES);
+                }
+                done += n;
+            }
+        }
+        catch (const fx::Error& e)
+        {
+            std::fprintf (stderr, "analysis failed: %s\n", e.what());
+            if (out != nullptr) std::fclose (out);
+            return 1;
+        }
+        if (out != nullptr) std::fclose (out);
+        std::printf ("%s: %d Hz, %d channel(s), %d-bit%s; %d hops of %zu samples; %ld OSC messages (/Audio/A0 .. /Audio/A%d)\n", path.c_str(),
+                     wav.sampleRate, wav.numChannels, wav.bitsPerSample, wav.isFloat ? " float" : "", numHops, hop, sent, K - 1);
+        return 0;
+    }
 
     try
     {
         fx::RealTimeBatchAnalyser analyser (1, window, (double) wav.sampleRate, device);
         analyser.setGain (gain);
         std::vector<float> raw ((std::size_t) batch * FX_NUM_FEATURES), smoothed ((std::size_t) batch * FX_NUM_FEATURES);
-        long tick = 1;                                               // next timer tick (k / rate seconds)
         fx::AudioDataCollector collector (analyser);
         const std::vector<float> mono = deviceBlock > 0 ? wav.channel (channel) : std::vector<float>();
         const std::vector<std::int16_t> mono16 = (deviceBlock > 0 && pcm16Direct) ? fx::samplesOfChannelPCM16 (wav, channel) : std::vector<std::int16_t>();
@@ -131,16 +192,7 @@ int main (int argc, char** argv)
             else if (pcm24Direct) analyser.pushHopsPCM24 (hops24.data() + (std::size_t) done * hop * 3, n, raw.data(), smoothed.data());
             else                  analyser.pushHops (hops.data() + (std::size_t) done * hop, n, raw.data(), smoothed.data());
             for (int t = 0; t < n; ++t)
-            {
-                const float* v = values + (std::size_t) t * FX_NUM_FEATURES;
-                if (rate <= 0.0) { emit (v); continue; }
-                // hop (done + t) is complete at sample (done + t + 1) * hop; it is what every tick in
-                // [that time, completion of the next hop) reads
-                const double from = (double) (done + t + 1) * (double) hop / wav.sampleRate;
-                const double to   = (double) (done + t + 2) * (double) hop / wav.sampleRate;
-                while ((double) tick / rate < from) ++tick;          // ticks before the first result read nothing
-                while ((double) tick / rate < to) { emit (v); ++tick; }
-            }
+                for (long r = ticksOf (done + t); r > 0; --r) emit (values + (std::size_t) t * FX_NUM_FEATURES);
             done += n;
         }
     }

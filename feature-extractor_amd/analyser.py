@@ -31,6 +31,24 @@ def pack_s24(values):
 _FORMAT_NAMES = {"f32": capi.SAMPLE_F32, "f16": capi.SAMPLE_F16, "s16": capi.SAMPLE_S16, "s24": capi.SAMPLE_S24}
 
 
+def interleaved_dims(shape, size, fmt, num_source_channels=None):
+    """(frames n, source channels K) of an interleaved block: K is num_source_channels, or the last axis of a 2-D block (in samples:
+    a third of it for packed s24).  ValueError unless the block holds whole frames of K samples."""
+    per = 3 if fmt == capi.SAMPLE_S24 else 1
+    if num_source_channels is None:
+        if len(shape) != 2:
+            raise ValueError("an interleaved block is [n][K] (uint8 [n][3K] for s24), or give num_source_channels")
+        if shape[1] % per:
+            raise ValueError("a frame of packed 24-bit samples is a multiple of 3 bytes, not %d" % shape[1])
+        num_source_channels = shape[1] // per
+    K = int(num_source_channels)
+    if K < 1:
+        raise ValueError("an interleaved block has at least one source channel")
+    if size % (K * per):
+        raise ValueError("input size is not a multiple of the source channel count (%d)" % K)
+    return size // (K * per), K
+
+
 class BatchAnalyser:
     def __init__(self, num_channels, window_size=2048, sample_rate=48000.0, device=0,
                  order=capi.ORDER_SPECTRAL_THEN_HARMONIC, analysers="both", low_latency=False):
@@ -350,6 +368,77 @@ class BatchAnalyser:
         capi.check(self._lib.fx_push_samples(self._h, x.ctypes.data_as(ctypes.c_void_p), n, fmt, capi.MEM_HOST,
                                              raw.ctypes.data_as(ctypes.c_void_p) if raw is not None and frames else None,
                                              sm.ctypes.data_as(ctypes.c_void_p) if sm is not None and frames else None, ctypes.byref(frames_out)))
+        assert frames_out.value == frames
+        return raw, sm
+
+    # ---- interleaved input through a per-track channel map (include/fx.h, fx_set_channel_map / fx_push_interleaved) ----
+    def set_channel_map(self, channel_map):
+        """AudioDataCollector::setChannelToCollect for every track at once: track c collects source channel channel_map[c] of the
+        blocks given to push_interleaved; None restores the identity.  Pending samples and histories are kept."""
+        if channel_map is None:
+            capi.check(self._lib.fx_set_channel_map(self._h, None))
+            return
+        m = np.ascontiguousarray(np.asarray(channel_map, dtype=np.int32).ravel())
+        if m.size != self.num_channels:
+            raise ValueError("a channel map has one entry per track (%d), not %d" % (self.num_channels, m.size))
+        capi.check(self._lib.fx_set_channel_map(self._h, m.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+
+    def push_interleaved(self, block, want_raw=True, want_smoothed=True, sample_format=None, num_source_channels=None):
+        """block [n][K] of K source channels per frame (uint8 [n][3K] for s24; a flat block needs num_source_channels) -> (raw, smoothed)
+        as push_samples returns them for the planar block [c][i] = block[i][map[c]].  numpy (host) or torch CUDA tensors."""
+        C, H = self.num_channels, self.window_size // 2
+        if sample_format is not None and sample_format not in _FORMAT_NAMES:
+            raise ValueError("sample_format must be one of %s" % ", ".join(sorted(_FORMAT_NAMES)))
+        want = None if sample_format is None else _FORMAT_NAMES[sample_format]
+        frames_out = ctypes.c_int(0)
+        if _is_torch(block):
+            import torch
+            x = block
+            if not x.is_cuda or not x.is_contiguous() or x.device.index != self.device:
+                raise ValueError("torch input must be a contiguous tensor on cuda:%d" % self.device)
+            fmt = {torch.float32: capi.SAMPLE_F32, torch.float16: capi.SAMPLE_F16, torch.int16: capi.SAMPLE_S16, torch.uint8: capi.SAMPLE_S24}.get(x.dtype)
+            if fmt is None or (fmt == capi.SAMPLE_S24 and want != capi.SAMPLE_S24) or (want is not None and want != fmt):
+                raise ValueError("samples must be float32, float16, int16, or uint8 with sample_format=\"s24\"")
+            n, K = interleaved_dims(tuple(x.shape), x.numel(), fmt, num_source_channels)
+            if x.data_ptr() % 4:
+                raise ValueError("device input must start on a 4-byte boundary")
+            frames = (self.pending_samples() + n) // H
+            raw = torch.empty((C, frames, 12), dtype=torch.float32, device=x.device) if want_raw else None
+            sm = torch.empty((C, frames, 12), dtype=torch.float32, device=x.device) if want_smoothed else None
+            cur = torch.cuda.current_stream(x.device)
+            lib = self._torch_stream(x.device)
+            foreign = cur.cuda_stream != lib.cuda_stream
+            if foreign:
+                lib.wait_stream(cur)
+            capi.check(self._lib.fx_push_interleaved(self._h, ctypes.c_void_p(x.data_ptr()), n, K, fmt, capi.MEM_DEVICE,
+                                                     ctypes.c_void_p(raw.data_ptr()) if raw is not None and frames else None,
+                                                     ctypes.c_void_p(sm.data_ptr()) if sm is not None and frames else None, ctypes.byref(frames_out)))
+            if foreign:
+                cur.wait_stream(lib)
+            assert frames_out.value == frames
+            return raw, sm
+        tagged = isinstance(block, PackedS24)
+        x = np.ascontiguousarray(block)
+        if x.dtype == np.float16:
+            fmt = capi.SAMPLE_F16
+        elif x.dtype == np.int16:
+            fmt = capi.SAMPLE_S16
+        elif x.dtype == np.uint8:
+            if not (tagged or want == capi.SAMPLE_S24):
+                raise ValueError('uint8 samples are packed 24-bit PCM only with sample_format="s24" (or as a PackedS24 array)')
+            fmt = capi.SAMPLE_S24
+        else:
+            x = np.ascontiguousarray(x, np.float32)
+            fmt = capi.SAMPLE_F32
+        if want is not None and want != fmt:
+            raise ValueError("sample_format=%r does not describe a %s array" % (sample_format, x.dtype))
+        n, K = interleaved_dims(x.shape, x.size, fmt, num_source_channels)
+        frames = (self.pending_samples() + n) // H
+        raw = np.empty((C, frames, 12), np.float32) if want_raw else None
+        sm = np.empty((C, frames, 12), np.float32) if want_smoothed else None
+        capi.check(self._lib.fx_push_interleaved(self._h, x.ctypes.data_as(ctypes.c_void_p), n, K, fmt, capi.MEM_HOST,
+                                                 raw.ctypes.data_as(ctypes.c_void_p) if raw is not None and frames else None,
+                                                 sm.ctypes.data_as(ctypes.c_void_p) if sm is not None and frames else None, ctypes.byref(frames_out)))
         assert frames_out.value == frames
         return raw, sm
 

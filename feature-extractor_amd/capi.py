@@ -32,14 +32,15 @@ EXPORTS = ["fx_create", "fx_destroy", "fx_reset_state", "fx_set_sample_rate", "f
            "fx_offline_create", "fx_offline_destroy", "fx_offline_reset", "fx_offline_sync", "fx_offline_get_previous_f0", "fx_offline_zero_crosses",
            "fx_offline_log_attack_time", "fx_offline_fft_lbp", "fx_offline_harmonic_characteristics", "fx_offline_spectral_characteristics",
            "fx_offline_get_previous_bins", "fx_offline_spectral_slope", "fx_offline_auto_correlation",
-           "fx_request_taps", "fx_get_taps"]
+           "fx_request_taps", "fx_get_taps", "fx_set_channel_map", "fx_push_interleaved"]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
 MAX_UNITS = 24
 # fx_last_launches_internal (csrc/fx_kernels.h, tests only): struct fx_launch_record, field by field, and FX_LAUNCH_* by number
 LAUNCH_FIELDS = ["kind", "window", "analysers", "T", "direct_state", "block_mode", "num_chunks", "ch_per_wg", "waves_per_ch", "hop_pairs",
                  "ep_T", "out_stride", "ep_form", "reblock"]
-LAUNCH_KINDS = {1: "frame", 2: "frame_tail", 3: "hop", 4: "hop_pair", 5: "pair", 6: "epilogue", 7: "reblock", 8: "osc", 9: "taps"}
+LAUNCH_KINDS = {1: "frame", 2: "frame_tail", 3: "hop", 4: "hop_pair", 5: "pair", 6: "epilogue", 7: "reblock", 8: "osc", 9: "taps",
+                10: "deinterleave"}
 MAX_TAP_CHANNELS = 64
 LAUNCH_RECORD_CAP = 8
 
@@ -152,6 +153,8 @@ def load_library(build_if_missing=True):
     L.fx_comm_sync.argtypes = [vp]
     L.fx_comm_stats.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(d), ctypes.POINTER(d)]
     L.fx_request_taps.argtypes = [vp, ctypes.POINTER(i), i]
+    L.fx_set_channel_map.argtypes = [vp, ctypes.POINTER(i)]
+    L.fx_push_interleaved.argtypes = [vp, vp, i, i, i, i, vp, vp, ctypes.POINTER(i)]
     L.fx_get_taps.argtypes = [vp, i, fp, fp, fp, fp, fp, fp, ctypes.POINTER(ctypes.c_longlong)]
     L.fx_plan_units.argtypes = [i, u, i, i, ctypes.POINTER(Tuning), ctypes.POINTER(i), i]
     L.fx_twiddle_symmetry.argtypes = [i]

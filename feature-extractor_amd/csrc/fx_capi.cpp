@@ -752,6 +752,7 @@ fx_status fx_destroy(fx_context* c)
     fx_comm_release(c);
     if (c->stream) (void) hipStreamSynchronize(c->stream);
     if (c->taps_release) c->taps_release(c);
+    if (c->interleave_release) c->interleave_release(c);
     void* bufs[] = {c->d_tw, c->d_prev, c->d_tail[0], c->d_tail[1], c->d_hist, c->d_latest,
                     c->d_raw, c->d_part, c->d_in, c->d_out_raw, c->d_queue, c->d_carry[0], c->d_carry[1], c->d_hops, c->d_osc};
     for (void* b : bufs) if (b) (void) hipFree(b);
@@ -835,41 +836,50 @@ fx_status fx_clear_pending(fx_context* c)
     return FX_OK;
 }
 
-// fx_push_samples; `taps`: whether the call serves armed taps (the ring's submissions do not, include/fx.h)
-static fx_status push_samples(fx_context* c, const void* samples, int num_samples, int sample_format, int mem_kind,
-                              float* out_raw, float* out_smoothed, int* frames_out, bool taps)
+// the refusals of a block that depend on the context's pending samples alone (fx_context.h): fx_push_block makes them, and
+// fx_push_interleaved makes them before its de-interleave launch
+extern "C++" fx_status fx_block_refusal(const fx_context* c, int num_samples, int sample_format)
 {
-    if (frames_out) *frames_out = 0;
-    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
-    begin_launches(c);
-    if (num_samples < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative sample count");
-    if (!known_format(sample_format)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown sample format %d", sample_format);
-    if (mem_kind != FX_MEM_HOST && mem_kind != FX_MEM_DEVICE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", mem_kind);
-    if (num_samples == 0) return FX_OK;
-    if (!samples) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null input buffer");
     if (c->carry_count > 0 && sample_format != c->carry_format)
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d pending samples per channel are in sample format %d, this block in %d: a stream keeps one format "
                                                 "between hop boundaries", c->carry_count, c->carry_format, sample_format);
+    if (((long long) c->carry_count + num_samples) / (c->N / 2) > (1ll << 24))
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "block of %d samples per channel is too long for one call", num_samples);
+    return FX_OK;
+}
+
+// the block path of fx_push_samples (fx_context.h): the launch record is the caller's
+extern "C++" fx_status fx_push_block(fx_context* c, const void* samples, int num_samples, int sample_format, int in_kind, int out_kind,
+                        float* out_raw, float* out_smoothed, int* frames_out, bool taps)
+{
+    if (frames_out) *frames_out = 0;
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    if (num_samples < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative sample count");
+    if (!known_format(sample_format)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown sample format %d", sample_format);
+    if ((in_kind != FX_MEM_HOST && in_kind != FX_MEM_DEVICE) || (out_kind != FX_MEM_HOST && out_kind != FX_MEM_DEVICE))
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", in_kind != FX_MEM_HOST && in_kind != FX_MEM_DEVICE ? in_kind : out_kind);
+    if (num_samples == 0) return FX_OK;
+    if (!samples) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null input buffer");
+    { const fx_status rs = fx_block_refusal(c, num_samples, sample_format); if (rs != FX_OK) return rs; }
     const int H = c->N / 2;
     const size_t esz = sample_size(sample_format);
     const long long have = (long long) c->carry_count + num_samples;
     const long long hops64 = have / H;
-    if (hops64 > (1ll << 24)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "block of %d samples per channel is too long for one call", num_samples);
     const int hops = (int) hops64, rest = (int) (have - hops64 * H);
     HIP_TRY(hipSetDevice(c->device));
     { const fx_status es = fx_check_device_error(c); if (es != FX_OK) return es; }
 
     // whole hops and nothing pending: the block IS the hop buffer -- from an aligned device buffer, or a host block (512-sample callbacks
     // against a 1024-point window: one copy in, no re-blocking)
-    if (c->carry_count == 0 && rest == 0 && (mem_kind == FX_MEM_HOST || reinterpret_cast<uintptr_t>(samples) % 16 == 0)) {
-        const fx_status st = run(c, samples, hops, sample_format, mem_kind, mem_kind, 1, out_raw, out_smoothed, nullptr, taps);
+    if (c->carry_count == 0 && rest == 0 && (in_kind == FX_MEM_HOST || reinterpret_cast<uintptr_t>(samples) % 16 == 0)) {
+        const fx_status st = run(c, samples, hops, sample_format, in_kind, out_kind, 1, out_raw, out_smoothed, nullptr, taps);
         if (st == FX_OK && frames_out) *frames_out = hops;
         return st;
     }
     fx_status st;
     const unsigned char* d_block = static_cast<const unsigned char*>(samples);
     const size_t block_bytes = (size_t) c->C * (size_t) num_samples * esz;
-    if (mem_kind == FX_MEM_HOST) {
+    if (in_kind == FX_MEM_HOST) {
         if ((st = grow(reinterpret_cast<unsigned char**>(&c->d_in), &c->in_cap, block_bytes)) != FX_OK) return st;
         HIP_TRY(hipMemcpyAsync(c->d_in, samples, block_bytes, hipMemcpyHostToDevice, c->stream));
         d_block = static_cast<const unsigned char*>(c->d_in);
@@ -883,7 +893,7 @@ static fx_status push_samples(fx_context* c, const void* samples, int num_sample
         // analysis.  (Windows of 2048 / 4096 points re-block calls of more than two hops: measured faster there, fx_kernels.hip launch_t.)
         const BlockFeed feed = {c->d_carry[c->carry_cur], c->d_carry[c->carry_cur ^ 1], (int) ((size_t) c->carry_count * esz), H * 4,
                                 (long long) num_samples * (long long) esz};
-        st = run(c, d_block, hops, sample_format, FX_MEM_DEVICE, mem_kind, 1, out_raw, out_smoothed, &feed, taps);
+        st = run(c, d_block, hops, sample_format, FX_MEM_DEVICE, out_kind, 1, out_raw, out_smoothed, &feed, taps);
         if (st != FX_OK) return st;             // (the stream is no longer the caller's: fx_reset_state, as the contract says)
         c->carry_cur ^= 1;
         c->carry_count = rest;
@@ -915,13 +925,23 @@ static fx_status push_samples(fx_context* c, const void* samples, int num_sample
     c->carry_count = rest;
     c->carry_format = sample_format;
     if (hops > 0) {
-        st = run(c, c->d_hops, hops, sample_format, FX_MEM_DEVICE, mem_kind, 1, out_raw, out_smoothed);
+        st = run(c, c->d_hops, hops, sample_format, FX_MEM_DEVICE, out_kind, 1, out_raw, out_smoothed);
         if (st != FX_OK) return st;
-    } else if (mem_kind == FX_MEM_HOST) {
+    } else if (in_kind == FX_MEM_HOST) {
         HIP_TRY(hipStreamSynchronize(c->stream));            // the caller's block may be reused on return
     }
     if (frames_out) *frames_out = hops;
     return FX_OK;
+}
+
+// fx_push_samples; `taps`: whether the call serves armed taps (the ring's submissions do not, include/fx.h)
+static fx_status push_samples(fx_context* c, const void* samples, int num_samples, int sample_format, int mem_kind,
+                              float* out_raw, float* out_smoothed, int* frames_out, bool taps)
+{
+    if (frames_out) *frames_out = 0;
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    begin_launches(c);
+    return fx_push_block(c, samples, num_samples, sample_format, mem_kind, mem_kind, out_raw, out_smoothed, frames_out, taps);
 }
 
 fx_status fx_push_samples(fx_context* c, const void* samples, int num_samples, int sample_format, int mem_kind,

@@ -26,9 +26,19 @@ fx_status fx_check_device_error(fx_context* ctx);   // after a synchronisation: 
 // null beyond FX_LAUNCH_RECORD_CAP.  The only writer of fx_context::launches.
 fx_launch_record* note_launch(fx_context* ctx, int kind, int analysers);
 
+// fx_push_samples after its launch record is started: a block of num_samples samples per channel, [C][num_samples], from in_kind memory
+// (a device block 4-byte aligned), results to out_kind memory.  Re-blocking, the block feed, taps and the carry all happen here, so that
+// fx_push_interleaved (fx_interleave.hip) hands over the planar block it assembled and shares every step after it.
+fx_status fx_push_block(fx_context* ctx, const void* samples, int num_samples, int sample_format, int in_kind, int out_kind,
+                        float* out_raw, float* out_smoothed, int* frames_out, bool taps);
+// fx_push_block's refusals that depend on the pending samples alone (a format change while samples are pending, a block of more than
+// 2^24 hops): FX_ERR_INVALID_ARGUMENT or FX_OK, no device use.  fx_push_interleaved makes them before it launches anything.
+fx_status fx_block_refusal(const fx_context* ctx, int num_samples, int sample_format);
+
 // Analysis taps (fx_request_taps / fx_get_taps, include/fx.h) live in fx_taps.hip; this file only carries their state and the two hooks
 // fx_request_taps installs, so that the rest of the library refers to no symbol of that unit.
 struct fx_taps;
+struct fx_interleave;   // fx_interleave.hip
 // Where an analysis call reads its FIRST frame, as the kernels read it: `in` (device) holds rows of in_row_bytes per channel; hop_mode 1:
 // hops of N/2 samples, the window is [the channel's tail | hop 0 x gain]; 0: whole frames, frame 0 as given.  carry != null: the hop is
 // the first N/2 samples of [pending | block] (fx_blocks.hip.h, BlockStream), the pending row of the channel at carry + c * carry_row_bytes.
@@ -109,6 +119,11 @@ struct fx_context {
     int      taps_armed = 0;
     fx_status (*taps_launch)(fx_context*, const fx_tap_source&) = nullptr;   // capture the call's first frame; clears the request
     void      (*taps_release)(fx_context*) = nullptr;                         // drop request, capture and memory (reset, destroy)
+
+    // interleaved input (fx_interleave.hip): the channel map, its device copy and the staging buffers; null until the first
+    // fx_set_channel_map / fx_push_interleaved, which installs the hook.  The map is a setting: fx_destroy calls the hook, fx_reset_state does not.
+    fx_interleave* interleave = nullptr;
+    void (*interleave_release)(fx_context*) = nullptr;
 };
 
 #endif

@@ -1,0 +1,295 @@
+// fx_interleave.hip -- interleaved input through a per-track channel map (include/fx.h, fx_set_channel_map / fx_push_interleaved).
+//
+// ref MainComponent.cpp:140-170 builds one track per active input of the audio device, and each track's AudioDataCollector collects
+// one device channel, channelData[channelToCollect] (AudioDataCollector.h:21-23,36-70), which setChannelToCollect (:123) moves while
+// the stream runs.  Here every track's source is one entry of the context's channel map, and a block arrives as the device and file
+// formats carry it, interleaved: [n][K] frames of K source channels.  One launch of fx_deinterleave_kernel turns it into the planar
+// block [C][n] that fx_push_samples takes (track c's row = source map[c]) in a staging buffer, and fx_push_block (fx_capi.cpp) does
+// the rest: the same launches, the same bits as fx_push_samples of that planar block.  Bytes only: no conversion, no gain (the
+// analysis kernels' load stage does both).
+//
+// Nothing in fx_capi.cpp refers to this unit: the first fx_set_channel_map / fx_push_interleaved installs the context's release hook.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <new>
+#include <vector>
+
+#include "fx_kernels.h"
+#include "fx_context.h"
+
+namespace fxk {
+namespace {
+
+// A workgroup takes DI_FRAMES frames of DI_TRACKS consecutive tracks.  Load: lane = track, wavefront = frame, so a wavefront reads
+// samples[f][map[c0 .. c0 + 63]] -- one contiguous run of 64 samples for the identity map or any map of consecutive sources.  The tile
+// goes to LDS as rows of tracks, each row placed at the byte its planar destination has modulo 16, so that the store reads whole
+// 16-byte chunks back (ds_read_b128) and writes them to 16-byte aligned addresses (global_store_dwordx4), consecutive lanes along a
+// row and on into the next one.  Only the first and last chunk of a row's segment are partial: they are written byte by byte, each
+// byte once, whatever the row pitch n * B makes of the alignment.
+constexpr int DI_FRAMES = 64, DI_TRACKS = 64, DI_THREADS = 256;
+static_assert(DI_THREADS == 4 * 64 && DI_TRACKS == 64, "lane = track, four wavefronts step through the frames");
+
+struct DeinterleaveParams {
+    const unsigned char* in;    // [n][K] samples of B bytes
+    const int*           map;   // [C], 0 <= map[c] < K
+    unsigned char*       out;   // [C][n] samples of B bytes, 16-byte aligned
+    long long            n;
+    int                  K, C;
+};
+
+// Byte `col` of tile row r: chunks of 16 bytes in order, the four dwords of a chunk rotated by (r / 8) % 4.  Row pitches of a whole
+// number of chunks put rows r and r + 8 on the same banks; the rotation moves them apart, so the load stage's stores (32 lanes = 32
+// rows at one column) fall on 32 distinct banks.  The store stage's reads of whole chunks are not affected.
+__device__ __forceinline__ int tile_at(int r, int row_bytes, int col)
+{
+    return r * row_bytes + (col & ~15) + ((((col >> 2) + (r >> 3)) & 3) << 2) + (col & 3);
+}
+
+template <int B> __device__ __forceinline__ unsigned load_sample(const unsigned char* p)
+{
+    if constexpr (B == 4) return *reinterpret_cast<const unsigned*>(p);
+    else if constexpr (B == 2) return *reinterpret_cast<const unsigned short*>(p);
+    else return (unsigned) p[0] | ((unsigned) p[1] << 8) | ((unsigned) p[2] << 16);
+}
+
+// (a row's offset modulo 16 is a multiple of B's alignment for 2- and 4-byte samples: those never straddle a dword of the tile)
+template <int B> __device__ __forceinline__ void store_sample(unsigned char* tile, int r, int row_bytes, int col, unsigned v)
+{
+    if constexpr (B == 4) *reinterpret_cast<unsigned*>(tile + tile_at(r, row_bytes, col)) = v;
+    else if constexpr (B == 2) *reinterpret_cast<unsigned short*>(tile + tile_at(r, row_bytes, col)) = (unsigned short) v;
+    else {
+#pragma unroll
+        for (int i = 0; i < 3; i++) tile[tile_at(r, row_bytes, col + i)] = (unsigned char) (v >> (8 * i));
+    }
+}
+
+__device__ __forceinline__ unsigned pick(const uint4& q, int j)
+{
+    j &= 3;
+    return j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w;
+}
+
+template <int B>
+__global__ void __launch_bounds__(DI_THREADS)
+fx_deinterleave_kernel(const DeinterleaveParams p)
+{
+    constexpr int CHUNKS = DI_FRAMES * B / 16 + 1;      // a row's segment of DI_FRAMES * B bytes, placed at its offset modulo 16
+    constexpr int ROW = 16 * CHUNKS;
+    __shared__ __attribute__((aligned(16))) unsigned char tile[DI_TRACKS * ROW];
+    const long long f0 = (long long) blockIdx.x * DI_FRAMES;
+    const int c0 = (int) blockIdx.y * DI_TRACKS;
+    const int nf = p.n - f0 < DI_FRAMES ? (int) (p.n - f0) : DI_FRAMES;
+    const long long row_bytes = p.n * B;
+
+    {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = c0 + lane;
+        if (c < p.C) {
+            const int m = (int) (((long long) c * row_bytes + f0 * B) & 15);
+            const unsigned char* src = p.in + (f0 * p.K + p.map[c]) * B;
+            const long long pitch = (long long) p.K * B;
+            unsigned v[DI_FRAMES / 4];
+#pragma unroll
+            for (int j = 0; j < DI_FRAMES / 4; j++) {
+                const int f = wave + 4 * j;
+                if (f < nf) v[j] = load_sample<B>(src + f * pitch);
+            }
+#pragma unroll
+            for (int j = 0; j < DI_FRAMES / 4; j++) {
+                const int f = wave + 4 * j;
+                if (f < nf) store_sample<B>(tile, lane, ROW, m + f * B, v[j]);
+            }
+        }
+    }
+    __syncthreads();
+
+    for (int i = threadIdx.x; i < DI_TRACKS * CHUNKS; i += DI_THREADS) {
+        const int r = i / CHUNKS, k = i - r * CHUNKS, c = c0 + r;
+        if (c >= p.C) break;                                // (r only grows with i)
+        const long long seg = (long long) c * row_bytes + f0 * B;
+        const int m = (int) (seg & 15);
+        const int lo = m > 16 * k ? m : 16 * k, hi = m + nf * B < 16 * k + 16 ? m + nf * B : 16 * k + 16;
+        if (lo >= hi) continue;
+        const uint4 s = *reinterpret_cast<const uint4*>(tile + r * ROW + 16 * k);
+        const int rot = r >> 3;
+        const uint4 q{pick(s, rot), pick(s, rot + 1), pick(s, rot + 2), pick(s, rot + 3)};
+        unsigned char* dst = p.out + (seg - m) + 16 * k;
+        if (hi - lo == 16) {
+            *reinterpret_cast<uint4*>(dst) = q;
+        } else {
+            for (int b = lo - 16 * k; b < hi - 16 * k; b++) dst[b] = (unsigned char) (pick(q, b >> 2) >> (8 * (b & 3)));
+        }
+    }
+}
+
+hipError_t launch_deinterleave_kernel(const DeinterleaveParams& p, int bytes_per_sample, hipStream_t stream)
+{
+    if (p.n <= 0 || p.C <= 0) return hipSuccess;
+    const long long gx = (p.n + DI_FRAMES - 1) / DI_FRAMES, gy = ((long long) p.C + DI_TRACKS - 1) / DI_TRACKS;
+    if (gx > 0x7fffffffll || gy > 65535) return hipErrorInvalidValue;
+    const dim3 grid((unsigned) gx, (unsigned) gy), block(DI_THREADS);
+    switch (bytes_per_sample) {
+        case 4: hipLaunchKernelGGL(fx_deinterleave_kernel<4>, grid, block, 0, stream, p); break;
+        case 3: hipLaunchKernelGGL(fx_deinterleave_kernel<3>, grid, block, 0, stream, p); break;
+        case 2: hipLaunchKernelGGL(fx_deinterleave_kernel<2>, grid, block, 0, stream, p); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+} // namespace
+} // namespace fxk
+
+struct fx_interleave {
+    std::vector<int> map;               // [C]: track c collects source map[c]
+    int              max_source = 0;    // the largest entry: blocks of fewer source channels are refused
+    int*             d_map = nullptr;   // device copy of map
+    unsigned char*   d_src = nullptr;   // a host block's interleaved samples
+    unsigned char*   d_planar = nullptr;// the planar block handed to fx_push_block
+    size_t           src_cap = 0, planar_cap = 0;
+};
+
+namespace {
+
+bool known_format(int f) { return f == FX_SAMPLE_F32 || f == FX_SAMPLE_F16 || f == FX_SAMPLE_S16 || f == FX_SAMPLE_S24; }
+int sample_size(int f) { return f == FX_SAMPLE_F32 ? 4 : (f == FX_SAMPLE_S24 ? 3 : 2); }
+
+void interleave_release(fx_context* c)
+{
+    fx_interleave* s = c->interleave;
+    if (!s) return;
+    void* bufs[] = {s->d_map, s->d_src, s->d_planar};
+    for (void* b : bufs) if (b) (void) hipFree(b);
+    delete s;
+    c->interleave = nullptr;
+}
+
+// the context's state for interleaved input, with the identity map on first use
+fx_status interleave_state(fx_context* c, fx_interleave** out)
+{
+    if (!c->interleave) {
+        std::vector<int> identity((size_t) c->C);
+        for (int i = 0; i < c->C; i++) identity[(size_t) i] = i;
+        void* q = nullptr;
+        HIP_TRY(hipMalloc(&q, sizeof(int) * (size_t) c->C));
+        const hipError_t e = hipMemcpy(q, identity.data(), sizeof(int) * (size_t) c->C, hipMemcpyHostToDevice);
+        fx_interleave* s = e == hipSuccess ? new (std::nothrow) fx_interleave() : nullptr;
+        if (!s) {
+            (void) hipFree(q);
+            return e != hipSuccess ? fx_fail(FX_ERR_HIP, "hipMemcpy of the channel map failed: %s", hipGetErrorString(e))
+                                   : fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
+        }
+        s->map.swap(identity);
+        s->max_source = c->C - 1;
+        s->d_map = static_cast<int*>(q);
+        c->interleave = s;
+        c->interleave_release = interleave_release;
+    }
+    *out = c->interleave;
+    return FX_OK;
+}
+
+// scratch that follows the largest block seen (fx_capi.cpp grow(): forgotten before it is freed, grows by half again at least)
+fx_status grow_bytes(unsigned char** ptr, size_t* cap, size_t need)
+{
+    if (need <= *cap) return FX_OK;
+    size_t want = *ptr && need < *cap + *cap / 2 ? *cap + *cap / 2 : need;
+    if (*ptr) {
+        unsigned char* old = *ptr;
+        *ptr = nullptr;
+        *cap = 0;
+        HIP_TRY(hipFree(old));
+    }
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, want);
+    if (e != hipSuccess && want != need) { (void) hipGetLastError(); want = need; e = hipMalloc(&q, want); }
+    if (e != hipSuccess) return fx_fail(e == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e));
+    *ptr = static_cast<unsigned char*>(q);
+    *cap = want;
+    return FX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+fx_status fx_set_channel_map(fx_context* c, const int* map)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    int top = c->C - 1;
+    if (map) {
+        top = 0;
+        for (int i = 0; i < c->C; i++) {
+            if (map[i] < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "map[%d] = %d: a source channel is >= 0", i, map[i]);
+            if (map[i] > top) top = map[i];
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    fx_interleave* s = nullptr;
+    fx_status st;
+    if ((st = interleave_state(c, &s)) != FX_OK) return st;
+    std::vector<int> next((size_t) c->C);
+    for (int i = 0; i < c->C; i++) next[(size_t) i] = map ? map[i] : i;
+    // blocks already pushed read the old map on the device: they finish before it is replaced.  The host copy, and the bound that
+    // fx_push_interleaved checks, change only once the device copy has.
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(s->d_map, next.data(), sizeof(int) * (size_t) c->C, hipMemcpyHostToDevice));
+    s->map.swap(next);
+    s->max_source = top;
+    return FX_OK;
+}
+
+fx_status fx_push_interleaved(fx_context* c, const void* samples, int num_samples, int num_source_channels, int sample_format,
+                              int mem_kind, float* out_raw, float* out_smoothed, int* frames_out)
+{
+    if (frames_out) *frames_out = 0;
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    c->num_launches = 0;
+    if (num_samples < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative sample count");
+    if (num_source_channels < 1) return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d source channels: a frame holds at least one", num_source_channels);
+    if (!known_format(sample_format)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown sample format %d", sample_format);
+    if (mem_kind != FX_MEM_HOST && mem_kind != FX_MEM_DEVICE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", mem_kind);
+    if (num_samples == 0) return FX_OK;
+    if (!samples) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null input buffer");
+    if (mem_kind == FX_MEM_DEVICE && reinterpret_cast<uintptr_t>(samples) % 4 != 0)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "device input must be 4-byte aligned");
+    // fx_push_block's own refusals, before the de-interleave is launched: a refused call changes nothing
+    { const fx_status rs = fx_block_refusal(c, num_samples, sample_format); if (rs != FX_OK) return rs; }
+    const int top = c->interleave ? c->interleave->max_source : c->C - 1;
+    if (top >= num_source_channels)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "the channel map reads source channel %d; the block has %d", top, num_source_channels);
+
+    HIP_TRY(hipSetDevice(c->device));
+    { const fx_status es = fx_check_device_error(c); if (es != FX_OK) return es; }
+    fx_interleave* s = nullptr;
+    fx_status st;
+    if ((st = interleave_state(c, &s)) != FX_OK) return st;
+    const int esz = sample_size(sample_format);
+    const size_t in_bytes = (size_t) num_samples * (size_t) num_source_channels * (size_t) esz;
+    const size_t planar_bytes = (size_t) c->C * (size_t) num_samples * (size_t) esz;
+    const unsigned char* d_in = static_cast<const unsigned char*>(samples);
+    if (mem_kind == FX_MEM_HOST) {
+        if ((st = grow_bytes(&s->d_src, &s->src_cap, in_bytes)) != FX_OK) return st;
+        HIP_TRY(hipMemcpyAsync(s->d_src, samples, in_bytes, hipMemcpyHostToDevice, c->stream));
+        d_in = s->d_src;
+    }
+    if ((st = grow_bytes(&s->d_planar, &s->planar_cap, planar_bytes)) != FX_OK) return st;
+    fxk::DeinterleaveParams p;
+    p.in = d_in;
+    p.map = s->d_map;
+    p.out = s->d_planar;
+    p.n = num_samples;
+    p.K = num_source_channels;
+    p.C = c->C;
+    if (fx_launch_record* r = note_launch(c, FX_LAUNCH_DEINTERLEAVE, 0)) r->T = num_samples;
+    HIP_TRY(fxk::launch_deinterleave_kernel(p, esz, c->stream));
+    int frames = 0;
+    st = fx_push_block(c, s->d_planar, num_samples, sample_format, FX_MEM_DEVICE, mem_kind, out_raw, out_smoothed, &frames, true);
+    if (st != FX_OK) return st;
+    // the caller may reuse a host block on return (a call that analysed frames into host memory has synchronised already)
+    if (mem_kind == FX_MEM_HOST && frames == 0) HIP_TRY(hipStreamSynchronize(c->stream));
+    if (frames_out) *frames_out = frames;
+    return FX_OK;
+}
+
+} // extern "C"

@@ -270,9 +270,9 @@ extern "C" fx_status fx_set_tuning_internal(fx_context* ctx, unsigned test_hooks
 // Launch record, NOT part of the public ABI (tests only): the launches the context's last call made -- fx_push_hops, fx_process_frames,
 // fx_push_samples, fx_stream_submit(_samples), fx_get_osc_datagrams each start a new one; a captured ring step replays the record it made
 // at capture.  Fields that do not apply to a launcher are 0.  A taps launch (fx_taps.hip) records T = the channels it captures and
-// block_mode = 1 when it reads [pending | block].
+// block_mode = 1 when it reads [pending | block].  A de-interleave launch (fx_interleave.hip) records T = the block's samples per channel.
 enum { FX_LAUNCH_FRAME = 1, FX_LAUNCH_FRAME_TAIL, FX_LAUNCH_HOP, FX_LAUNCH_HOP_PAIR, FX_LAUNCH_PAIR, FX_LAUNCH_EPILOGUE, FX_LAUNCH_REBLOCK,
-       FX_LAUNCH_OSC, FX_LAUNCH_TAPS };
+       FX_LAUNCH_OSC, FX_LAUNCH_TAPS, FX_LAUNCH_DEINTERLEAVE };
 struct fx_launch_record {
     int kind;               // FX_LAUNCH_*
     int window, analysers;  // window size, analysers mask (bit 0 spectral, bit 1 harmonic)

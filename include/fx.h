@@ -151,6 +151,25 @@ fx_status fx_push_hops(fx_context* ctx, const void* hops, int num_hops, int samp
  * fx_process_frames and fx_stream_submit refuse (whole hops would overtake them); fx_reset_state drops them. */
 fx_status fx_push_samples(fx_context* ctx, const void* samples, int num_samples, int sample_format, int mem_kind,
                           float* out_raw, float* out_smoothed, int* frames_out);
+/* ---- interleaved input through a per-track channel map ----
+ * The reference builds one track per active input of the audio device, and each track's AudioDataCollector collects one
+ * device channel, channelData[channelToCollect] (MainComponent.cpp:140-170, AudioDataCollector.h:21-23,36-70).
+ * AudioDataCollector::setChannelToCollect (AudioDataCollector.h:123) for every track at once: track c collects source channel
+ * map[c] of the interleaved blocks given to fx_push_interleaved.  map == NULL restores the identity (track c <- source c).
+ * 0 <= map[c]; duplicates allowed; a source need not be used.  Takes effect for blocks pushed after it; pending samples and every
+ * history are kept (the reference's ring is not cleared).  A setting: fx_reset_state keeps it.  Synchronises the context's stream
+ * (blocks already pushed read the old map); the caller may free or reuse `map` on return. */
+fx_status fx_set_channel_map(fx_context* ctx, const int* map /*[num_channels] or NULL*/);
+/* fx_push_samples for an INTERLEAVED block: `samples` holds num_samples frames of num_source_channels samples each
+ * ([num_samples][num_source_channels], packed 24-bit: 3 bytes per sample).  Every result, the pending samples and the launch
+ * sequence after the de-interleave are those of fx_push_samples on the planar block [c][i] = samples[i][map[c]], bit for bit.
+ * The rules of fx_push_samples hold: any num_samples >= 0 (0 is a no-op), device input 4-byte aligned, the format may change only
+ * while nothing is pending, mem_kind covers the input and the outputs, and a failure after samples have moved on leaves the
+ * stream as fx_push_samples describes.  FX_ERR_INVALID_ARGUMENT if some map[c] >= num_source_channels (nothing is changed then).
+ * The caller may reuse a host block on return.  The block passes through one de-interleave kernel into a planar staging buffer
+ * on the device: with host input only the interleaved block crosses to the device. */
+fx_status fx_push_interleaved(fx_context* ctx, const void* samples, int num_samples, int num_source_channels,
+                              int sample_format, int mem_kind, float* out_raw, float* out_smoothed, int* frames_out);
 /* samples per channel held back by fx_push_samples / fx_stream_submit_samples, 0 <= n < window_size/2 */
 int fx_pending_samples(fx_context* ctx);
 /* AudioDataCollector::clearBuffer (AudioDataCollector.h:122; the transport buttons, AnalyserTrackController.h:135-137,167-171):

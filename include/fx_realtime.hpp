@@ -109,9 +109,10 @@ public:
     // ref RealTimeAnalyser.h:100 (AudioDataCollector&, AudioFeatures&, int windowSize, double sampleRate = 48000.0)
     RealTimeBatchAnalyser (int numChannels, int windowSize = 2048, double sampleRate = 48000.0, int deviceId = 0,
                            unsigned flags = FX_ORDER_SPECTRAL_THEN_HARMONIC)
-        : channels (numChannels), window (windowSize)
+        : channels (numChannels), window (windowSize), channelMap ((std::size_t) (numChannels > 0 ? numChannels : 0))
     {
         check (fx_create (&ctx, deviceId, numChannels, windowSize, sampleRate, flags));
+        for (int c = 0; c < channels; ++c) channelMap[(std::size_t) c] = c;
     }
     ~RealTimeBatchAnalyser() { fx_destroy (ctx); }
     RealTimeBatchAnalyser (const RealTimeBatchAnalyser&) = delete;
@@ -123,6 +124,23 @@ public:
     void setOnsetDetectionType (eOnsetDetectionType t)         { check (fx_set_onset_type (ctx, (int) t)); }      // ref :258
     void setGain (float g)                                     { check (fx_set_gain (ctx, g)); }                  // AudioDataCollector.h:124
     void reset()                                               { check (fx_reset_state (ctx)); }
+    // AudioDataCollector::setChannelToCollect (AudioDataCollector.h:123) for every track at once (fx_set_channel_map): track c
+    // collects source channel map[c]; an empty map restores the identity.  A setting: reset() keeps it.  The analyser keeps the map it
+    // gave the context, and every AudioDataCollector on it reads that copy: change the map here or through a collector, not with
+    // fx_set_channel_map on handle().
+    void setChannelMap (const std::vector<int>& map)
+    {
+        if (! map.empty() && (int) map.size() != channels) throw Error (FX_ERR_INVALID_ARGUMENT, "a channel map has one entry per track");
+        check (fx_set_channel_map (ctx, map.empty() ? nullptr : map.data()));
+        highestSource = map.empty() ? channels - 1 : 0;
+        for (int c = 0; c < channels; ++c)
+        {
+            channelMap[(std::size_t) c] = map.empty() ? c : map[(std::size_t) c];
+            if (channelMap[(std::size_t) c] > highestSource) highestSource = channelMap[(std::size_t) c];
+        }
+    }
+    const std::vector<int>& getChannelMap() const { return channelMap; }
+    int getHighestSourceChannel() const           { return highestSource; }      // the highest source channel the map reads
 
     // The analysers' display buffers (fx_request_taps / fx_get_taps): what RealTimeAudioDataOverlapper, both FFTAnalysers and the
     // PitchAnalyser hand out after their enable...NeedsUpdating flags (RealTimeAudioAnalysis.h:221-232,268-283, PitchAnalyser.h:30-72).
@@ -205,6 +223,8 @@ public:
 private:
     fx_context* ctx = nullptr;
     int channels, window;
+    std::vector<int> channelMap;             // [track]: what fx_set_channel_map was last given (the identity by default)
+    int highestSource = channels - 1;
     std::vector<float> latest;
 };
 
@@ -219,16 +239,47 @@ public:
     explicit AudioDataCollector (RealTimeBatchAnalyser& analyserToFeed)
         : analyser (analyserToFeed), channels (analyserToFeed.getNumChannels()), hop (analyserToFeed.getWindowSize() / 2) {}
 
-    // ref :36-70.  inputChannelData[c] points at `numberOfSamples` floats of channel c (JUCE's layout); returns the number of analysis
+    // ref :36-70.  inputChannelData[k] points at `numberOfSamples` floats of device channel k (JUCE's layout); track c collects
+    // inputChannelData[channel c collects] (setChannelToCollect; by default track c <- channel c).  Returns the number of analysis
     // frames per channel this block completed (0 is normal for blocks shorter than a hop).  Their values: raw() / smoothed(),
     // [channel][frame][12], and the callback set below is called once per block that completed at least one frame.
     int audioDeviceIOCallback (const float* const* inputChannelData, int numInputChannels, int numberOfSamples)
     {
-        if (numInputChannels < channels) throw Error (FX_ERR_INVALID_ARGUMENT, "fewer input channels than the analyser has");   // jassert, :44-47
+        const int highest = analyser.getHighestSourceChannel();
+        if (numInputChannels <= highest)                                                                          // jassert, :44-47
+            throw Error (FX_ERR_INVALID_ARGUMENT, ((highest == channels - 1 ? std::string ("fewer input channels than the analyser has")
+                                                                            : std::string ("fewer input channels than the channel map reads"))
+                                                  + " (it collects input channel " + std::to_string (highest) + ", the device gives "
+                                                  + std::to_string (numInputChannels) + ")").c_str());
+        const std::vector<int>& map = analyser.getChannelMap();
         block.resize ((std::size_t) channels * (std::size_t) numberOfSamples);
         for (int c = 0; c < channels; ++c)
-            if (numberOfSamples > 0) std::memcpy (block.data() + (std::size_t) c * (std::size_t) numberOfSamples, inputChannelData[c], sizeof (float) * (std::size_t) numberOfSamples);
+            if (numberOfSamples > 0) std::memcpy (block.data() + (std::size_t) c * (std::size_t) numberOfSamples, inputChannelData[map[(std::size_t) c]], sizeof (float) * (std::size_t) numberOfSamples);
         return pushBlock (block.data(), numberOfSamples, FX_SAMPLE_F32);
+    }
+    // ref :123: track `track` collects device channel `source` from the next block on (pending samples are kept).  The map is the
+    // context's (fx_set_channel_map): pushInterleaved reads it on the GPU, audioDeviceIOCallback on the host.
+    void setChannelToCollect (int track, int source)
+    {
+        if (track < 0 || track >= channels || source < 0) throw Error (FX_ERR_INVALID_ARGUMENT, "no such track, or a negative channel");
+        std::vector<int> map = analyser.getChannelMap();
+        map[(std::size_t) track] = source;
+        analyser.setChannelMap (map);
+    }
+    int getChannelToCollect (int track) const { return analyser.getChannelMap().at ((std::size_t) track); }
+    // an interleaved block as a device or file delivers it: `frames` holds numberOfSamples frames of numSourceChannels samples in
+    // sampleFormat ([frame][source]; 3 bytes per sample for FX_SAMPLE_S24), de-interleaved on the GPU (fx_push_interleaved)
+    int pushInterleaved (const void* frames, int numSourceChannels, int numberOfSamples, int sampleFormat = FX_SAMPLE_F32)
+    {
+        const std::size_t most = (std::size_t) ((fx_pending_samples (analyser.handle()) + numberOfSamples) / hop);
+        rawValues.resize ((std::size_t) channels * most * FX_NUM_FEATURES);
+        smoothedValues.resize (rawValues.size());
+        int got = 0;
+        check (fx_push_interleaved (analyser.handle(), frames, numberOfSamples, numSourceChannels, sampleFormat, FX_MEM_HOST,
+                                    most ? rawValues.data() : nullptr, most ? smoothedValues.data() : nullptr, &got));
+        lastFrames = got;
+        if (got > 0 && framesAnalysed) framesAnalysed (got);
+        return got;
     }
     // the same for a block that is already [channel][numberOfSamples] in one piece, in any sample format of fx.h
     int pushBlock (const void* samples, int numberOfSamples, int sampleFormat = FX_SAMPLE_F32)
