@@ -97,6 +97,38 @@ class BatchAnalyser:
     def reset_state(self):
         capi.check(self._lib.fx_reset_state(self._h))
 
+    # ---- the same settings per track (include/fx.h, fx_set_channel_gains / fx_set_channel_onset; AnalyserTrackController.h:126-134) ----
+    def _per_track(self, values, dtype, what):
+        if values is None:
+            return None, None
+        a = np.ascontiguousarray(np.asarray(values, dtype=dtype).ravel())
+        if a.size != self.num_channels:
+            raise ValueError("per-track %s have one entry per track (%d), not %d" % (what, self.num_channels, a.size))
+        return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float if dtype == np.float32 else ctypes.c_int))
+
+    def set_channel_gains(self, gains):
+        """AudioDataCollector::setGain per track: track c's hops are scaled by gains[c] from the next call on."""
+        a, ptr = self._per_track(gains, np.float32, "gains")
+        capi.check(self._lib.fx_set_channel_gains(self._h, ptr))
+
+    def set_channel_onset(self, sensitivity=None, window=None, type=None):
+        """Onset sensitivity / window length / detection type per track; None leaves a setting alone.  A window entry < 0 leaves that
+        track's window and onset histories alone, one in [1, 32] sets it and empties that track's histories."""
+        s, sp = self._per_track(sensitivity, np.float32, "sensitivities")
+        w, wp = self._per_track(window, np.int32, "onset windows")
+        t, tp = self._per_track(type, np.int32, "onset types")
+        capi.check(self._lib.fx_set_channel_onset(self._h, sp, wp, tp))
+
+    def channel_settings(self):
+        """What each track runs with now: dict of gain, sensitivity (float32 [C]), window, type (int32 [C])."""
+        C = self.num_channels
+        out = {"gain": np.empty(C, np.float32), "sensitivity": np.empty(C, np.float32), "window": np.empty(C, np.int32), "type": np.empty(C, np.int32)}
+        capi.check(self._lib.fx_get_channel_settings(self._h, out["gain"].ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                     out["sensitivity"].ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                     out["window"].ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                     out["type"].ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return out
+
     # ---- launch-shape knobs (within a kernel family they never change a result bit; waves_per_frame selects the family) ----
     def get_tuning(self):
         t = capi.Tuning()

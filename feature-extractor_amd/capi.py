@@ -32,7 +32,8 @@ EXPORTS = ["fx_create", "fx_destroy", "fx_reset_state", "fx_set_sample_rate", "f
            "fx_offline_create", "fx_offline_destroy", "fx_offline_reset", "fx_offline_sync", "fx_offline_get_previous_f0", "fx_offline_zero_crosses",
            "fx_offline_log_attack_time", "fx_offline_fft_lbp", "fx_offline_harmonic_characteristics", "fx_offline_spectral_characteristics",
            "fx_offline_get_previous_bins", "fx_offline_spectral_slope", "fx_offline_auto_correlation",
-           "fx_request_taps", "fx_get_taps", "fx_set_channel_map", "fx_push_interleaved"]
+           "fx_request_taps", "fx_get_taps", "fx_set_channel_map", "fx_push_interleaved",
+           "fx_set_channel_gains", "fx_set_channel_onset", "fx_get_channel_settings"]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
 MAX_UNITS = 24
@@ -154,6 +155,9 @@ def load_library(build_if_missing=True):
     L.fx_comm_stats.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(d), ctypes.POINTER(d)]
     L.fx_request_taps.argtypes = [vp, ctypes.POINTER(i), i]
     L.fx_set_channel_map.argtypes = [vp, ctypes.POINTER(i)]
+    L.fx_set_channel_gains.argtypes = [vp, fp]
+    L.fx_set_channel_onset.argtypes = [vp, fp, ctypes.POINTER(i), ctypes.POINTER(i)]
+    L.fx_get_channel_settings.argtypes = [vp, fp, fp, ctypes.POINTER(i), ctypes.POINTER(i)]
     L.fx_push_interleaved.argtypes = [vp, vp, i, i, i, i, vp, vp, ctypes.POINTER(i)]
     L.fx_get_taps.argtypes = [vp, i, fp, fp, fp, fp, fp, fp, ctypes.POINTER(ctypes.c_longlong)]
     L.fx_plan_units.argtypes = [i, u, i, i, ctypes.POINTER(Tuning), ctypes.POINTER(i), i]

@@ -51,8 +51,60 @@ size_t sample_size(int f) { return f == FX_SAMPLE_F32 ? 4 : (f == FX_SAMPLE_S24 
 
 namespace {
 
+// ---- per-track settings (fx_set_channel_gains / fx_set_channel_onset; fx_context::chan) ----
+// what every track runs with now: the table's rows, or the context-wide values while no table exists
+void channel_rows(const fx_context* c, std::vector<fxk::ChannelSettings>* rows, std::vector<float>* sensitivity)
+{
+    if (!c->chan.empty()) { *rows = c->chan; *sensitivity = c->chan_sensitivity; return; }
+    rows->assign((size_t) c->C, fxk::ChannelSettings{c->gain, c->onset_multiplier, c->onset_window, c->onset_type, c->onset_reset_frame});
+    sensitivity->assign((size_t) c->C, c->onset_sensitivity);
+}
+
+// Puts `rows` in force for the calls that follow, in stream order: a copy on the context's stream from pinned rows that stay until the
+// next upload has waited for it.  The first upload allocates the table.  A failure leaves the old settings in force (and no table
+// where there was none).
+fx_status upload_channel_rows(fx_context* c, const std::vector<fxk::ChannelSettings>& rows, const std::vector<float>& sensitivity)
+{
+    const size_t bytes = rows.size() * sizeof(fxk::ChannelSettings);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));               // (the upload before this one has read the staging rows)
+    if (!c->h_chan_stage) {
+        void* q = nullptr;
+        HIP_TRY(hipHostMalloc(&q, bytes, hipHostMallocDefault));
+        c->h_chan_stage = static_cast<fxk::ChannelSettings*>(q);
+    }
+    fxk::ChannelSettings* table = c->d_chan;
+    if (!table) {
+        void* q = nullptr;
+        HIP_TRY(hipMalloc(&q, bytes));
+        table = static_cast<fxk::ChannelSettings*>(q);
+    }
+    memcpy(c->h_chan_stage, rows.data(), bytes);
+    const hipError_t e = hipMemcpyAsync(table, c->h_chan_stage, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) {
+        if (!c->d_chan) (void) hipFree(table);
+        return fx_fail(FX_ERR_HIP, "uploading the per-track settings failed: %s", hipGetErrorString(e));
+    }
+    c->d_chan = table;
+    c->chan = rows;
+    c->chan_sensitivity = sensitivity;
+    return FX_OK;
+}
+
+// A context-wide setter on a context that has a table: `set` changes one row, every row gets it.  No table: nothing to do.
+template <typename F> fx_status set_every_channel(fx_context* c, F set)
+{
+    if (c->chan.empty()) return FX_OK;
+    std::vector<fxk::ChannelSettings> rows = c->chan;
+    std::vector<float> sensitivity = c->chan_sensitivity;
+    for (size_t i = 0; i < rows.size(); i++) set(rows[i], sensitivity[i]);
+    return upload_channel_rows(c, rows, sensitivity);
+}
+
 fx_status zero_state(fx_context* c)
 {
+    // (first: the one step that can leave the per-track rows as they were.  Every track's onset histories start at frame 0 again.)
+    { const fx_status st = set_every_channel(c, [](fxk::ChannelSettings& r, float&) { r.onset_reset_frame = 0; }); if (st != FX_OK) return st; }
     const size_t half = (size_t) c->C * (c->N / 2);
     HIP_TRY(hipMemsetAsync(c->d_prev, 0, half * sizeof(float), c->stream));
     for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(c->d_tail[i], 0, half * sizeof(float), c->stream));
@@ -334,6 +386,7 @@ fx_status plan_call(const fx_context* c, const void* d_in, int T, int sample_for
     fp.T = part_T;
     fp.C = c->C;
     fp.gain = c->gain;
+    fp.chan = c->d_chan;
     fp.prev_re = c->d_prev;
     fp.tw = c->d_tw;
     fp.tw_image = c->d_tw + 2 * (size_t) c->N;
@@ -425,6 +478,7 @@ fx_status plan_call(const fx_context* c, const void* d_in, int T, int sample_for
     ep.onset_window = c->onset_window;
     ep.onset_type = c->onset_type;
     ep.onset_multiplier = c->onset_multiplier;
+    ep.chan = c->d_chan;
     ep.order_mode = (int) (c->flags & FX_ORDER_MASK);
     ep.analysers = analysers;
     ep.dyn = dyn;
@@ -754,9 +808,10 @@ fx_status fx_destroy(fx_context* c)
     if (c->taps_release) c->taps_release(c);
     if (c->interleave_release) c->interleave_release(c);
     void* bufs[] = {c->d_tw, c->d_prev, c->d_tail[0], c->d_tail[1], c->d_hist, c->d_latest,
-                    c->d_raw, c->d_part, c->d_in, c->d_out_raw, c->d_queue, c->d_carry[0], c->d_carry[1], c->d_hops, c->d_osc};
+                    c->d_raw, c->d_part, c->d_in, c->d_out_raw, c->d_queue, c->d_carry[0], c->d_carry[1], c->d_hops, c->d_osc, c->d_chan};
     for (void* b : bufs) if (b) (void) hipFree(b);
     if (c->h_err) (void) hipHostFree(c->h_err);
+    if (c->h_chan_stage) (void) hipHostFree(c->h_chan_stage);
     for (int i = 0; i < 3; i++) if (c->ev[i]) (void) hipEventDestroy(c->ev[i]);
     for (hipEvent_t e : c->prof_events) (void) hipEventDestroy(e);
     if (c->stream) (void) hipStreamDestroy(c->stream);
@@ -786,7 +841,10 @@ fx_status fx_set_onset_sensitivity(fx_context* c, float s)
 {
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
     if (!(s >= 0.0f)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "sensitivity must be >= 0");   // jassert, RealTimeAnalyser.h:246
+    const fx_status st = set_every_channel(c, [s](fxk::ChannelSettings& r, float& sens) { r.onset_multiplier = 1.0f + s; sens = s; });
+    if (st != FX_OK) return st;
     c->onset_multiplier = 1.0f + s;
+    c->onset_sensitivity = s;
     return FX_OK;
 }
 
@@ -795,6 +853,9 @@ fx_status fx_set_onset_window(fx_context* c, int length)
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
     if (length < 1 || length > fxk::MAX_ONSET_WINDOW)
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "onset window must be in [1,%d]", fxk::MAX_ONSET_WINDOW);
+    const long long now = c->frames_seen;
+    const fx_status st = set_every_channel(c, [length, now](fxk::ChannelSettings& r, float&) { r.onset_window = length; r.onset_reset_frame = now; });
+    if (st != FX_OK) return st;
     c->onset_window = length;
     c->onset_reset_frame = c->frames_seen;      // both histories emptied, RealTimeAudioAnalysis.h:73-81
     return FX_OK;
@@ -804,6 +865,8 @@ fx_status fx_set_onset_type(fx_context* c, int type)
 {
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
     if (type < FX_ONSET_SPECTRAL || type > FX_ONSET_COMBINATION) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown onset type %d", type);
+    const fx_status st = set_every_channel(c, [type](fxk::ChannelSettings& r, float&) { r.onset_type = type; });
+    if (st != FX_OK) return st;
     c->onset_type = type;
     return FX_OK;
 }
@@ -811,7 +874,59 @@ fx_status fx_set_onset_type(fx_context* c, int type)
 fx_status fx_set_gain(fx_context* c, float gain)
 {
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    const fx_status st = set_every_channel(c, [gain](fxk::ChannelSettings& r, float&) { r.gain = gain; });
+    if (st != FX_OK) return st;
     c->gain = gain;
+    return FX_OK;
+}
+
+fx_status fx_set_channel_gains(fx_context* c, const float* gain)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    if (!gain) return FX_OK;
+    std::vector<fxk::ChannelSettings> rows;
+    std::vector<float> sensitivity;
+    channel_rows(c, &rows, &sensitivity);
+    for (int i = 0; i < c->C; i++) rows[(size_t) i].gain = gain[i];
+    return upload_channel_rows(c, rows, sensitivity);
+}
+
+fx_status fx_set_channel_onset(fx_context* c, const float* sensitivity, const int* window, const int* type)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    if (!sensitivity && !window && !type) return FX_OK;
+    // every entry is checked before any is taken (the context-wide setters' own conditions)
+    for (int i = 0; i < c->C; i++) {
+        if (sensitivity && !(sensitivity[i] >= 0.0f)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "track %d: sensitivity must be >= 0", i);
+        if (window && (window[i] == 0 || window[i] > fxk::MAX_ONSET_WINDOW))
+            return fx_fail(FX_ERR_INVALID_ARGUMENT, "track %d: onset window must be in [1,%d] (or < 0: unchanged)", i, fxk::MAX_ONSET_WINDOW);
+        if (type && (type[i] < FX_ONSET_SPECTRAL || type[i] > FX_ONSET_COMBINATION))
+            return fx_fail(FX_ERR_INVALID_ARGUMENT, "track %d: unknown onset type %d", i, type[i]);
+    }
+    std::vector<fxk::ChannelSettings> rows;
+    std::vector<float> sens;
+    channel_rows(c, &rows, &sens);
+    for (int i = 0; i < c->C; i++) {
+        fxk::ChannelSettings& r = rows[(size_t) i];
+        if (sensitivity) { r.onset_multiplier = 1.0f + sensitivity[i]; sens[(size_t) i] = sensitivity[i]; }
+        if (window && window[i] > 0) { r.onset_window = window[i]; r.onset_reset_frame = c->frames_seen; }   // setHistoryLength: both histories emptied
+        if (type) r.onset_type = type[i];
+    }
+    return upload_channel_rows(c, rows, sens);
+}
+
+fx_status fx_get_channel_settings(fx_context* c, float* gain, float* sensitivity, int* window, int* type)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    std::vector<fxk::ChannelSettings> rows;
+    std::vector<float> sens;
+    channel_rows(c, &rows, &sens);
+    for (int i = 0; i < c->C; i++) {
+        if (gain) gain[i] = rows[(size_t) i].gain;
+        if (sensitivity) sensitivity[i] = sens[(size_t) i];
+        if (window) window[i] = rows[(size_t) i].onset_window;
+        if (type) type[i] = rows[(size_t) i].onset_type;
+    }
     return FX_OK;
 }
 
@@ -1385,6 +1500,12 @@ fx_status fx_stream_submit(fx_stream* s)
     if (s->use_graph) {
         const int par = c->cur;
         fill_dyn(c, sl.h_dyn);
+        // a graph keeps the addresses it was captured with: a step captured before the per-track table existed is captured once more
+        if (sl.exec[par] && sl.captured[par].launch[0].fp.chan != c->d_chan) {
+            const hipGraphExec_t old = sl.exec[par];
+            sl.exec[par] = nullptr;
+            HIP_TRY(hipGraphExecDestroy(old));
+        }
         if (!sl.exec[par]) {
             // capture the step once for this slot and parity: everything below is recorded, not executed
             // A few KB per step: the kernels read the hop and the per-call scalars straight from the pinned host slot and

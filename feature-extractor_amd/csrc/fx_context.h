@@ -61,8 +61,17 @@ struct fx_context {
     int      onset_window = 5;
     int      onset_type = FX_ONSET_AMPLITUDE;
     float    onset_multiplier = 1.7f;
+    float    onset_sensitivity = 0.7f;      // what fx_get_channel_settings reports (onset_multiplier is the float sum 1 + sensitivity)
     long long frames_seen = 0;
     long long onset_reset_frame = 0;
+    // Per-track settings (fx_set_channel_gains / fx_set_channel_onset): empty / null until the first per-track call, and until then the
+    // kernels read the four values above.  `chan` is what every track runs with, d_chan its device copy (FrameParams::chan: allocated
+    // once, never moved), h_chan_stage the pinned rows an upload in flight reads.  Once they exist the context-wide setters write every
+    // row too, so the values above and the table never disagree about a track nobody set on its own.
+    std::vector<fxk::ChannelSettings> chan;
+    std::vector<float>                chan_sensitivity;
+    fxk::ChannelSettings* d_chan = nullptr;
+    fxk::ChannelSettings* h_chan_stage = nullptr;
 
     hipStream_t stream = nullptr;
     hipEvent_t  ev[3] = {nullptr, nullptr, nullptr};

@@ -1144,6 +1144,7 @@ __device__ __forceinline__ void frame_kernel_body(const FrameParams& p_arg)
     }
     const int c = group * CH + chl;
     const bool live = c < p.C;                          // the last workgroup may hold fewer channels
+    if (live) p.gain = channel_gain(p, c);              // per-track settings: this wavefront's channel has a gain of its own (a scalar, like p.gain)
     const int t_begin = p.num_chunks > 1 ? p_arg.chunk_begin[chunk] : 0;
     const int t_end = p.num_chunks > 1 ? p_arg.chunk_begin[chunk + 1] : T;
 

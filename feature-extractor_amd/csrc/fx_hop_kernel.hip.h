@@ -51,6 +51,7 @@ fx_hop_kernel(const FrameParams p_arg, const EpilogueParams ep_arg, const HopSig
     const int wave = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));     // wave-uniform: scalar registers for all that follows from it
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x;
+    p.gain = channel_gain(p, c);                        // per-track settings (a scalar, like p.gain)
     f2*    cbuf = reinterpret_cast<f2*>(smem + HG::OFF_WAVES + (size_t) G::BUF_BYTES * wave);
     float* rbuf = reinterpret_cast<float*>(cbuf);
 
@@ -207,6 +208,7 @@ fx_hop_pair_kernel(const FrameParams p_arg, const EpilogueParams ep_arg, const H
     const int lane = threadIdx.x & 63;
     const int pair = wave >> 1, w = wave & 1;
     const int c = blockIdx.x;
+    p.gain = channel_gain(p, c);                        // per-track settings (a scalar, like p.gain)
     unsigned char* mine = smem + HG::OFF_PAIRS + HG::PAIR_BYTES * pair;
     f2* cbuf = reinterpret_cast<f2*>(mine);
     double* mbox = reinterpret_cast<double*>(mine + PG::BUF_BYTES);

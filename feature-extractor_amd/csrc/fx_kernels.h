@@ -54,6 +54,19 @@ struct DynParams {
     int       hist_base;            // frames_before mod HLEN (EpilogueParams::hist_base)
 };
 
+// Per-track settings (fx_set_channel_gains / fx_set_channel_onset): one row per channel in device memory, allocated by the first
+// per-track call.  Until then FrameParams::chan / EpilogueParams::chan are null and every kernel reads the context-wide values it
+// always read.  The table's address never changes once it exists (a captured step keeps it); its contents are replaced by copies on
+// the context's stream, so they are ordered with the analysis calls.
+struct ChannelSettings {
+    float     gain;
+    float     onset_multiplier;
+    int       onset_window;
+    int       onset_type;
+    long long onset_reset_frame;    // global index of the channel's first frame after its last onset-window reset
+};
+static_assert(sizeof(ChannelSettings) == 24, "rows are copied as they are");
+
 constexpr int FX_MAX_CHUNKS = FX_MAX_UNITS;
 
 struct FrameParams {
@@ -113,6 +126,7 @@ struct FrameParams {
     long long    blk_in_row_bytes;
     const unsigned char* blk_carry_in;
     unsigned char*       blk_carry_out;
+    const ChannelSettings* chan;    // per-track settings, or null: hop-mode input of channel c is scaled by chan[c].gain instead of `gain` (channel_gain)
 };
 
 struct EpilogueParams {
@@ -147,7 +161,29 @@ struct EpilogueParams {
     const DynParams* dyn;       // non-null in a captured step: overrides nyquist, frames_before, hist_base, onset_*
     unsigned*    clear_queue;   // a call cut in time (FrameParams::num_chunks > 1): its ticket counter and hand-over counts, which the step's
     int          clear_count;   // LAST kernel zeroes for the next call (a memset per call was two fill kernels and their gaps); else null
+    const ChannelSettings* chan;    // per-track settings, or null: channel c's detector runs with chan[c] instead of onset_* above (onset_settings)
 };
+
+#if defined(__HIPCC__)
+// The gain of channel c's hops.  Every caller's c is wave-uniform (a wavefront loads samples of one channel), so the table's value is
+// read as a scalar: a load through the constant address space (the table does not change while a kernel runs: its uploads are ordered
+// with the launches on the context's stream) at a uniform address is an s_load_dword into an SGPR, like the kernel argument it stands
+// in for -- no vector register, no vector-memory instruction.
+typedef const float __attribute__((address_space(4)))* UniformFloatPtr;
+__device__ __forceinline__ float channel_gain(const FrameParams& p, int c)
+{
+    if (!p.chan) return p.gain;
+    return *(UniformFloatPtr) &p.chan[__builtin_amdgcn_readfirstlane(c)].gain;
+}
+// What channel c's onset detector runs with (not uniform: the tails hold several channels in a wavefront).
+struct OnsetSettings { long long reset_frame; int window, type; float multiplier; };
+__device__ __forceinline__ OnsetSettings onset_settings(const EpilogueParams& p, int c)
+{
+    if (!p.chan) return {p.onset_reset_frame, p.onset_window, p.onset_type, p.onset_multiplier};
+    const ChannelSettings s = p.chan[c];
+    return {s.onset_reset_frame, s.onset_window, s.onset_type, s.onset_multiplier};
+}
+#endif
 
 // Completion signal of a one-hop call (fx_hop_kernel): workgroups count themselves in `arrivals` (device memory, zero
 // between calls); the last one resets it and stores `seq` to `host_flag` (pinned host memory, system scope), after the

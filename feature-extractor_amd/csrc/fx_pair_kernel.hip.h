@@ -900,6 +900,7 @@ fx_pair_kernel(const FrameParams p_arg)
     }
     const int c = group * CH + chl;
     const bool live = c < p.C;
+    if (live) p.gain = channel_gain(p, c);              // per-track settings (a scalar, like p.gain)
     const int t_begin = p.num_chunks > 1 ? p_arg.chunk_begin[chunk] : 0;
     const int t_end = p.num_chunks > 1 ? p_arg.chunk_begin[chunk + 1] : T;
 

@@ -232,19 +232,19 @@ __device__ __forceinline__ float rms_value(const RawView& v, int tau, int order_
 // (ref RealTimeAnalyser.h:236-242): flux of that frame, and the RMS mean at that moment.
 // `amp` (optional): amp[f - amp_first] = rms_value(v, f, order_mode, pushes at detection) for the frames around t,
 // evaluated once per frame by the caller's workgroup instead of once per (frame, candidate) here.
-__device__ __forceinline__ bool detect_onset(const EpilogueParams& p, const RawView& v, int t, int order_mode, bool spec,
+__device__ __forceinline__ bool detect_onset(const EpilogueParams& p, const OnsetSettings& o, const RawView& v, int t, int order_mode, bool spec,
                                              const float* amp = nullptr, int amp_first = 0)
 {
-    const int L = p.onset_window;
+    const int L = o.window;
     const int rms_pushes_at_detect = (order_mode == FX_ORDER_HARMONIC_THEN_SPECTRAL) ? 2 : 1;
     const long long g = p.frames_before + t;
-    long long recorded = g - p.onset_reset_frame + 1;
+    long long recorded = g - o.reset_frame + 1;
     if (recorded > L) recorded = L;
     bool onset = false;
     if (spec && recorded >= L && L > 0) {                           // :253-258 both histories full
         int cand = L - 1;                                           // :263-266
-        const bool use_amp = p.onset_type == FX_ONSET_AMPLITUDE || p.onset_type == FX_ONSET_COMBINATION;
-        const bool use_flux = p.onset_type == FX_ONSET_SPECTRAL || p.onset_type == FX_ONSET_COMBINATION;
+        const bool use_amp = o.type == FX_ONSET_AMPLITUDE || o.type == FX_ONSET_COMBINATION;
+        const bool use_flux = o.type == FX_ONSET_SPECTRAL || o.type == FX_ONSET_COMBINATION;
         if (use_flux) cand = L / 2;
         const float cand_amp = amp ? amp[t - L + 1 + cand - amp_first] : rms_value(v, t - L + 1 + cand, order_mode, rms_pushes_at_detect);
         const float cand_sf = (0.0f + v.get(t - L + 1 + cand, FX_FLUX)) / 1.0f;
@@ -264,12 +264,12 @@ __device__ __forceinline__ bool detect_onset(const EpilogueParams& p, const RawV
         }
         const float mean_flux = tot_flux / (float) recorded;
         const float mean_amp = tot_amp / (float) recorded;
-        const bool on_sf = cand_sf > mean_flux * p.onset_multiplier;    // :291-292
-        const bool on_amp = cand_amp > mean_amp * p.onset_multiplier;
+        const bool on_sf = cand_sf > mean_flux * o.multiplier;    // :291-292
+        const bool on_amp = cand_amp > mean_amp * o.multiplier;
         bool res = false;
-        if (p.onset_type == FX_ONSET_AMPLITUDE) res = on_amp;
-        else if (p.onset_type == FX_ONSET_SPECTRAL) res = on_sf;
-        else if (p.onset_type == FX_ONSET_COMBINATION) res = on_amp && on_sf;
+        if (o.type == FX_ONSET_AMPLITUDE) res = on_amp;
+        else if (o.type == FX_ONSET_SPECTRAL) res = on_sf;
+        else if (o.type == FX_ONSET_COMBINATION) res = on_amp && on_sf;
         onset = ok && res;
     }
     return onset;
@@ -313,7 +313,7 @@ __device__ __forceinline__ void epilogue_frame(const EpilogueParams& p, int c, i
     // RMS after every analyser of this hop has inserted (what the OSC timer samples)
     sm[FX_RMS] = rms_value(v, t, order_mode, 2);
 
-    const bool onset = detect_onset(p, v, t, order_mode, spec, amp, amp_first);
+    const bool onset = detect_onset(p, onset_settings(p, c), v, t, order_mode, spec, amp, amp_first);
     rw[FX_ONSET] = onset ? 1.0f : 0.0f;
     sm[FX_ONSET] = spec ? (0.0f + rw[FX_ONSET]) / 1.0f : never;      // history length 1
 
@@ -337,12 +337,12 @@ __device__ __forceinline__ void epilogue_frame(const EpilogueParams& p, int c, i
 // group's own [64] floats of LDS); the detector's serial loop then only reads them back.  Same values, same order of
 // additions; the result is uniform in the group.
 template <int GROUP = 64>
-__device__ __forceinline__ bool detect_onset_wave(const EpilogueParams& p, const RawView& v, int t, int order_mode, bool spec, int lane, float* scratch)
+__device__ __forceinline__ bool detect_onset_wave(const EpilogueParams& p, const OnsetSettings& o, const RawView& v, int t, int order_mode, bool spec, int lane, float* scratch)
 {
-    const int L = p.onset_window;
+    const int L = o.window;
     const int rms_pushes_at_detect = (order_mode == FX_ORDER_HARMONIC_THEN_SPECTRAL) ? 2 : 1;
     const long long g = p.frames_before + t;
-    long long recorded = g - p.onset_reset_frame + 1;
+    long long recorded = g - o.reset_frame + 1;
     if (recorded > L) recorded = L;
     if (!(spec && recorded >= L && L > 0)) return false;            // :253-258 both histories full
     for (int k = group_lane<GROUP>(lane); k < L; k += GROUP) {
@@ -352,8 +352,8 @@ __device__ __forceinline__ bool detect_onset_wave(const EpilogueParams& p, const
     }
     wave_fence();
     int cand = L - 1;                                               // :263-266
-    const bool use_amp = p.onset_type == FX_ONSET_AMPLITUDE || p.onset_type == FX_ONSET_COMBINATION;
-    const bool use_flux = p.onset_type == FX_ONSET_SPECTRAL || p.onset_type == FX_ONSET_COMBINATION;
+    const bool use_amp = o.type == FX_ONSET_AMPLITUDE || o.type == FX_ONSET_COMBINATION;
+    const bool use_flux = o.type == FX_ONSET_SPECTRAL || o.type == FX_ONSET_COMBINATION;
     if (use_flux) cand = L / 2;
     const float cand_amp = scratch[cand];
     const float cand_sf = scratch[32 + cand];
@@ -372,12 +372,12 @@ __device__ __forceinline__ bool detect_onset_wave(const EpilogueParams& p, const
     }
     const float mean_flux = tot_flux / (float) recorded;
     const float mean_amp = tot_amp / (float) recorded;
-    const bool on_sf = cand_sf > mean_flux * p.onset_multiplier;    // :291-292
-    const bool on_amp = cand_amp > mean_amp * p.onset_multiplier;
+    const bool on_sf = cand_sf > mean_flux * o.multiplier;    // :291-292
+    const bool on_amp = cand_amp > mean_amp * o.multiplier;
     bool res = false;
-    if (p.onset_type == FX_ONSET_AMPLITUDE) res = on_amp;
-    else if (p.onset_type == FX_ONSET_SPECTRAL) res = on_sf;
-    else if (p.onset_type == FX_ONSET_COMBINATION) res = on_amp && on_sf;
+    if (o.type == FX_ONSET_AMPLITUDE) res = on_amp;
+    else if (o.type == FX_ONSET_SPECTRAL) res = on_sf;
+    else if (o.type == FX_ONSET_COMBINATION) res = on_amp && on_sf;
     return ok && res;
 }
 
@@ -399,7 +399,7 @@ __device__ __forceinline__ void epilogue_hop(const EpilogueParams& p, int c, int
     const bool spec = p.analysers & 1, harm = p.analysers & 2;
     const int order_mode = (spec && harm) ? p.order_mode : FX_ORDER_ISOLATED;
     const float never = __int_as_float(0x7fc00000);
-    const bool onset = detect_onset_wave<GROUP>(p, v, t, order_mode, spec, lane, scratch);       // all lanes
+    const bool onset = detect_onset_wave<GROUP>(p, onset_settings(p, c), v, t, order_mode, spec, lane, scratch);       // all lanes
     const bool mine = s < FX_NUM_FEATURES;
     float rw = 0.0f, sm = 0.0f;
     if (mine) {
@@ -534,7 +534,7 @@ __device__ __forceinline__ void tail_one_hop(const EpilogueParams& p, int c_firs
     const float* ring = p.hist + (size_t) c * HLEN * FX_NUM_FEATURES;
     {
         // the LDS copy keeps the ring's row positions; rows nobody reads are not fetched (a row is 48 bytes: three 16-byte pieces)
-        const int need = hist_rows_read(p.onset_window);
+        const int need = hist_rows_read(onset_settings(p, c).window);
         for (int i = gl; i < need * 3; i += TAIL_GROUP) {
             const int r = hist_row_before(p.hist_base, -need + i / 3), q = i % 3;
             reinterpret_cast<uint4*>(s_hist)[r * 3 + q] = reinterpret_cast<const uint4*>(ring)[r * 3 + q];
@@ -609,7 +609,7 @@ fx_tail_fused_kernel(const EpilogueParams p_arg)
     const int c = live ? c_mine : p.C - 1;                // a group beyond the last channel keeps in step on the last one and stores nothing
     const float* ring = p.hist + (size_t) c * HLEN * FX_NUM_FEATURES;
     {
-        const int need = hist_rows_read(p.onset_window);            // what the call's FIRST frame reaches back; later frames less
+        const int need = hist_rows_read(onset_settings(p, c).window);            // what the call's FIRST frame reaches back; later frames less
         for (int i = gl; i < need * 3; i += TAIL_GROUP) {
             const int r = hist_row_before(p.hist_base, -need + i / 3), q = i % 3;
             reinterpret_cast<uint4*>(s_hist)[r * 3 + q] = reinterpret_cast<const uint4*>(ring)[r * 3 + q];

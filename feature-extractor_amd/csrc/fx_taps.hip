@@ -45,6 +45,7 @@ struct TapsParams {
     fx_tap_source src;
     const float*  tail;         // [C][N/2] fp32, already gained: FrameParams::tail_in of the call
     float         gain;
+    const ChannelSettings* chan;    // per-track settings or null (FrameParams::chan): the window shows the channel's own gain
     const float*  tw;           // [N][2] the reference's forward table (phase in double, rounded to float); the inverse uses its conjugate
     const float*  ramp;         // [N] the Bartlett window's gains, as applyGainRamp accumulates them
     float         lpf_a, lpf_b; // FrameParams::lpf_a / lpf_b
@@ -135,13 +136,15 @@ template <int FMT> __device__ __forceinline__ float first_sample(const fx_tap_so
 template <int N, int FMT> __device__ void load_window(const TapsParams& p, int c, float* win)
 {
     constexpr int H = N / 2;
+    // (c is the workgroup's channel: uniform, the gain a scalar as in the analysis kernels -- channel_gain)
+    const float gain = p.chan ? *(UniformFloatPtr) &p.chan[__builtin_amdgcn_readfirstlane(c)].gain : p.gain;
     for (int i = threadIdx.x; i < N; i += TAP_THREADS) {
         float x;
         if (!p.src.hop_mode) x = first_sample<FMT>(p.src, c, i);                      // fx_process_frames: as given, no gain
         else if (i < H) x = p.tail[(long long) c * H + i];
         else {
             x = first_sample<FMT>(p.src, c, i - H);
-            if (p.gain != 1.0f) x *= p.gain;                                           // ref AudioDataCollector.h:88, as the kernels apply it
+            if (gain != 1.0f) x *= gain;                                           // ref AudioDataCollector.h:88, as the kernels apply it
         }
         win[i] = x;
     }
@@ -326,6 +329,7 @@ fx_status taps_launch(fx_context* c, const fx_tap_source& src)
     p.src = src;
     p.tail = c->d_tail[c->cur];
     p.gain = c->gain;
+    p.chan = c->d_chan;
     p.tw = t->d_consts;
     p.ramp = t->d_consts + 2 * (size_t) n;
     p.lpf_a = c->lpf_a;

@@ -23,6 +23,28 @@ def my_shard(num_channels, rank, world_size):
     return shard_bounds(num_channels, world_size)[rank]
 
 
+def shard_slice(values, num_channels, rank, world_size):
+    """This rank's part of a GLOBAL per-track array (one entry per channel of the whole run: gains, onset sensitivities / windows /
+    types for BatchAnalyser.set_channel_gains / set_channel_onset, a channel map): the entries of the channels my_shard gives the
+    rank, in order.  None stays None (a setting left alone)."""
+    if values is None:
+        return None
+    a = np.asarray(values)
+    if a.ndim != 1 or a.shape[0] != num_channels:
+        raise ValueError("a global per-track array has one entry per channel (%d), not shape %s" % (num_channels, a.shape))
+    first, count = my_shard(num_channels, rank, world_size)
+    return a[first:first + count]
+
+
+def set_shard_channel_settings(analyser, num_channels, rank, world_size, gains=None, sensitivity=None, window=None, type=None):
+    """Per-track settings given for the whole run, applied to this rank's analyser (its channels are the rank's shard)."""
+    if gains is not None:
+        analyser.set_channel_gains(shard_slice(gains, num_channels, rank, world_size))
+    if sensitivity is not None or window is not None or type is not None:
+        analyser.set_channel_onset(shard_slice(sensitivity, num_channels, rank, world_size), shard_slice(window, num_channels, rank, world_size),
+                                   shard_slice(type, num_channels, rank, world_size))
+
+
 def gather_features(local, num_channels, dst=0, group=None, async_op=False, single_rank_collective=False):
     """Gather per-rank feature blocks [C_local][...][12] (torch tensors, CPU for gloo / CUDA for
     RCCL) to rank `dst`.  Returns (result, work): on dst `result` is the [num_channels][...][12]

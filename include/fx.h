@@ -113,6 +113,28 @@ fx_status fx_set_onset_type(fx_context* ctx, int type);
  * as AudioDataCollector::getAnalysisBuffer does at :88) */
 fx_status fx_set_gain(fx_context* ctx, float gain);
 
+/* ---- the same settings per track ----
+ * In the reference every track is an AnalyserTrackController with its own gain slider and its own onset controls
+ * (AnalyserTrackController.h:126-134).  These take whole-context arrays in host memory, one entry per track; NULL leaves that
+ * setting alone.  A context on which none of them was ever called runs exactly as before; a track given values here produces, bit
+ * for bit, what it produces in a context that has those values context-wide.  Like the context-wide setters they take effect for
+ * the hops analysed by the next call, in stream order (the gain where a hop is read: pending samples are kept un-gained, the stored
+ * window tail is already gained), fx_reset_state keeps them, and the caller may free or reuse the arrays on return.  The
+ * context-wide setters above keep their meaning "set it on every track": fx_set_gain(ctx, g) after these leaves every track with g.
+ * A bad entry fails the whole call with FX_ERR_INVALID_ARGUMENT (fx_last_error names the track) and changes nothing; a failed
+ * upload reports FX_ERR_HIP and leaves the old settings in force.  They synchronise the context's stream.
+ * Not per track: clearing the pending samples (tracks would hold different numbers of them -- ragged blocks), the sample rate, the
+ * window size and the analysers' order; those stay one per context. */
+/* AudioDataCollector::setGain per track (AnalyserTrackController.h:126-130).  gain [num_channels]; any float, as fx_set_gain. */
+fx_status fx_set_channel_gains(fx_context* ctx, const float* gain);
+/* setOnsetDetectionSensitivity / setOnsetWindowLength / setOnsetDetectionType per track (AnalyserTrackController.h:132-134).
+ * Each array is [num_channels] or NULL (unchanged).  sensitivity >= 0; type FX_ONSET_*.  window: an entry < 0 leaves that track's
+ * window AND its onset histories alone; an entry in [1, 32] is a setHistoryLength call on that track (histories emptied even when
+ * the length is the one it had, RealTimeAudioAnalysis.h:73-81); 0 and entries above 32 are refused. */
+fx_status fx_set_channel_onset(fx_context* ctx, const float* sensitivity, const int* window, const int* type);
+/* What each track runs with now ([num_channels] each; any pointer may be NULL): after a context-wide setter, its value on every track. */
+fx_status fx_get_channel_settings(fx_context* ctx, float* gain, float* sensitivity, int* window, int* type);
+
 /* Replaces RealTimeAudioDataOverlapper::getNextBuffer (RealTimeAudioAnalysis.h:
  * 205-228) + both run() loops (RealTimeAnalyser.h:141-177, :201-234) for
  * `num_hops` consecutive hops of window_size/2 samples per channel.

@@ -124,6 +124,48 @@ public:
     void setOnsetDetectionType (eOnsetDetectionType t)         { check (fx_set_onset_type (ctx, (int) t)); }      // ref :258
     void setGain (float g)                                     { check (fx_set_gain (ctx, g)); }                  // AudioDataCollector.h:124
     void reset()                                               { check (fx_reset_state (ctx)); }
+    // The same four per track, as each AnalyserTrackController has its own (AnalyserTrackController.h:126-134): fx_set_channel_gains /
+    // fx_set_channel_onset.  One track: the others keep what they have (and their onset histories).  The context-wide forms above
+    // still set every track.  A setting: reset() keeps it.
+    void setGain (int track, float g)
+    {
+        std::vector<float> v = perTrack().gain; v[at (track)] = g; setGains (v);
+    }
+    void setOnsetDetectionSensitivity (int track, float s)
+    {
+        std::vector<float> v = perTrack().sensitivity; v[at (track)] = s; setOnsetSettings (&v, nullptr, nullptr);
+    }
+    void setOnsetWindowLength (int track, int length)
+    {
+        std::vector<int> v ((std::size_t) channels, -1); v[at (track)] = length; setOnsetSettings (nullptr, &v, nullptr);
+    }
+    void setOnsetDetectionType (int track, eOnsetDetectionType t)
+    {
+        std::vector<int> v = perTrack().type; v[at (track)] = (int) t; setOnsetSettings (nullptr, nullptr, &v);
+    }
+    // array forms, one entry per track; a null vector leaves that setting alone, a window entry < 0 leaves that track's window and
+    // histories alone
+    void setGains (const std::vector<float>& gains)
+    {
+        if ((int) gains.size() != channels) throw Error (FX_ERR_INVALID_ARGUMENT, "per-track gains have one entry per track");
+        check (fx_set_channel_gains (ctx, gains.data()));
+    }
+    void setOnsetSettings (const std::vector<float>* sensitivity, const std::vector<int>* windowLength, const std::vector<int>* type)
+    {
+        if ((sensitivity && (int) sensitivity->size() != channels) || (windowLength && (int) windowLength->size() != channels)
+            || (type && (int) type->size() != channels))
+            throw Error (FX_ERR_INVALID_ARGUMENT, "per-track onset settings have one entry per track");
+        check (fx_set_channel_onset (ctx, sensitivity ? sensitivity->data() : nullptr, windowLength ? windowLength->data() : nullptr,
+                                     type ? type->data() : nullptr));
+    }
+    struct TrackSettings { std::vector<float> gain, sensitivity; std::vector<int> windowLength, type; };
+    TrackSettings perTrack() const                             // what each track runs with now (fx_get_channel_settings)
+    {
+        const std::size_t n = (std::size_t) channels;
+        TrackSettings t { std::vector<float> (n), std::vector<float> (n), std::vector<int> (n), std::vector<int> (n) };
+        check (fx_get_channel_settings (ctx, t.gain.data(), t.sensitivity.data(), t.windowLength.data(), t.type.data()));
+        return t;
+    }
     // AudioDataCollector::setChannelToCollect (AudioDataCollector.h:123) for every track at once (fx_set_channel_map): track c
     // collects source channel map[c]; an empty map restores the identity.  A setting: reset() keeps it.  The analyser keeps the map it
     // gave the context, and every AudioDataCollector on it reads that copy: change the map here or through a collector, not with
@@ -221,6 +263,11 @@ public:
     fx_context* handle()       { return ctx; }
 
 private:
+    std::size_t at (int track) const
+    {
+        if (track < 0 || track >= channels) throw Error (FX_ERR_INVALID_ARGUMENT, "no such track");
+        return (std::size_t) track;
+    }
     fx_context* ctx = nullptr;
     int channels, window;
     std::vector<int> channelMap;             // [track]: what fx_set_channel_map was last given (the identity by default)
