@@ -157,7 +157,7 @@ class BatchAnalyser:
 
     def last_launches(self):
         """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
-        (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps)."""
+        (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events)."""
         fn = self._lib.fx_last_launches_internal
         fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int], ctypes.c_int
         cap = capi.LAUNCH_RECORD_CAP
@@ -193,6 +193,25 @@ class BatchAnalyser:
                                          ptr["autocorrelation"], ptr["cnd"], ptr["lag_position"], ctypes.byref(frame)))
         out["frame_index"] = frame.value
         return out
+
+    # ---- onset events: every track's onset callback as one list made on the GPU (include/fx.h, fx_enable_onset_events) ----
+    def enable_onset_events(self, capacity):
+        """Enable the onset event list with room for `capacity` events (or resize it: the stored events are dropped); 0 disables it."""
+        capi.check(self._lib.fx_enable_onset_events(self._h, int(capacity)))
+
+    def onset_events(self, max_events=None):
+        """Drain the list: (events, dropped).  `events` is a structured array (capi.ONSET_EVENT_DTYPE: frame i8, channel i4,
+        call_frame i4) of the oldest stored events -- all of them, or at most max_events, the rest staying for the next call -- in
+        (frame, channel) order; `dropped` the events lost to overflow since the previous drain."""
+        n, dropped = ctypes.c_int(0), ctypes.c_longlong(0)
+        if max_events is None:
+            capi.check(self._lib.fx_get_onset_events(self._h, None, 0, ctypes.byref(n), None))
+            max_events = n.value
+        if int(max_events) < 0:
+            raise ValueError("max_events must be >= 0")
+        out = np.empty(max(int(max_events), 1), capi.ONSET_EVENT_DTYPE)      # (never a null pointer: max_events == 0 is still a drain)
+        capi.check(self._lib.fx_get_onset_events(self._h, out.ctypes.data_as(ctypes.c_void_p), int(max_events), ctypes.byref(n), ctypes.byref(dropped)))
+        return out[:n.value].copy(), dropped.value
 
     def last_kernel_ms(self):
         a, b = ctypes.c_float(), ctypes.c_float()

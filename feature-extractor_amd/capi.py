@@ -33,7 +33,8 @@ EXPORTS = ["fx_create", "fx_destroy", "fx_reset_state", "fx_set_sample_rate", "f
            "fx_offline_log_attack_time", "fx_offline_fft_lbp", "fx_offline_harmonic_characteristics", "fx_offline_spectral_characteristics",
            "fx_offline_get_previous_bins", "fx_offline_spectral_slope", "fx_offline_auto_correlation",
            "fx_request_taps", "fx_get_taps", "fx_set_channel_map", "fx_push_interleaved",
-           "fx_set_channel_gains", "fx_set_channel_onset", "fx_get_channel_settings"]
+           "fx_set_channel_gains", "fx_set_channel_onset", "fx_get_channel_settings",
+           "fx_enable_onset_events", "fx_get_onset_events"]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
 MAX_UNITS = 24
@@ -41,7 +42,7 @@ MAX_UNITS = 24
 LAUNCH_FIELDS = ["kind", "window", "analysers", "T", "direct_state", "block_mode", "num_chunks", "ch_per_wg", "waves_per_ch", "hop_pairs",
                  "ep_T", "out_stride", "ep_form", "reblock"]
 LAUNCH_KINDS = {1: "frame", 2: "frame_tail", 3: "hop", 4: "hop_pair", 5: "pair", 6: "epilogue", 7: "reblock", 8: "osc", 9: "taps",
-                10: "deinterleave"}
+                10: "deinterleave", 11: "onset_events"}
 MAX_TAP_CHANNELS = 64
 LAUNCH_RECORD_CAP = 8
 
@@ -53,6 +54,16 @@ class OscSenderStats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class OnsetEvent(ctypes.Structure):
+    """struct fx_onset_event of include/fx.h: one (track, frame) whose raw onset slot is 1"""
+    _fields_ = [("frame", ctypes.c_longlong), ("channel", ctypes.c_int), ("call_frame", ctypes.c_int)]
+
+
+# the same record as a numpy structured type (BatchAnalyser.onset_events)
+ONSET_EVENT_DTYPE = np.dtype([("frame", np.int64), ("channel", np.int32), ("call_frame", np.int32)])
+MAX_ONSET_EVENTS = 1 << 26
 
 
 class Tuning(ctypes.Structure):
@@ -159,6 +170,8 @@ def load_library(build_if_missing=True):
     L.fx_set_channel_onset.argtypes = [vp, fp, ctypes.POINTER(i), ctypes.POINTER(i)]
     L.fx_get_channel_settings.argtypes = [vp, fp, fp, ctypes.POINTER(i), ctypes.POINTER(i)]
     L.fx_push_interleaved.argtypes = [vp, vp, i, i, i, i, vp, vp, ctypes.POINTER(i)]
+    L.fx_enable_onset_events.argtypes = [vp, i]
+    L.fx_get_onset_events.argtypes = [vp, vp, i, ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
     L.fx_get_taps.argtypes = [vp, i, fp, fp, fp, fp, fp, fp, ctypes.POINTER(ctypes.c_longlong)]
     L.fx_plan_units.argtypes = [i, u, i, i, ctypes.POINTER(Tuning), ctypes.POINTER(i), i]
     L.fx_twiddle_symmetry.argtypes = [i]

@@ -601,7 +601,7 @@ bool blocks_feed_kernels(const fx_context* c)
 // in_kind / out_kind: where the caller's samples and result buffers live (fx_push_samples hands over hops it has assembled in device
 // memory with results that may go to the host)
 fx_status run(fx_context* c, const void* in, int T, int sample_format, int in_kind, int out_kind, int hop_mode,
-              float* out_raw, float* out_smoothed, const BlockFeed* blocks = nullptr, bool taps = false)
+              float* out_raw, float* out_smoothed, const BlockFeed* blocks = nullptr, bool taps = false, bool events = false)
 {
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
     if (T < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative frame count");
@@ -627,8 +627,11 @@ fx_status run(fx_context* c, const void* in, int T, int sample_format, int in_ki
     const void* d_in = in;
     float* d_or = out_raw;
     float* d_os = out_smoothed;
-    if (out_kind == FX_MEM_HOST) {
-        if (out_raw || out_smoothed) {
+    // the onset event list (fx_enable_onset_events) reads the raw vectors where the tails write them: with the list enabled they
+    // always get a device out_raw, the context's staging where the caller gave none (copied back only if the caller asked)
+    const bool list_events = events && c->events_launch;
+    if (out_kind == FX_MEM_HOST || (list_events && !out_raw)) {
+        if (out_raw || out_smoothed || list_events) {
             // one allocation, two halves
             if (2 * raw_bytes > c->out_cap) {
                 float* old = c->d_out_raw;
@@ -641,8 +644,8 @@ fx_status run(fx_context* c, const void* in, int T, int sample_format, int in_ki
             }
             c->d_out_sm = c->d_out_raw + out_elems;
         }
-        d_or = out_raw ? c->d_out_raw : nullptr;
-        d_os = out_smoothed ? c->d_out_sm : nullptr;
+        d_or = out_raw || list_events ? c->d_out_raw : nullptr;
+        if (out_kind == FX_MEM_HOST) d_os = out_smoothed ? c->d_out_sm : nullptr;
     }
     if (in_kind == FX_MEM_HOST) {
         if ((st = grow(reinterpret_cast<unsigned char**>(&c->d_in), &c->in_cap, in_bytes)) != FX_OK) return st;
@@ -688,6 +691,8 @@ fx_status run(fx_context* c, const void* in, int T, int sample_format, int in_ki
     }
     HIP_TRY(mark(e2));
     c->ev_valid = last_valid;
+    // every frame's raw vector is on its way to d_or: the list's one launch (a failure leaves the stream to fx_reset_state)
+    if (list_events && (st = c->events_launch(c, d_or, T, c->frames_seen - T)) != FX_OK) return st;
 
     if (out_kind == FX_MEM_HOST) {
         if (out_raw) HIP_TRY(hipMemcpyAsync(out_raw, c->d_out_raw, raw_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -807,6 +812,7 @@ fx_status fx_destroy(fx_context* c)
     if (c->stream) (void) hipStreamSynchronize(c->stream);
     if (c->taps_release) c->taps_release(c);
     if (c->interleave_release) c->interleave_release(c);
+    if (c->events_release) c->events_release(c);
     void* bufs[] = {c->d_tw, c->d_prev, c->d_tail[0], c->d_tail[1], c->d_hist, c->d_latest,
                     c->d_raw, c->d_part, c->d_in, c->d_out_raw, c->d_queue, c->d_carry[0], c->d_carry[1], c->d_hops, c->d_osc, c->d_chan};
     for (void* b : bufs) if (b) (void) hipFree(b);
@@ -826,6 +832,7 @@ fx_status fx_reset_state(fx_context* c)
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->h_err) *c->h_err = 0;
     if (c->taps_release) c->taps_release(c);
+    if (c->events_reset) { const fx_status st = c->events_reset(c); if (st != FX_OK) return st; }     // the list emptied, still enabled
     return zero_state(c);
 }
 
@@ -937,7 +944,7 @@ fx_status fx_push_hops(fx_context* c, const void* hops, int num_hops, int sample
     if (c && c->carry_count > 0)
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d samples per channel are pending from fx_push_samples; whole hops would overtake them "
                                                 "(finish the stream with fx_push_samples, or fx_reset_state)", c->carry_count);
-    return run(c, hops, num_hops, sample_format, mem_kind, mem_kind, 1, out_raw, out_smoothed, nullptr, true);
+    return run(c, hops, num_hops, sample_format, mem_kind, mem_kind, 1, out_raw, out_smoothed, nullptr, true, true);
 }
 
 // ---- the collector's real interface: device blocks of any length (ref AudioDataCollector.h:36-94) ----
@@ -987,7 +994,7 @@ extern "C++" fx_status fx_push_block(fx_context* c, const void* samples, int num
     // whole hops and nothing pending: the block IS the hop buffer -- from an aligned device buffer, or a host block (512-sample callbacks
     // against a 1024-point window: one copy in, no re-blocking)
     if (c->carry_count == 0 && rest == 0 && (in_kind == FX_MEM_HOST || reinterpret_cast<uintptr_t>(samples) % 16 == 0)) {
-        const fx_status st = run(c, samples, hops, sample_format, in_kind, out_kind, 1, out_raw, out_smoothed, nullptr, taps);
+        const fx_status st = run(c, samples, hops, sample_format, in_kind, out_kind, 1, out_raw, out_smoothed, nullptr, taps, taps);
         if (st == FX_OK && frames_out) *frames_out = hops;
         return st;
     }
@@ -1008,7 +1015,7 @@ extern "C++" fx_status fx_push_block(fx_context* c, const void* samples, int num
         // analysis.  (Windows of 2048 / 4096 points re-block calls of more than two hops: measured faster there, fx_kernels.hip launch_t.)
         const BlockFeed feed = {c->d_carry[c->carry_cur], c->d_carry[c->carry_cur ^ 1], (int) ((size_t) c->carry_count * esz), H * 4,
                                 (long long) num_samples * (long long) esz};
-        st = run(c, d_block, hops, sample_format, FX_MEM_DEVICE, out_kind, 1, out_raw, out_smoothed, &feed, taps);
+        st = run(c, d_block, hops, sample_format, FX_MEM_DEVICE, out_kind, 1, out_raw, out_smoothed, &feed, taps, taps);
         if (st != FX_OK) return st;             // (the stream is no longer the caller's: fx_reset_state, as the contract says)
         c->carry_cur ^= 1;
         c->carry_count = rest;
@@ -1040,7 +1047,7 @@ extern "C++" fx_status fx_push_block(fx_context* c, const void* samples, int num
     c->carry_count = rest;
     c->carry_format = sample_format;
     if (hops > 0) {
-        st = run(c, c->d_hops, hops, sample_format, FX_MEM_DEVICE, out_kind, 1, out_raw, out_smoothed);
+        st = run(c, c->d_hops, hops, sample_format, FX_MEM_DEVICE, out_kind, 1, out_raw, out_smoothed, nullptr, false, taps);   // (taps: served above)
         if (st != FX_OK) return st;
     } else if (in_kind == FX_MEM_HOST) {
         HIP_TRY(hipStreamSynchronize(c->stream));            // the caller's block may be reused on return
@@ -1071,7 +1078,7 @@ fx_status fx_process_frames(fx_context* c, const void* frames, int num_frames, i
     begin_launches(c);
     if (c && c->carry_count > 0)
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d samples per channel are pending from fx_push_samples (finish the stream with fx_push_samples, or fx_reset_state)", c->carry_count);
-    return run(c, frames, num_frames, sample_format, mem_kind, mem_kind, 0, out_raw, out_smoothed, nullptr, true);
+    return run(c, frames, num_frames, sample_format, mem_kind, mem_kind, 0, out_raw, out_smoothed, nullptr, true, true);
 }
 
 fx_status fx_get_smoothed(fx_context* c, float* out, int mem_kind)

@@ -39,6 +39,7 @@ fx_status fx_block_refusal(const fx_context* ctx, int num_samples, int sample_fo
 // fx_request_taps installs, so that the rest of the library refers to no symbol of that unit.
 struct fx_taps;
 struct fx_interleave;   // fx_interleave.hip
+struct fx_events;       // fx_events.hip
 // Where an analysis call reads its FIRST frame, as the kernels read it: `in` (device) holds rows of in_row_bytes per channel; hop_mode 1:
 // hops of N/2 samples, the window is [the channel's tail | hop 0 x gain]; 0: whole frames, frame 0 as given.  carry != null: the hop is
 // the first N/2 samples of [pending | block] (fx_blocks.hip.h, BlockStream), the pending row of the channel at carry + c * carry_row_bytes.
@@ -133,6 +134,14 @@ struct fx_context {
     // fx_set_channel_map / fx_push_interleaved, which installs the hook.  The map is a setting: fx_destroy calls the hook, fx_reset_state does not.
     fx_interleave* interleave = nullptr;
     void (*interleave_release)(fx_context*) = nullptr;
+
+    // the onset event list (fx_events.hip): null until fx_enable_onset_events, which installs the hooks (and removes them again when
+    // it disables the list).  events_launch: after the last analysis launch of a call of T frames per channel whose raw vectors are
+    // in d_raw [C][T][12], frame0 the stream index of the call's first frame.  events_reset: fx_reset_state, the list emptied and kept.
+    fx_events* events = nullptr;
+    fx_status (*events_launch)(fx_context*, const float* d_raw, int T, long long frame0) = nullptr;
+    fx_status (*events_reset)(fx_context*) = nullptr;
+    void      (*events_release)(fx_context*) = nullptr;
 };
 
 #endif

@@ -309,6 +309,9 @@ extern "C" fx_status fx_set_tuning_internal(fx_context* ctx, unsigned test_hooks
 // block_mode = 1 when it reads [pending | block].  A de-interleave launch (fx_interleave.hip) records T = the block's samples per channel.
 enum { FX_LAUNCH_FRAME = 1, FX_LAUNCH_FRAME_TAIL, FX_LAUNCH_HOP, FX_LAUNCH_HOP_PAIR, FX_LAUNCH_PAIR, FX_LAUNCH_EPILOGUE, FX_LAUNCH_REBLOCK,
        FX_LAUNCH_OSC, FX_LAUNCH_TAPS, FX_LAUNCH_DEINTERLEAVE };
+// The onset event list's step (fx_events.hip), the last entry of an analysis call on a context with events enabled: ONE entry and one
+// launch per call (counts, scan and records in one kernel), T = the frames per channel the call analysed.
+constexpr int FX_LAUNCH_ONSET_EVENTS = 11;
 struct fx_launch_record {
     int kind;               // FX_LAUNCH_*
     int window, analysers;  // window size, analysers mask (bit 0 spectral, bit 1 harmonic)

@@ -45,6 +45,22 @@ def set_shard_channel_settings(analyser, num_channels, rank, world_size, gains=N
                                    shard_slice(type, num_channels, rank, world_size))
 
 
+def gather_onset_events(per_rank_events, num_channels):
+    """The onset event lists of every rank (BatchAnalyser.onset_events()[0], in rank order: one structured array per rank, channels
+    numbered within the rank's shard) as ONE list of the whole run: each shard's `channel` is offset by the shard's first channel,
+    and the result is in the list's own order, (frame, channel).  call_frame is kept as each rank reported it."""
+    bounds = shard_bounds(num_channels, len(per_rank_events))
+    parts = []
+    for (first, count), ev in zip(bounds, per_rank_events):
+        ev = np.array(ev, copy=True)
+        if len(ev) and (ev["channel"].min() < 0 or ev["channel"].max() >= count):
+            raise ValueError("a shard of %d channels reported channel %d" % (count, int(ev["channel"].max())))
+        ev["channel"] += first
+        parts.append(ev)
+    out = np.concatenate(parts)
+    return out[np.lexsort((out["channel"], out["frame"]))]
+
+
 def gather_features(local, num_channels, dst=0, group=None, async_op=False, single_rank_collective=False):
     """Gather per-rank feature blocks [C_local][...][12] (torch tensors, CPU for gloo / CUDA for
     RCCL) to rank `dst`.  Returns (result, work): on dst `result` is the [num_channels][...][12]

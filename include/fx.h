@@ -266,6 +266,39 @@ fx_status fx_request_taps(fx_context* ctx, const int* channels, int num_channels
 fx_status fx_get_taps(fx_context* ctx, int channel, float* window, float* spectrum, float* pitch_spectrum,
                       float* autocorrelation, float* cnd, float* lag_position, long long* frame_index);
 
+/* ---- onset events: every track's onset callback as one list made on the GPU ----
+ * RealTimeSpectralAnalyser::run calls onsetDetectedCallback() after any frame whose onset slot is above zero
+ * (RealTimeAnalyser.h:228-229, :256), and AnalyserTrackController.h:80-84 binds that callback per track.  Here a context on which
+ * the list is enabled appends one record per (track, frame) to a list in device memory, and the host drains it when it likes:
+ *   - an event is exactly raw[FX_ONSET] == 1.0f of a frame analysed by fx_push_hops, fx_process_frames, fx_push_samples or
+ *     fx_push_interleaved: the reference's condition, since getValue(enOnset) has history length 1 and so equals the value just
+ *     inserted.  A FX_HARMONIC_ONLY context never produces one (the reference never writes its onset slot, and NaN > 0 is false).
+ *   - `frame` is the frame's 0-based index in the track's stream since fx_create / fx_reset_state, the count fx_get_taps reports as
+ *     frame_index; `call_frame` its index within the call that analysed it; `channel` the track.
+ *   - order: events of earlier calls first, within a call by ascending frame, then ascending channel.  The whole list is therefore
+ *     sorted by (frame, channel) and can be replayed in time order.  The order is part of the contract: it is a function of the
+ *     onset slots alone.
+ *   - events beyond `capacity` are not stored and are counted: the stored ones are the earliest.
+ *   - the list is made by one extra launch on the context's stream after the call's last analysis launch.  The number of events
+ *     stored lives in device memory: an analysis call on an enabled context makes no host wait it does not make otherwise, and
+ *     the results it returns are the bits it returns with the list disabled.  The call's raw vectors need not go to the caller:
+ *     out_raw (and out_smoothed) may be NULL.  If that launch fails the analysis call returns FX_ERR_HIP and, as after a failed
+ *     analysis launch of fx_push_samples, the stream is fx_reset_state's.  On a context that never enabled the list an analysis
+ *     call makes exactly the launches it made before.
+ *   - fx_reset_state empties the list and zeroes the overflow count; the list stays enabled and keeps its capacity.
+ *   - the fx_stream_* ring does not produce events, as it does not serve taps: its captured steps stay as they are. */
+typedef struct fx_onset_event { long long frame; int channel; int call_frame; } fx_onset_event;   /* 16 bytes */
+/* capacity > 0: enable the list with room for `capacity` events, or resize it (the events stored are dropped); 0: disable it and
+ * free its memory.  Synchronises the context's stream.  A null context, a negative capacity or one above 2^26 is
+ * FX_ERR_INVALID_ARGUMENT, before any device use. */
+fx_status fx_enable_onset_events(fx_context* ctx, int capacity);
+/* Synchronises the context's stream, copies the min(stored, cap) oldest events to `out`, removes exactly those from the list (the
+ * rest stay for the next call) and sets *count to their number; *dropped = the events lost to overflow since the previous drain,
+ * and that count starts again.  out == NULL with cap == 0 only reports: *count = the events stored, *dropped = the count so far,
+ * nothing removed or cleared.  count and dropped may be NULL.  FX_ERR_INVALID_ARGUMENT, before any device use: a null context,
+ * cap < 0, out == NULL with cap > 0, a context on which the list is not enabled. */
+fx_status fx_get_onset_events(fx_context* ctx, fx_onset_event* out, int cap, int* count, long long* dropped);
+
 /* ---- streaming ingest: replaces AudioDataCollector's ring + busy-wait reader ----
  * (AudioDataCollector.h:24,36-94: audio thread writes a 4096-sample ring, the analysis thread spins
  * until a hop is available.)  Here the producer owns a ring of `slots` PINNED host batches, each

@@ -216,6 +216,23 @@ public:
         return b;
     }
 
+    // The onset callback of every track as one list (fx_enable_onset_events / fx_get_onset_events): the reference's analysis thread
+    // calls onsetDetectedCallback() after a frame whose onset slot is above zero (RealTimeAnalyser.h:228-229, :256), one callback
+    // per track (AnalyserTrackController.h:80-84).  Once enabled, every analysis call appends its (track, frame) onsets on the GPU,
+    // in (frame, track) order; getOnsetEvents drains what is stored (all of it) and reports what overflowed since the last drain.
+    void enableOnsetEvents (int capacity)                       { check (fx_enable_onset_events (ctx, capacity)); }
+    std::vector<fx_onset_event> getOnsetEvents (long long* droppedSinceLastCall = nullptr)
+    {
+        int stored = 0, got = 0;
+        long long lost = 0;
+        check (fx_get_onset_events (ctx, nullptr, 0, &stored, nullptr));
+        std::vector<fx_onset_event> events ((std::size_t) (stored > 0 ? stored : 1));
+        check (fx_get_onset_events (ctx, events.data(), stored, &got, &lost));
+        events.resize ((std::size_t) got);
+        if (droppedSinceLastCall != nullptr) *droppedSinceLastCall = lost;
+        return events;
+    }
+
     // hops [channels][numHops][window/2] host floats -> raw / smoothed [channels][numHops][12]
     void pushHops (const float* hops, int numHops, float* raw, float* smoothed)
     {
@@ -326,6 +343,7 @@ public:
                                     most ? rawValues.data() : nullptr, most ? smoothedValues.data() : nullptr, &got));
         lastFrames = got;
         if (got > 0 && framesAnalysed) framesAnalysed (got);
+        if (got > 0) reportOnsets();
         return got;
     }
     // the same for a block that is already [channel][numberOfSamples] in one piece, in any sample format of fx.h
@@ -339,9 +357,19 @@ public:
                                 most ? rawValues.data() : nullptr, most ? smoothedValues.data() : nullptr, &frames));
         lastFrames = frames;
         if (frames > 0 && framesAnalysed) framesAnalysed (frames);      // where the reference calls notifyAnalysisThread(), :68-69
+        if (frames > 0) reportOnsets();
         return frames;
     }
     void setNotifyAnalysisThreadCallback (std::function<void (int)> f)  { framesAnalysed = f; }    // ref :107 (argument: frames per channel)
+    // The tracks' onsetDetectedCallback (RealTimeAnalyser.h:256, AnalyserTrackController.h:80-84) as one callback: after each block
+    // that completed frames it is called once per (track, frame) whose onset slot is 1, in (frame, track) order.  Setting it enables
+    // the analyser's onset event list (room for `capacity` events between two blocks; what does not fit is lost and counted by the list).
+    void setOnsetDetectedCallback (std::function<void (int track, long long frame)> f, int capacity = 1 << 16)
+    {
+        onsetDetected = f;
+        analyser.enableOnsetEvents (f ? capacity : 0);
+        drainOnsets = [this] { return analyser.getOnsetEvents(); };
+    }
     void setGain (float g)       { analyser.setGain (g); }                                          // ref :124
     void clearBuffer()           { check (fx_clear_pending (analyser.handle())); }                  // ref :122
     int  getNumPendingSamples()  { return fx_pending_samples (analyser.handle()); }
@@ -350,10 +378,18 @@ public:
     const float* smoothed() const { return smoothedValues.data(); }
 
 private:
+    void reportOnsets()
+    {
+        // (through drainOnsets: a host that never sets the callback needs no symbol of the event list from the library)
+        if (! onsetDetected || ! drainOnsets) return;
+        for (const fx_onset_event& e : drainOnsets()) onsetDetected (e.channel, e.frame);
+    }
     RealTimeBatchAnalyser& analyser;
     int channels, hop, lastFrames = 0;
     std::vector<float> block, rawValues, smoothedValues;
     std::function<void (int)> framesAnalysed;
+    std::function<void (int, long long)> onsetDetected;
+    std::function<std::vector<fx_onset_event>()> drainOnsets;
 };
 
 // The stand-in for AudioDataCollector's ring (ref Source/AudioDataCollector.h:24,36-94: the audio thread writes a ring, the analysis thread
@@ -682,6 +718,7 @@ class LiveAnalyser
 {
 public:
     typedef std::function<void (int frames, const float* raw, const float* smoothed)> FramesCallback;   // [channels][frames][12], worker thread
+    typedef std::function<void (int track, long long frame)> OnsetCallback;                              // worker thread
 
     // sampleFormat: what pushBlock's blocks hold -- FX_SAMPLE_F32 (JUCE's float callbacks; audioDeviceIOCallback needs it), or the device's own
     // integers as they are (FX_SAMPLE_S16, packed FX_SAMPLE_S24) or FX_SAMPLE_F16: half / three quarters of the bytes across the link, the same
@@ -689,7 +726,8 @@ public:
     LiveAnalyser (RealTimeBatchAnalyser& analyserToFeed, int maxBlockSamples, int fifoBlocks = 8, int sampleFormat = FX_SAMPLE_F32)
         : analyser (analyserToFeed), channels (analyserToFeed.getNumChannels()), hop (analyserToFeed.getWindowSize() / 2),
           maxBlock (maxBlockSamples), format (sampleFormat),
-          sampleBytes (sampleFormat == FX_SAMPLE_F32 ? 4 : (sampleFormat == FX_SAMPLE_S24 ? 3 : 2)), slots ((std::size_t) (fifoBlocks > 1 ? fifoBlocks : 2))
+          sampleBytes (sampleFormat == FX_SAMPLE_F32 ? 4 : (sampleFormat == FX_SAMPLE_S24 ? 3 : 2)), slots ((std::size_t) (fifoBlocks > 1 ? fifoBlocks : 2)),
+          mostFrames ((maxBlockSamples > 0 ? maxBlockSamples + analyserToFeed.getWindowSize() / 2 - 1 : 0) / (analyserToFeed.getWindowSize() / 2) + 1)
     {
         if (maxBlockSamples < 1) throw Error (FX_ERR_INVALID_ARGUMENT, "maxBlockSamples must be positive");
         if (sampleFormat != FX_SAMPLE_F32 && sampleFormat != FX_SAMPLE_F16 && sampleFormat != FX_SAMPLE_S16 && sampleFormat != FX_SAMPLE_S24)
@@ -740,6 +778,18 @@ public:
 
     // set before the first block (not synchronised against the worker)
     void setFramesAnalysedCallback (FramesCallback f)                               { framesAnalysed = f; }
+    // The tracks' onsetDetectedCallback (RealTimeAnalyser.h:256, AnalyserTrackController.h:80-84) as one callback: the worker drains
+    // the analyser's onset event list after each block that completed frames and calls `f` once per (track, frame) whose onset
+    // slot is 1, in (frame, track) order.  Setting it enables the list on the analyser, with room for every onset one block can
+    // hold.  With this callback and NO frames callback the engine asks for neither result buffer: the block's vectors never cross
+    // the link (latestSmoothed() then stays empty; an attached OSC sender still gets its messages, formed on the GPU).
+    void setOnsetDetectedCallback (OnsetCallback f)
+    {
+        onsetDetected = f;
+        const long long room = (long long) channels * (long long) mostFrames;
+        analyser.enableOnsetEvents (f ? (int) (room < (1ll << 26) ? room : (1ll << 26)) : 0);
+        drainOnsets = [this] { return analyser.getOnsetEvents(); };       // (the worker's only way to the list: see analyse())
+    }
     void attachOSCSender (OSCBatchSender* sender, const std::string& bundlePrefix = "/Audio/A", int firstChannel = 0)
     {
         osc = sender; oscPrefix = bundlePrefix; oscFirst = firstChannel;
@@ -828,9 +878,16 @@ private:
     void analyse (Slot& s)
     {
         int got = 0;
-        if (fx_push_samples (analyser.handle(), s.samples, s.count, format, FX_MEM_HOST, rawValues, smoothedValues, &got) != FX_OK) { fail ("fx_push_samples"); return; }
+        const bool onsetsOnly = onsetDetected && ! framesAnalysed;      // nobody reads the vectors: they stay on the GPU
+        if (fx_push_samples (analyser.handle(), s.samples, s.count, format, FX_MEM_HOST, onsetsOnly ? nullptr : rawValues,
+                             onsetsOnly ? nullptr : smoothedValues, &got) != FX_OK) { fail ("fx_push_samples"); return; }
         if (got <= 0) return;
         if (framesAnalysed) framesAnalysed (got, rawValues, smoothedValues);
+        if (onsetDetected && drainOnsets)       // (a host that never sets the callback needs no symbol of the event list from the library)
+        {
+            try { for (const fx_onset_event& e : drainOnsets()) onsetDetected (e.channel, e.frame); }
+            catch (const Error&) { fail ("fx_get_onset_events"); }
+        }
         if (osc != nullptr)
         {
             try { osc->updateFromContext (analyser.handle(), channels, oscPrefix, oscFirst); }
@@ -840,6 +897,7 @@ private:
         std::lock_guard<std::mutex> g (statLock);
         frames += got;
         if (latencies.size() < latencies.capacity()) latencies.push_back ((float) ms);
+        if (onsetsOnly) return;
         latest.resize ((std::size_t) channels * FX_NUM_FEATURES);
         for (int c = 0; c < channels; ++c)
             std::memcpy (&latest[(std::size_t) c * FX_NUM_FEATURES], &smoothedValues[((std::size_t) c * (std::size_t) got + (std::size_t) (got - 1)) * FX_NUM_FEATURES], sizeof (float) * FX_NUM_FEATURES);
@@ -876,6 +934,7 @@ private:
     int channels, hop, maxBlock, format;
     std::size_t sampleBytes;
     std::vector<Slot> slots;
+    int mostFrames;                      // frames per channel a block plus the pending samples can complete
     std::atomic<long long> written { 0 }, consumed { 0 }, dropped { 0 };
     std::mutex wake;
     std::condition_variable ready, idle;
@@ -884,6 +943,8 @@ private:
     std::atomic<bool> running { false };
     std::thread worker;
     FramesCallback framesAnalysed;
+    OnsetCallback onsetDetected;
+    std::function<std::vector<fx_onset_event>()> drainOnsets;
     OSCBatchSender* osc = nullptr;
     std::string oscPrefix;
     int oscFirst = 0;

@@ -8,7 +8,10 @@
 // publication latency (p50 / p99 / max), the worker's busy share of real time, resident memory at the start and the end; at the end every
 // channel's newest received datagram is compared with fx_osc_encode of the vector the analyser last published.
 //
-//   live_soak [channels=8192] [window=1024] [block=480] [seconds=60] [sender_threads=4] [gso=1] [dump=path]
+//   live_soak [channels=8192] [window=1024] [block=480] [seconds=60] [sender_threads=4] [gso=1] [dump=path] [onsets=0]
+// onsets=1: the host hears about onsets through fx::LiveAnalyser::setOnsetDetectedCallback alone (the list made on the GPU; no result
+// vector crosses the link); onsets=2: through a frames callback that walks raw[channels][frames][12], as hosts did before the list.
+// Both report the onsets heard and the bytes of results that came back to the host per block.
 // dump=path writes {int32 channels, window, block, blocks, pool_blocks; float32 smoothed[channels][12]} for tests/test_gpu_soak.py, which
 // rebuilds the input (integer arithmetic below) and holds a sample of channels to the oracle.
 // Build: g++ -std=c++14 -O2 -I include tools/live_soak.cpp -L feature-extractor_amd/lib -lfx_hip -Wl,-rpath,$PWD/feature-extractor_amd/lib -pthread
@@ -45,7 +48,7 @@ long resident_kb()
 
 int main(int argc, char** argv)
 {
-    int channels = 8192, window = 1024, block = 480, seconds = 60, senderThreads = 4, gso = 1, withOsc = 1;
+    int channels = 8192, window = 1024, block = 480, seconds = 60, senderThreads = 4, gso = 1, withOsc = 1, onsets = 0;
     std::string dump;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -55,6 +58,7 @@ int main(int argc, char** argv)
         else if (k == "block") block = std::atoi(v.c_str()); else if (k == "seconds") seconds = std::atoi(v.c_str());
         else if (k == "sender_threads") senderThreads = std::atoi(v.c_str()); else if (k == "gso") gso = std::atoi(v.c_str());
         else if (k == "dump") dump = v;
+        else if (k == "onsets") onsets = std::atoi(v.c_str());
         else if (k == "osc") withOsc = std::atoi(v.c_str());            // 0: analysis only (diagnostics: nothing is published or sent)
         else { std::fprintf(stderr, "live_soak: unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -73,6 +77,14 @@ int main(int argc, char** argv)
         fx::OSCBatchSender sender("127.0.0.1:" + std::to_string(fx_osc_receiver_port(rx)), "", senderThreads, gso != 0);
         fx::LiveAnalyser live(analyser, block, 8);
         if (withOsc) live.attachOSCSender(&sender, "/Audio/A", 0);
+        long long onsetsHeard = 0, resultBytes = 0;                  // written by the worker, read after drain()
+        if (onsets == 1)
+            live.setOnsetDetectedCallback([&](int, long long) { onsetsHeard++; resultBytes += (long long) sizeof(fx_onset_event); });
+        else if (onsets == 2)
+            live.setFramesAnalysedCallback([&](int frames, const float* raw, const float*) {
+                for (size_t i = 0; i < (size_t) channels * (size_t) frames; i++) onsetsHeard += raw[i * 12 + FX_ONSET] > 0.0f;
+                resultBytes += 2ll * channels * frames * 12 * (long long) sizeof(float);
+            });
         sender.startTimerHz(60);
 
         // two seconds of warm-up (allocations, first touches, clocks), then the measured run
@@ -107,7 +119,11 @@ int main(int argc, char** argv)
         std::this_thread::sleep_for(std::chrono::milliseconds(300));
         long long rxn = 0, rxbad = 0;
         fx_osc_receiver_get_stats(rx, &rxn, nullptr, &rxbad);
-        const std::vector<float> latest = live.latestSmoothed();
+        std::vector<float> latest = live.latestSmoothed();
+        if (latest.empty()) {                                        // onsets=1: the vectors stayed on the GPU; the worker is idle now
+            latest.resize((size_t) channels * 12);
+            fx::check(fx_get_smoothed(analyser.handle(), latest.data(), FX_MEM_HOST));
+        }
         long long wrong = 0;
         for (int c = 0; c < channels; c++) {
             unsigned char got[160], want[160];
@@ -128,6 +144,10 @@ int main(int argc, char** argv)
                     sent / wall, ss.dropped - sw.dropped, ss.max_tick_ms);
         std::printf("  receiver: %lld datagrams (%.4f of those sent), %lld malformed; after the last tick %lld of %d channels hold a datagram that is not fx_osc_encode of the last published vector\n",
                     rxn - rxw - lastSent, (double) (rxn - rxw - lastSent) / (double) (sent > 0 ? sent : 1), rxbad, wrong, channels);
+        if (onsets)
+            std::printf("  onsets heard through %s: %lld (warm-up included); result bytes back to the host per block %.0f\n",
+                        onsets == 1 ? "the onset callback alone (list made on the GPU)" : "a frames callback walking raw[channels][frames][12]", onsetsHeard,
+                        (double) resultBytes / (double) (st.blocksAnalysed > 0 ? st.blocksAnalysed : 1));
         std::printf("  resident memory %ld KB after warm-up, %ld KB at the end (%+ld KB)\n", rss0, rss1, rss1 - rss0);
         const bool ok = st.errors == 0 && st.blocksDropped == warm.blocksDropped && ss.dropped == sw.dropped && (wrong == 0 || ! withOsc) && rxbad == 0 && frames > 0;
         // one machine-readable line (bench.py's `live_soak` extra reads it)
