@@ -129,6 +129,37 @@ class BatchAnalyser:
                                                      out["type"].ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out
 
+    # ---- per-track reset and clear (include/fx.h, fx_reset_channels / fx_clear_pending_channels; MainComponent.cpp:137-186) ----
+    def _track_list(self, channels):
+        """a list of tracks as int32, checked here before any context use: integers in [0, num_channels); duplicates allowed"""
+        a = np.asarray(channels if channels is not None else [])
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("a track list holds integers, not %s" % a.dtype)
+        a = np.ascontiguousarray(a.ravel().astype(np.int64))
+        bad = np.flatnonzero((a < 0) | (a >= self.num_channels))
+        if bad.size:
+            raise ValueError("entry %d: track %d out of range [0,%d)" % (int(bad[0]), int(a[bad[0]]), self.num_channels))
+        a = a.astype(np.int32)
+        return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+    def reset_channels(self, channels):
+        """A new AnalyserTrackController in these slots: the listed tracks' window tail, flux state, histories, latest vector and pending
+        samples become those of a new context (the pending count and every setting stay); their frame index starts at 0 again.  The
+        other tracks are untouched.  Synchronises the context's stream."""
+        a, ptr = self._track_list(channels)
+        capi.check(self._lib.fx_reset_channels(self._h, ptr, int(a.size)))
+
+    def clear_pending_channels(self, channels):
+        """AudioDataCollector::clearBuffer on the listed tracks only: their pending samples become zeros."""
+        a, ptr = self._track_list(channels)
+        capi.check(self._lib.fx_clear_pending_channels(self._h, ptr, int(a.size)))
+
+    def channel_frames(self):
+        """Frames each track has analysed since it was created or last reset (int64 [C])."""
+        out = np.empty(self.num_channels, np.int64)
+        capi.check(self._lib.fx_get_channel_frames(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return out
+
     # ---- launch-shape knobs (within a kernel family they never change a result bit; waves_per_frame selects the family) ----
     def get_tuning(self):
         t = capi.Tuning()
@@ -202,7 +233,8 @@ class BatchAnalyser:
     def onset_events(self, max_events=None):
         """Drain the list: (events, dropped).  `events` is a structured array (capi.ONSET_EVENT_DTYPE: frame i8, channel i4,
         call_frame i4) of the oldest stored events -- all of them, or at most max_events, the rest staying for the next call -- in
-        (frame, channel) order; `dropped` the events lost to overflow since the previous drain."""
+        the list's order (earlier calls first, then call_frame, then channel: (frame, channel) order while no track was reset on
+        its own); `dropped` the events lost to overflow since the previous drain."""
         n, dropped = ctypes.c_int(0), ctypes.c_longlong(0)
         if max_events is None:
             capi.check(self._lib.fx_get_onset_events(self._h, None, 0, ctypes.byref(n), None))

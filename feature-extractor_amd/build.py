@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfx_hip.so")
-SOURCES = ["fx_kernels.hip", "fx_capi.cpp", "fx_comm.cpp", "fx_offline.hip", "fx_reblock.hip", "fx_osc.hip", "fx_osc_sender.cpp", "fx_taps.hip", "fx_interleave.hip", "fx_events.hip"]
+SOURCES = ["fx_kernels.hip", "fx_capi.cpp", "fx_comm.cpp", "fx_offline.hip", "fx_reblock.hip", "fx_osc.hip", "fx_osc_sender.cpp", "fx_taps.hip", "fx_interleave.hip", "fx_events.hip", "fx_tracks.hip"]
 # fx_kernels.hip is compiled twice: frame kernels up to 1024 points (+ tail kernels + host helpers) with the scheduler's
 # alternative register-pressure tracker (+3.5 % at 1024 points), the 2048- / 4096-point frame kernels without (-7 % at 4096)
 UNITS = [("fx_kernels.hip", "fx_kernels_small.o", ["-DFX_PART=1", "-mllvm", "-amdgpu-use-amdgpu-trackers=1"]),
@@ -22,6 +22,7 @@ UNITS = [("fx_kernels.hip", "fx_kernels_small.o", ["-DFX_PART=1", "-mllvm", "-am
          ("fx_taps.hip", "fx_taps.o", []),
          ("fx_interleave.hip", "fx_interleave.o", []),
          ("fx_events.hip", "fx_events.o", []),
+         ("fx_tracks.hip", "fx_tracks.o", []),
          ("fx_osc_sender.cpp", "fx_osc_sender.o", []),
          ("fx_capi.cpp", "fx_capi.o", []),
          ("fx_comm.cpp", "fx_comm.o", [])]

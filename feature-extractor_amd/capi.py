@@ -34,7 +34,8 @@ EXPORTS = ["fx_create", "fx_destroy", "fx_reset_state", "fx_set_sample_rate", "f
            "fx_offline_get_previous_bins", "fx_offline_spectral_slope", "fx_offline_auto_correlation",
            "fx_request_taps", "fx_get_taps", "fx_set_channel_map", "fx_push_interleaved",
            "fx_set_channel_gains", "fx_set_channel_onset", "fx_get_channel_settings",
-           "fx_enable_onset_events", "fx_get_onset_events"]
+           "fx_enable_onset_events", "fx_get_onset_events",
+           "fx_reset_channels", "fx_clear_pending_channels", "fx_get_channel_frames"]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
 MAX_UNITS = 24
@@ -170,6 +171,9 @@ def load_library(build_if_missing=True):
     L.fx_set_channel_onset.argtypes = [vp, fp, ctypes.POINTER(i), ctypes.POINTER(i)]
     L.fx_get_channel_settings.argtypes = [vp, fp, fp, ctypes.POINTER(i), ctypes.POINTER(i)]
     L.fx_push_interleaved.argtypes = [vp, vp, i, i, i, i, vp, vp, ctypes.POINTER(i)]
+    L.fx_reset_channels.argtypes = [vp, ctypes.POINTER(i), i]
+    L.fx_clear_pending_channels.argtypes = [vp, ctypes.POINTER(i), i]
+    L.fx_get_channel_frames.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     L.fx_enable_onset_events.argtypes = [vp, i]
     L.fx_get_onset_events.argtypes = [vp, vp, i, ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
     L.fx_get_taps.argtypes = [vp, i, fp, fp, fp, fp, fp, fp, ctypes.POINTER(ctypes.c_longlong)]

@@ -49,21 +49,19 @@ size_t sample_size(int f) { return f == FX_SAMPLE_F32 ? 4 : (f == FX_SAMPLE_S24 
 } // namespace
 
 
-namespace {
-
 // ---- per-track settings (fx_set_channel_gains / fx_set_channel_onset; fx_context::chan) ----
-// what every track runs with now: the table's rows, or the context-wide values while no table exists
-void channel_rows(const fx_context* c, std::vector<fxk::ChannelSettings>* rows, std::vector<float>* sensitivity)
+// what every track runs with now: the table's rows, or the context-wide values while no table exists (fx_context.h)
+void fx_channel_rows(const fx_context* c, std::vector<fxk::ChannelSettings>* rows, std::vector<float>* sensitivity)
 {
     if (!c->chan.empty()) { *rows = c->chan; *sensitivity = c->chan_sensitivity; return; }
-    rows->assign((size_t) c->C, fxk::ChannelSettings{c->gain, c->onset_multiplier, c->onset_window, c->onset_type, c->onset_reset_frame});
+    rows->assign((size_t) c->C, fxk::ChannelSettings{c->gain, c->onset_multiplier, c->onset_window, c->onset_type, c->onset_reset_frame, 0});
     sensitivity->assign((size_t) c->C, c->onset_sensitivity);
 }
 
 // Puts `rows` in force for the calls that follow, in stream order: a copy on the context's stream from pinned rows that stay until the
 // next upload has waited for it.  The first upload allocates the table.  A failure leaves the old settings in force (and no table
 // where there was none).
-fx_status upload_channel_rows(fx_context* c, const std::vector<fxk::ChannelSettings>& rows, const std::vector<float>& sensitivity)
+fx_status fx_upload_channel_rows(fx_context* c, const std::vector<fxk::ChannelSettings>& rows, const std::vector<float>& sensitivity)
 {
     const size_t bytes = rows.size() * sizeof(fxk::ChannelSettings);
     HIP_TRY(hipSetDevice(c->device));
@@ -91,6 +89,8 @@ fx_status upload_channel_rows(fx_context* c, const std::vector<fxk::ChannelSetti
     return FX_OK;
 }
 
+namespace {
+
 // A context-wide setter on a context that has a table: `set` changes one row, every row gets it.  No table: nothing to do.
 template <typename F> fx_status set_every_channel(fx_context* c, F set)
 {
@@ -98,13 +98,13 @@ template <typename F> fx_status set_every_channel(fx_context* c, F set)
     std::vector<fxk::ChannelSettings> rows = c->chan;
     std::vector<float> sensitivity = c->chan_sensitivity;
     for (size_t i = 0; i < rows.size(); i++) set(rows[i], sensitivity[i]);
-    return upload_channel_rows(c, rows, sensitivity);
+    return fx_upload_channel_rows(c, rows, sensitivity);
 }
 
 fx_status zero_state(fx_context* c)
 {
-    // (first: the one step that can leave the per-track rows as they were.  Every track's onset histories start at frame 0 again.)
-    { const fx_status st = set_every_channel(c, [](fxk::ChannelSettings& r, float&) { r.onset_reset_frame = 0; }); if (st != FX_OK) return st; }
+    // (first: the one step that can leave the per-track rows as they were.  Every track's stream and onset histories start at frame 0 again.)
+    { const fx_status st = set_every_channel(c, [](fxk::ChannelSettings& r, float&) { r.onset_reset_frame = 0; r.first_frame = 0; }); if (st != FX_OK) return st; }
     const size_t half = (size_t) c->C * (c->N / 2);
     HIP_TRY(hipMemsetAsync(c->d_prev, 0, half * sizeof(float), c->stream));
     for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(c->d_tail[i], 0, half * sizeof(float), c->stream));
@@ -813,6 +813,7 @@ fx_status fx_destroy(fx_context* c)
     if (c->taps_release) c->taps_release(c);
     if (c->interleave_release) c->interleave_release(c);
     if (c->events_release) c->events_release(c);
+    if (c->tracks_release) c->tracks_release(c);
     void* bufs[] = {c->d_tw, c->d_prev, c->d_tail[0], c->d_tail[1], c->d_hist, c->d_latest,
                     c->d_raw, c->d_part, c->d_in, c->d_out_raw, c->d_queue, c->d_carry[0], c->d_carry[1], c->d_hops, c->d_osc, c->d_chan};
     for (void* b : bufs) if (b) (void) hipFree(b);
@@ -893,9 +894,9 @@ fx_status fx_set_channel_gains(fx_context* c, const float* gain)
     if (!gain) return FX_OK;
     std::vector<fxk::ChannelSettings> rows;
     std::vector<float> sensitivity;
-    channel_rows(c, &rows, &sensitivity);
+    fx_channel_rows(c, &rows, &sensitivity);
     for (int i = 0; i < c->C; i++) rows[(size_t) i].gain = gain[i];
-    return upload_channel_rows(c, rows, sensitivity);
+    return fx_upload_channel_rows(c, rows, sensitivity);
 }
 
 fx_status fx_set_channel_onset(fx_context* c, const float* sensitivity, const int* window, const int* type)
@@ -912,14 +913,14 @@ fx_status fx_set_channel_onset(fx_context* c, const float* sensitivity, const in
     }
     std::vector<fxk::ChannelSettings> rows;
     std::vector<float> sens;
-    channel_rows(c, &rows, &sens);
+    fx_channel_rows(c, &rows, &sens);
     for (int i = 0; i < c->C; i++) {
         fxk::ChannelSettings& r = rows[(size_t) i];
         if (sensitivity) { r.onset_multiplier = 1.0f + sensitivity[i]; sens[(size_t) i] = sensitivity[i]; }
         if (window && window[i] > 0) { r.onset_window = window[i]; r.onset_reset_frame = c->frames_seen; }   // setHistoryLength: both histories emptied
         if (type) r.onset_type = type[i];
     }
-    return upload_channel_rows(c, rows, sens);
+    return fx_upload_channel_rows(c, rows, sens);
 }
 
 fx_status fx_get_channel_settings(fx_context* c, float* gain, float* sensitivity, int* window, int* type)
@@ -927,7 +928,7 @@ fx_status fx_get_channel_settings(fx_context* c, float* gain, float* sensitivity
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
     std::vector<fxk::ChannelSettings> rows;
     std::vector<float> sens;
-    channel_rows(c, &rows, &sens);
+    fx_channel_rows(c, &rows, &sens);
     for (int i = 0; i < c->C; i++) {
         if (gain) gain[i] = rows[(size_t) i].gain;
         if (sensitivity) sensitivity[i] = sens[(size_t) i];

@@ -40,6 +40,7 @@ fx_status fx_block_refusal(const fx_context* ctx, int num_samples, int sample_fo
 struct fx_taps;
 struct fx_interleave;   // fx_interleave.hip
 struct fx_events;       // fx_events.hip
+struct fx_tracks;       // fx_tracks.hip
 // Where an analysis call reads its FIRST frame, as the kernels read it: `in` (device) holds rows of in_row_bytes per channel; hop_mode 1:
 // hops of N/2 samples, the window is [the channel's tail | hop 0 x gain]; 0: whole frames, frame 0 as given.  carry != null: the hop is
 // the first N/2 samples of [pending | block] (fx_blocks.hip.h, BlockStream), the pending row of the channel at carry + c * carry_row_bytes.
@@ -142,6 +143,18 @@ struct fx_context {
     fx_status (*events_launch)(fx_context*, const float* d_raw, int T, long long frame0) = nullptr;
     fx_status (*events_reset)(fx_context*) = nullptr;
     void      (*events_release)(fx_context*) = nullptr;
+
+    // per-track reset and clear (fx_tracks.hip): the channel list's staging and device copy; null until the first fx_reset_channels /
+    // fx_clear_pending_channels, which installs the hook fx_destroy calls.  The tracks' first frames live in `chan` (first_frame).
+    fx_tracks* tracks = nullptr;
+    void (*tracks_release)(fx_context*) = nullptr;
 };
+
+// The per-track rows (fx_capi.cpp), for the units that change them.  fx_channel_rows: what every track runs with now -- the table's rows,
+// or the context-wide values (first_frame 0) while no table exists.  fx_upload_channel_rows: puts `rows` in force for the calls that
+// follow, in stream order; synchronises the stream; the first upload allocates the table; a failure leaves the old rows in force, on
+// the device and in fx_context::chan (and no table where there was none).
+void fx_channel_rows(const fx_context* ctx, std::vector<fxk::ChannelSettings>* rows, std::vector<float>* sensitivity);
+fx_status fx_upload_channel_rows(fx_context* ctx, const std::vector<fxk::ChannelSettings>& rows, const std::vector<float>& sensitivity);
 
 #endif

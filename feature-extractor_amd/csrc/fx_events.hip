@@ -4,7 +4,8 @@
 // ref RealTimeAnalyser.h:228-229, :256: RealTimeSpectralAnalyser::run calls onsetDetectedCallback() after any frame whose onset slot is
 // above zero, and AnalyserTrackController.h:80-84 binds that callback per track.  getValue(enOnset) has history length 1, so the
 // condition is the raw slot of the frame just analysed: raw[FX_ONSET] == 1.0f.  Here an enabled context appends one record per
-// (track, frame) with that value to a list in device memory, ordered by (frame, channel), and the host drains the list when it likes.
+// (track, frame) with that value to a list in device memory, ordered by (call, frame of the call, channel), and the host drains the list
+// when it likes.  A record's `frame` is the track's own index: the call's stream index less the track's first_frame (fx_tracks.hip).
 //
 // One launch of fx_onset_events_kernel per analysis call, after the call's last analysis launch (the tails have then written every
 // frame's raw vector to the call's device out_raw, [C][T][12]).  A wavefront reads the onset slot of 64 consecutive channels of one
@@ -48,6 +49,7 @@ struct EventsParams {
     fx_onset_event*     ring;       // [capacity]
     EventsState*        state;
     long long           frame0;     // stream index of the call's first frame
+    const ChannelSettings* chan;    // per-track rows or null: a track's `frame` counts from its own first_frame (fx_reset_channels)
     int                 C, T, G;    // G = ceil(C / 64)
     int                 capacity, head;     // head < capacity: only a drain moves it, and a drain synchronises
 };
@@ -143,7 +145,7 @@ __global__ void __launch_bounds__(EV_THREADS) fx_onset_events_kernel(const Event
                 m &= m - 1;
                 long long at = (long long) p.head + (long long) pos;
                 if (at >= p.capacity) at -= p.capacity;
-                const long long frame = p.frame0 + t;
+                const long long frame = p.frame0 + t - (p.chan ? p.chan[c0 + bit].first_frame : 0);
                 uint4 rec;
                 rec.x = (unsigned) ((unsigned long long) frame & 0xffffffffull);
                 rec.y = (unsigned) ((unsigned long long) frame >> 32);
@@ -227,6 +229,7 @@ fx_status events_launch(fx_context* c, const float* d_raw, int T, long long fram
     p.ring = e->d_ring;
     p.state = e->d_state;
     p.frame0 = frame0;
+    p.chan = c->d_chan;
     p.C = c->C;
     p.T = T;
     p.G = G;

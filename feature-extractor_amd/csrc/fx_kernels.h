@@ -64,8 +64,10 @@ struct ChannelSettings {
     int       onset_window;
     int       onset_type;
     long long onset_reset_frame;    // global index of the channel's first frame after its last onset-window reset
+    long long first_frame;          // global index of the first frame of the channel's current stream (fx_reset_channels, fx_tracks.hip): what
+                                    // the channel's histories hold is counted from here; 0 until the track is reset on its own
 };
-static_assert(sizeof(ChannelSettings) == 24, "rows are copied as they are");
+static_assert(sizeof(ChannelSettings) == 32, "rows are copied as they are");
 
 constexpr int FX_MAX_CHUNKS = FX_MAX_UNITS;
 
@@ -183,6 +185,12 @@ __device__ __forceinline__ OnsetSettings onset_settings(const EpilogueParams& p,
     const ChannelSettings s = p.chan[c];
     return {s.onset_reset_frame, s.onset_window, s.onset_type, s.onset_multiplier};
 }
+// Frames of channel c's CURRENT stream analysed before this call: what decides how full its ValueHistorys are.  The ring row of a frame
+// stays its global index mod HLEN; rows older than the track's first frame are never valid (RawView::valid), so a reset clears none.
+__device__ __forceinline__ long long track_frames_before(const EpilogueParams& p, int c)
+{
+    return p.chan ? p.frames_before - p.chan[c].first_frame : p.frames_before;
+}
 #endif
 
 // Completion signal of a one-hop call (fx_hop_kernel): workgroups count themselves in `arrivals` (device memory, zero
@@ -232,6 +240,21 @@ struct OscParams {
     unsigned char  prefix[FX_OSC_PREFIX_MAX];
 };
 hipError_t launch_osc_kernel(const OscParams& p, hipStream_t stream);
+
+// fx_reset_channels / fx_clear_pending_channels (fx_tracks.hip): rows of the listed channels become zeros in the buffers `clear` names.
+// prev / tail / carry rows are row_pieces 16-byte pieces (N/2 * 4 bytes), a latest row is three (12 floats).
+enum { FX_CLEAR_PREV = 1, FX_CLEAR_TAIL = 2, FX_CLEAR_CARRY = 4, FX_CLEAR_LATEST = 8 };
+struct ResetParams {
+    const int* list;            // [n] channels, device memory; every entry in [0, C) (checked by the host, and again by the kernel)
+    int        n, C;
+    int        row_pieces;
+    unsigned   clear;           // FX_CLEAR_*
+    float*     prev;            // [C][N/2]
+    float*     tail;            // [C][N/2]: the tail the next call reads
+    unsigned char* carry;       // [C][N/2 * 4 bytes]: the pending rows the next call reads
+    float*     latest;          // [C][12]
+};
+hipError_t launch_reset_channels_kernel(const ResetParams& p, hipStream_t stream);
 
 // Re-order the reference's N-entry twiddle table (canonical[i] = (re, im) of e^{-2*pi*i/N} as floats)
 // into the order the FFT passes read it; `out` has room for window_size complex entries.

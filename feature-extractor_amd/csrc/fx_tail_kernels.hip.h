@@ -187,7 +187,7 @@ __device__ __forceinline__ int hist_row_before(int hist_base, int tau) { const i
 // detector's L candidates each want an RMS mean that reaches nine frames back with one insert per hop, five with two
 __device__ __forceinline__ int hist_rows_read(int onset_window) { const int n = onset_window + 8; return n < 9 ? 9 : (n > HLEN ? HLEN : n); }
 struct RawView {
-    const float* raw; const float* hist; int T; long long frames_before; int hist_base;
+    const float* raw; const float* hist; int T; long long frames_before; int hist_base;     // frames_before: the TRACK's (track_frames_before)
     const float* tile = nullptr; int tile_first = 0; bool tiled = false;     // (a flag, not `tile != nullptr`: a dynamic-LDS tile may sit at LDS address 0)
     // raw value of slot s at frame index tau relative to this call (tau may be negative);
     // frames before the stream began read as "not recorded"
@@ -283,7 +283,7 @@ __device__ __forceinline__ void epilogue_frame(const EpilogueParams& p, int c, i
     v.raw = p.raw + (size_t) c * p.T * FX_NUM_FEATURES;
     v.hist = p.hist + (size_t) c * HLEN * FX_NUM_FEATURES;
     v.T = p.T;
-    v.frames_before = p.frames_before;
+    v.frames_before = track_frames_before(p, c);
     v.hist_base = p.hist_base;
     v.tile = tile;
     v.tile_first = tile_first;
@@ -299,7 +299,7 @@ __device__ __forceinline__ void epilogue_frame(const EpilogueParams& p, int c, i
     const int order_mode = (spec && harm) ? p.order_mode : FX_ORDER_ISOLATED;
     const float never = __int_as_float(0x7fc00000);                  // getValue() of a slot nobody wrote: 0.0f / 0
     // 10-deep slots (ref RealTimeAnalyser.h:73)
-    long long rec10 = p.frames_before + t + 1; if (rec10 > 10) rec10 = 10;
+    long long rec10 = v.frames_before + t + 1; if (rec10 > 10) rec10 = 10;
 #pragma unroll
     for (int s = 0; s < FX_NUM_FEATURES; s++) {
         if (s == FX_ONSET || s == FX_FLUX || s == FX_RMS) continue;
@@ -393,7 +393,7 @@ __device__ __forceinline__ void epilogue_hop(const EpilogueParams& p, int c, int
     v.raw = p.raw + (size_t) c * p.T * FX_NUM_FEATURES;
     v.hist = p.hist + (size_t) c * HLEN * FX_NUM_FEATURES;
     v.T = p.T;
-    v.frames_before = p.frames_before;
+    v.frames_before = track_frames_before(p, c);
     v.hist_base = p.hist_base;
     const int t = 0, s = group_lane<GROUP>(lane);
     const bool spec = p.analysers & 1, harm = p.analysers & 2;
@@ -412,7 +412,7 @@ __device__ __forceinline__ void epilogue_hop(const EpilogueParams& p, int c, int
         } else if (s == FX_RMS) {
             sm = rms_value(v, t, order_mode, 2);
         } else {
-            long long rec10 = p.frames_before + t + 1; if (rec10 > 10) rec10 = 10;
+            long long rec10 = v.frames_before + t + 1; if (rec10 > 10) rec10 = 10;
             const bool harm_slot = s == FX_F0 || s == FX_HER || s == FX_OER || s == FX_INHARM;
             float total = 0.0f;
 #pragma unroll
@@ -458,7 +458,7 @@ fx_epilogue_kernel(const EpilogueParams p_arg)
     // before them.
     {
         RawView v;
-        v.raw = raw; v.hist = hist; v.T = p.T; v.frames_before = p.frames_before; v.hist_base = p.hist_base; v.tile = tile; v.tile_first = first; v.tiled = true;
+        v.raw = raw; v.hist = hist; v.T = p.T; v.frames_before = track_frames_before(p, c); v.hist_base = p.hist_base; v.tile = tile; v.tile_first = first; v.tiled = true;
         const bool both = (p.analysers & 1) && (p.analysers & 2);
         const int order_mode = both ? p.order_mode : FX_ORDER_ISOLATED;
         const int pushes = (order_mode == FX_ORDER_HARMONIC_THEN_SPECTRAL) ? 2 : 1;

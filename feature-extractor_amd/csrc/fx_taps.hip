@@ -286,7 +286,9 @@ std::vector<float> tap_constants(int n)
 struct fx_taps {
     std::vector<int> armed;         // channels waiting for a capture, in the order they were armed
     std::vector<int> captured;      // channels of the latest capture, in slot order
-    long long        frame = -1;    // frame index of the latest capture
+    long long        frame = -1;    // frame index of the latest capture (the context's count)
+    std::vector<long long> first;   // per captured channel: the first frame of its stream then (fx_reset_channels), so that
+                                    // fx_get_taps reports the track's own index
     float*           d_consts = nullptr;    // fxk::tap_constants
     float*           d_store = nullptr;     // [slots][tap_row_floats(N)]
     int              slots = 0;
@@ -351,6 +353,9 @@ fx_status taps_launch(fx_context* c, const fx_tap_source& src)
     t->captured.swap(t->armed);
     t->armed.clear();
     t->frame = c->frames_seen;
+    t->first.assign(t->captured.size(), 0);
+    if (!c->chan.empty())
+        for (size_t i = 0; i < t->captured.size(); i++) t->first[i] = c->chan[(size_t) t->captured[i]].first_frame;
     c->taps_armed = 0;
     return FX_OK;
 }
@@ -401,7 +406,7 @@ fx_status fx_get_taps(fx_context* c, int channel, float* window, float* spectrum
     if (autocorrelation) std::copy(r + 5 * n, r + 6 * n, autocorrelation);
     if (cnd) std::copy(r + 6 * n, r + 7 * n, cnd);
     if (lag_position) std::copy(r + 7 * n, r + 7 * n + 2, lag_position);
-    if (frame_index) *frame_index = t->frame;
+    if (frame_index) *frame_index = t->frame - t->first[(size_t) slot];
     return FX_OK;
 }
 

@@ -36,6 +36,16 @@ def shard_slice(values, num_channels, rank, world_size):
     return a[first:first + count]
 
 
+def shard_channel_list(channels, num_channels, rank, world_size):
+    """This rank's part of a GLOBAL track list (channels of the whole run, for BatchAnalyser.reset_channels / clear_pending_channels /
+    request_taps): the entries that fall in the rank's shard, in the list's order, as indices within the shard (int32; may be empty)."""
+    a = np.asarray(channels if channels is not None else [], dtype=np.int64).ravel()
+    if a.size and (a.min() < 0 or a.max() >= num_channels):
+        raise ValueError("a global track list holds channels in [0,%d)" % num_channels)
+    first, count = my_shard(num_channels, rank, world_size)
+    return (a[(a >= first) & (a < first + count)] - first).astype(np.int32)
+
+
 def set_shard_channel_settings(analyser, num_channels, rank, world_size, gains=None, sensitivity=None, window=None, type=None):
     """Per-track settings given for the whole run, applied to this rank's analyser (its channels are the rank's shard)."""
     if gains is not None:

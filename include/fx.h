@@ -96,7 +96,8 @@ fx_status fx_create(fx_context** out, int device_id, int num_channels,
 fx_status fx_destroy(fx_context* ctx);
 
 /* Zero overlap buffers, flux state and every ValueHistory (a freshly
- * constructed AnalyserTrackController); settings are kept. */
+ * constructed AnalyserTrackController); settings are kept.  Every track's
+ * frame index is 0 again (fx_get_channel_frames). */
 fx_status fx_reset_state(fx_context* ctx);
 
 /* RealTimeAnalyser::sampleRateChanged, RealTimeAnalyser.h:111-114 */
@@ -123,7 +124,7 @@ fx_status fx_set_gain(fx_context* ctx, float gain);
  * context-wide setters above keep their meaning "set it on every track": fx_set_gain(ctx, g) after these leaves every track with g.
  * A bad entry fails the whole call with FX_ERR_INVALID_ARGUMENT (fx_last_error names the track) and changes nothing; a failed
  * upload reports FX_ERR_HIP and leaves the old settings in force.  They synchronise the context's stream.
- * Not per track: clearing the pending samples (tracks would hold different numbers of them -- ragged blocks), the sample rate, the
+ * Not per track: the NUMBER of pending samples (tracks would hold different numbers of them -- ragged blocks), the sample rate, the
  * window size and the analysers' order; those stay one per context. */
 /* AudioDataCollector::setGain per track (AnalyserTrackController.h:126-130).  gain [num_channels]; any float, as fx_set_gain. */
 fx_status fx_set_channel_gains(fx_context* ctx, const float* gain);
@@ -134,6 +135,34 @@ fx_status fx_set_channel_gains(fx_context* ctx, const float* gain);
 fx_status fx_set_channel_onset(fx_context* ctx, const float* sensitivity, const int* window, const int* type);
 /* What each track runs with now ([num_channels] each; any pointer may be NULL): after a context-wide setter, its value on every track. */
 fx_status fx_get_channel_settings(fx_context* ctx, float* gain, float* sensitivity, int* window, int* type);
+
+/* ---- per-track reset and clear: replace one track without touching the rest ----
+ * In the reference tracks are destroyed and built again one object at a time (MainComponent.cpp:137-186), and the transport buttons
+ * and a dropped file call clearBuffer() on THAT track's collectors only (AnalyserTrackController.h:109-112,135-137,167-171).  Both
+ * calls take a list of tracks in host memory (the caller may free or reuse it on return) and follow the same rules:
+ *   - they take effect in stream order for the analysis calls that follow, and they synchronise the context's stream, as the
+ *     per-track setters do.  With a fx_stream_* ring on the context they are therefore ordered after the batches already submitted
+ *     and reach every batch submitted later, the captured one-hop step included.
+ *   - num_channels == 0 is a no-op; duplicates are allowed.  A null context, a null list with num_channels > 0, num_channels < 0 or
+ *     an entry outside [0, num_channels of the context) is FX_ERR_INVALID_ARGUMENT before any device use: fx_last_error names the
+ *     entry, nothing changes.
+ *   - a failed allocation, upload or launch reports FX_ERR_OUT_OF_MEMORY / FX_ERR_HIP.  The tracks NOT listed are untouched in every
+ *     case.  The listed tracks may then be part old, part new, as after a failed analysis launch: repeat the call, or fx_reset_state.
+ *   - a context on which neither was ever called makes exactly the launches it made before and returns the bits it returned before.
+ * A new AnalyserTrackController in these slots: overlap tail, flux state, every ValueHistory, both onset histories and the latest
+ * vector become those of fx_create; the tracks' pending samples become zeros (a new collector's ring).  The pending COUNT stays (it is
+ * one per context).  Settings -- gain, onset settings, channel map -- are kept, as fx_reset_state keeps them.  The tracks' frame index
+ * (fx_get_taps frame_index, fx_onset_event::frame) starts at 0 again.  So a listed track produces, bit for bit, what the same track
+ * of a freshly created context with the same settings produces when that context is first given fx_pending_samples() zeros and then
+ * the same input; every other track produces what it produces in a context where the call was never made.  The first call on a
+ * context without a per-track table creates it with the context-wide values, as the first per-track setter does. */
+fx_status fx_reset_channels(fx_context* ctx, const int* channels, int num_channels);
+/* AudioDataCollector::clearBuffer (AudioDataCollector.h:119,122) on these tracks only: their pending samples become zeros, nothing
+ * else changes (fx_clear_pending is the same for every track). */
+fx_status fx_clear_pending_channels(fx_context* ctx, const int* channels, int num_channels);
+/* Frames each track has analysed since fx_create / fx_reset_state / its last fx_reset_channels; frames [num_channels], host memory.
+ * No device use. */
+fx_status fx_get_channel_frames(fx_context* ctx, long long* frames);
 
 /* Replaces RealTimeAudioDataOverlapper::getNextBuffer (RealTimeAudioAnalysis.h:
  * 205-228) + both run() loops (RealTimeAnalyser.h:141-177, :201-234) for
@@ -262,7 +291,8 @@ fx_status fx_request_taps(fx_context* ctx, const int* channels, int num_channels
  *   autocorrelation [N]   getAutoCorrelationBufferToDraw: v[s] = d[s] * d[s] * s of the inverse transform d of the squared real parts
  *   cnd             [N]   getCumulativeDifferenceBufferToDraw: the cumulative normalised difference of v
  *   lag_position    [2]   getNormalisedLagPosition: (lag / 2N, cnd[lag]), or (-1 / 2N, 100) when no value fell below the threshold
- *   frame_index     which frame of the channel's stream was captured: frames analysed since fx_create / fx_reset_state, 0-based */
+ *   frame_index     which frame of the channel's stream was captured: frames analysed since fx_create / fx_reset_state / the channel's
+ *                   last fx_reset_channels, 0-based */
 fx_status fx_get_taps(fx_context* ctx, int channel, float* window, float* spectrum, float* pitch_spectrum,
                       float* autocorrelation, float* cnd, float* lag_position, long long* frame_index);
 
@@ -273,11 +303,12 @@ fx_status fx_get_taps(fx_context* ctx, int channel, float* window, float* spectr
  *   - an event is exactly raw[FX_ONSET] == 1.0f of a frame analysed by fx_push_hops, fx_process_frames, fx_push_samples or
  *     fx_push_interleaved: the reference's condition, since getValue(enOnset) has history length 1 and so equals the value just
  *     inserted.  A FX_HARMONIC_ONLY context never produces one (the reference never writes its onset slot, and NaN > 0 is false).
- *   - `frame` is the frame's 0-based index in the track's stream since fx_create / fx_reset_state, the count fx_get_taps reports as
- *     frame_index; `call_frame` its index within the call that analysed it; `channel` the track.
- *   - order: events of earlier calls first, within a call by ascending frame, then ascending channel.  The whole list is therefore
- *     sorted by (frame, channel) and can be replayed in time order.  The order is part of the contract: it is a function of the
- *     onset slots alone.
+ *   - `frame` is the frame's 0-based index in the track's OWN stream since fx_create / fx_reset_state / the track's last
+ *     fx_reset_channels, the count fx_get_taps reports as frame_index; `call_frame` its index within the call that analysed it;
+ *     `channel` the track.
+ *   - order: events of earlier calls first, within a call by ascending call_frame, then ascending channel.  While no track was
+ *     reset on its own the whole list is therefore sorted by (frame, channel); it can always be replayed in time order.  The order
+ *     is part of the contract: it is a function of the onset slots alone.
  *   - events beyond `capacity` are not stored and are counted: the stored ones are the earliest.
  *   - the list is made by one extra launch on the context's stream after the call's last analysis launch.  The number of events
  *     stored lives in device memory: an analysis call on an enabled context makes no host wait it does not make otherwise, and

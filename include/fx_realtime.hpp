@@ -143,6 +143,17 @@ public:
     {
         std::vector<int> v = perTrack().type; v[at (track)] = (int) t; setOnsetSettings (nullptr, nullptr, &v);
     }
+    // A new AnalyserTrackController in one slot or several (ref MainComponent.cpp:137-186: tracks are destroyed and built one at a
+    // time): fx_reset_channels.  The tracks' tail, flux state, histories, latest vector and pending samples are a new context's, their
+    // frame index starts at 0 again; settings stay, the other tracks are untouched.
+    void resetTrack (int track)                                { const int t = at (track); resetTracks (&t, 1); }
+    void resetTracks (const int* tracks, int count)            { check (fx_reset_channels (ctx, tracks, count)); }
+    std::vector<long long> trackFrames() const                 // frames each track has analysed since it was created or last reset
+    {
+        std::vector<long long> f ((std::size_t) channels);
+        check (fx_get_channel_frames (ctx, f.data()));
+        return f;
+    }
     // array forms, one entry per track; a null vector leaves that setting alone, a window entry < 0 leaves that track's window and
     // histories alone
     void setGains (const std::vector<float>& gains)
@@ -372,6 +383,7 @@ public:
     }
     void setGain (float g)       { analyser.setGain (g); }                                          // ref :124
     void clearBuffer()           { check (fx_clear_pending (analyser.handle())); }                  // ref :122
+    void clearBuffer (int track) { check (fx_clear_pending_channels (analyser.handle(), &track, 1)); }   // one track's collector (AnalyserTrackController.h:135-137)
     int  getNumPendingSamples()  { return fx_pending_samples (analyser.handle()); }
     int  getNumFrames() const    { return lastFrames; }
     const float* raw() const      { return rawValues.data(); }        // [channel][getNumFrames()][12] of the last block
@@ -802,6 +814,19 @@ public:
     {
         { std::lock_guard<std::mutex> g (wake); commands.push_back (std::move (f)); }
         ready.notify_one();
+    }
+
+    // A track handed to a new source while the engine runs (RealTimeBatchAnalyser::resetTracks): queued like any other command, so the
+    // worker makes the call between two blocks and the audio thread is never involved.  The list is copied.
+    void resetTracks (const int* tracks, int count)
+    {
+        // refused here as fx_reset_channels refuses them, on the caller's thread: a bad count, a null list, a track out of range
+        if (count < 0 || (count > 0 && tracks == nullptr)) throw Error (FX_ERR_INVALID_ARGUMENT, "bad track list");
+        for (int i = 0; i < count; ++i)
+            if (tracks[i] < 0 || tracks[i] >= analyser.getNumChannels()) throw Error (FX_ERR_INVALID_ARGUMENT, "no such track");
+        if (count == 0) return;
+        std::vector<int> list (tracks, tracks + count);
+        callOnWorker ([list] (RealTimeBatchAnalyser& a) { a.resetTracks (list.data(), (int) list.size()); });
     }
 
     // wait until everything pushed so far has been analysed and published (not for the audio thread)
