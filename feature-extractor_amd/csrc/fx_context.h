@@ -1,4 +1,5 @@
-// fx_context.h -- the context behind the C ABI (include/fx.h), shared by fx_capi.cpp and fx_comm.cpp.  Internal.
+// fx_context.h -- the context behind the C ABI (include/fx.h), shared by the shim's host units (fx_capi.cpp, fx_plan.cpp, fx_stream.cpp,
+// fx_comm.cpp) and the units that attach through its hooks (fx_taps.hip, fx_interleave.hip, fx_events.hip, fx_tracks.hip).  Internal.
 #ifndef FX_CONTEXT_H
 #define FX_CONTEXT_H
 
@@ -18,6 +19,23 @@ fx_status fx_fail(fx_status code, const char* fmt, ...) __attribute__((format(pr
             return fx_fail(e_ == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP,       \
                            "%s failed: %s", #expr, hipGetErrorString(e_));                     \
     } while (0)
+
+inline bool known_format(int f) { return f == FX_SAMPLE_F32 || f == FX_SAMPLE_F16 || f == FX_SAMPLE_S16 || f == FX_SAMPLE_S24; }
+inline size_t sample_size(int f) { return f == FX_SAMPLE_F32 ? 4 : (f == FX_SAMPLE_S24 ? 3 : 2); }
+// A call's sample format and the memory kinds of its input and results (an entry point passes what it has): FX_ERR_INVALID_ARGUMENT
+// for an unknown one, the format's refusal first.
+fx_status fx_check_call(int sample_format, int in_kind = FX_MEM_HOST, int out_kind = FX_MEM_HOST);
+
+// Scratch that follows the largest call seen (fx_capi.cpp): *ptr holds at least `need` bytes afterwards, or is null (capacity 0) with
+// FX_ERR_OUT_OF_MEMORY / FX_ERR_HIP.  What the buffer held is not kept.
+fx_status fx_grow(void** ptr, size_t* cap, size_t need);
+template <typename T> fx_status fx_grow(T** ptr, size_t* cap, size_t need)
+{
+    void* p = *ptr;
+    const fx_status st = fx_grow(&p, cap, need);
+    *ptr = static_cast<T*>(p);
+    return st;
+}
 
 struct fx_comm;     // fx_comm.cpp
 void fx_comm_release(fx_context* ctx);   // called by fx_destroy

@@ -16,7 +16,7 @@
 // therefore a function of the flags alone, never of which workgroup ran when.  The stored / dropped counts live in device memory and
 // only this kernel's last workgroup (and a drain, which synchronises) writes them: no host wait per call.
 //
-// Nothing in fx_capi.cpp refers to this unit: fx_enable_onset_events installs the context's three hooks (fx_context.h).
+// Nothing in the shim's host units (build.py, HOST_SOURCES) refers to this unit: fx_enable_onset_events installs the context's three hooks (fx_context.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -212,17 +212,8 @@ fx_status events_launch(fx_context* c, const float* d_raw, int T, long long fram
     const long long wgs = (groups + fxk::EV_GROUPS_PER_WG - 1) / fxk::EV_GROUPS_PER_WG;
     if (wgs > 0x7fffffffll) return fx_fail(FX_ERR_INVALID_ARGUMENT, "call of %d frames x %d channels is too long for the onset event list", T, c->C);
     const size_t need = (size_t) groups * sizeof(unsigned long long);
-    if (need > e->masks_cap) {
-        // (forgotten before it is freed, as fx_capi.cpp's grow(); hipFree waits for the launches that read the old table)
-        unsigned long long* old = e->d_masks;
-        e->d_masks = nullptr;
-        e->masks_cap = 0;
-        if (old) HIP_TRY(hipFree(old));
-        void* q = nullptr;
-        HIP_TRY(hipMalloc(&q, need));
-        e->d_masks = static_cast<unsigned long long*>(q);
-        e->masks_cap = need;
-    }
+    // (growing frees the old table: hipFree waits for the launches that read it)
+    { const fx_status st = fx_grow(&e->d_masks, &e->masks_cap, need); if (st != FX_OK) return st; }
     fxk::EventsParams p;
     p.raw = d_raw;
     p.masks = e->d_masks;

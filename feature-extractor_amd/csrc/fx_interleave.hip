@@ -8,7 +8,7 @@
 // the rest: the same launches, the same bits as fx_push_samples of that planar block.  Bytes only: no conversion, no gain (the
 // analysis kernels' load stage does both).
 //
-// Nothing in fx_capi.cpp refers to this unit: the first fx_set_channel_map / fx_push_interleaved installs the context's release hook.
+// Nothing in the shim's host units (build.py, HOST_SOURCES) refers to this unit: the first fx_set_channel_map / fx_push_interleaved installs the context's release hook.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -151,9 +151,6 @@ struct fx_interleave {
 
 namespace {
 
-bool known_format(int f) { return f == FX_SAMPLE_F32 || f == FX_SAMPLE_F16 || f == FX_SAMPLE_S16 || f == FX_SAMPLE_S24; }
-int sample_size(int f) { return f == FX_SAMPLE_F32 ? 4 : (f == FX_SAMPLE_S24 ? 3 : 2); }
-
 void interleave_release(fx_context* c)
 {
     fx_interleave* s = c->interleave;
@@ -186,26 +183,6 @@ fx_status interleave_state(fx_context* c, fx_interleave** out)
         c->interleave_release = interleave_release;
     }
     *out = c->interleave;
-    return FX_OK;
-}
-
-// scratch that follows the largest block seen (fx_capi.cpp grow(): forgotten before it is freed, grows by half again at least)
-fx_status grow_bytes(unsigned char** ptr, size_t* cap, size_t need)
-{
-    if (need <= *cap) return FX_OK;
-    size_t want = *ptr && need < *cap + *cap / 2 ? *cap + *cap / 2 : need;
-    if (*ptr) {
-        unsigned char* old = *ptr;
-        *ptr = nullptr;
-        *cap = 0;
-        HIP_TRY(hipFree(old));
-    }
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, want);
-    if (e != hipSuccess && want != need) { (void) hipGetLastError(); want = need; e = hipMalloc(&q, want); }
-    if (e != hipSuccess) return fx_fail(e == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e));
-    *ptr = static_cast<unsigned char*>(q);
-    *cap = want;
     return FX_OK;
 }
 
@@ -247,8 +224,7 @@ fx_status fx_push_interleaved(fx_context* c, const void* samples, int num_sample
     c->num_launches = 0;
     if (num_samples < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative sample count");
     if (num_source_channels < 1) return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d source channels: a frame holds at least one", num_source_channels);
-    if (!known_format(sample_format)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown sample format %d", sample_format);
-    if (mem_kind != FX_MEM_HOST && mem_kind != FX_MEM_DEVICE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", mem_kind);
+    { const fx_status cs = fx_check_call(sample_format, mem_kind, mem_kind); if (cs != FX_OK) return cs; }
     if (num_samples == 0) return FX_OK;
     if (!samples) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null input buffer");
     if (mem_kind == FX_MEM_DEVICE && reinterpret_cast<uintptr_t>(samples) % 4 != 0)
@@ -264,16 +240,16 @@ fx_status fx_push_interleaved(fx_context* c, const void* samples, int num_sample
     fx_interleave* s = nullptr;
     fx_status st;
     if ((st = interleave_state(c, &s)) != FX_OK) return st;
-    const int esz = sample_size(sample_format);
+    const int esz = (int) sample_size(sample_format);
     const size_t in_bytes = (size_t) num_samples * (size_t) num_source_channels * (size_t) esz;
     const size_t planar_bytes = (size_t) c->C * (size_t) num_samples * (size_t) esz;
     const unsigned char* d_in = static_cast<const unsigned char*>(samples);
     if (mem_kind == FX_MEM_HOST) {
-        if ((st = grow_bytes(&s->d_src, &s->src_cap, in_bytes)) != FX_OK) return st;
+        if ((st = fx_grow(&s->d_src, &s->src_cap, in_bytes)) != FX_OK) return st;
         HIP_TRY(hipMemcpyAsync(s->d_src, samples, in_bytes, hipMemcpyHostToDevice, c->stream));
         d_in = s->d_src;
     }
-    if ((st = grow_bytes(&s->d_planar, &s->planar_cap, planar_bytes)) != FX_OK) return st;
+    if ((st = fx_grow(&s->d_planar, &s->planar_cap, planar_bytes)) != FX_OK) return st;
     fxk::DeinterleaveParams p;
     p.in = d_in;
     p.map = s->d_map;

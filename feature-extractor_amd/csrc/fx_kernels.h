@@ -1,4 +1,4 @@
-// fx_kernels.h -- launch interface between the C-ABI shim (fx_capi.cpp) and the gfx950 kernels.
+// fx_kernels.h -- launch interface between the C-ABI shim (fx_capi.cpp, fx_plan.cpp, fx_stream.cpp) and the gfx950 kernels.
 #ifndef FX_KERNELS_H
 #define FX_KERNELS_H
 

@@ -303,21 +303,11 @@ __global__ void __launch_bounds__(NT) harmonic_characteristics_kernel(const floa
 
 size_t harmonic_lds_bytes(int num_bins) { return 4 * (size_t) (num_bins + (num_bins & 1)) * sizeof(float); }
 
-fx_status grow_bytes(void** ptr, size_t* cap, size_t need)
-{
-    if (need <= *cap) return FX_OK;
-    if (*ptr) HIP_TRY(hipFree(*ptr));
-    *ptr = nullptr; *cap = 0;
-    HIP_TRY(hipMalloc(ptr, need));
-    *cap = need;
-    return FX_OK;
-}
-
 // input(s) on the device: the caller's pointers, or a staged copy of host buffers (two inputs back to back)
 fx_status stage_in(fx_offline* o, int mem_kind, const void* a, size_t a_bytes, const void* b, size_t b_bytes, const void** da, const void** db)
 {
     if (mem_kind == FX_MEM_DEVICE) { *da = a; *db = b; return FX_OK; }
-    fx_status st = grow_bytes(&o->d_in, &o->in_cap, a_bytes + b_bytes);
+    fx_status st = fx_grow(&o->d_in, &o->in_cap, a_bytes + b_bytes);
     if (st != FX_OK) return st;
     HIP_TRY(hipMemcpyAsync(o->d_in, a, a_bytes, hipMemcpyHostToDevice, o->stream));
     *da = o->d_in;
@@ -561,7 +551,7 @@ fx_status fx_offline_zero_crosses(fx_offline* o, const float* audio, int num_sam
     const void *da, *db;
     if ((st = stage_in(o, mem_kind, audio, in_bytes, nullptr, 0, &da, &db)) != FX_OK) return st;
     float* d_out = out;
-    if (mem_kind == FX_MEM_HOST) { if ((st = grow_bytes(&o->d_out, &o->out_cap, out_bytes)) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
+    if (mem_kind == FX_MEM_HOST) { if ((st = fx_grow(&o->d_out, &o->out_cap, out_bytes)) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
     hipLaunchKernelGGL(zero_crosses_kernel, dim3((unsigned) (o->C * num_downsamples)), dim3(NT), 0, o->stream, static_cast<const float*>(da), num_samples, num_downsamples, d_out);
     HIP_TRY(hipGetLastError());
     if (mem_kind == FX_MEM_HOST) { HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, o->stream)); HIP_TRY(hipStreamSynchronize(o->stream)); }
@@ -577,7 +567,7 @@ fx_status fx_offline_log_attack_time(fx_offline* o, const float* envelope, int n
     const void *da, *db;
     if ((st = stage_in(o, mem_kind, envelope, sizeof(float) * (size_t) n, nullptr, 0, &da, &db)) != FX_OK) return st;
     float* d_out = out;
-    if (mem_kind == FX_MEM_HOST) { if ((st = grow_bytes(&o->d_out, &o->out_cap, sizeof(float))) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
+    if (mem_kind == FX_MEM_HOST) { if ((st = fx_grow(&o->d_out, &o->out_cap, sizeof(float))) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
     hipLaunchKernelGGL(log_attack_time_kernel, dim3(1), dim3(NT), 0, o->stream, static_cast<const float*>(da), n, num_input_samples, num_downsamples, sample_rate, d_out);
     HIP_TRY(hipGetLastError());
     if (mem_kind == FX_MEM_HOST) { HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(float), hipMemcpyDeviceToHost, o->stream)); HIP_TRY(hipStreamSynchronize(o->stream)); }
@@ -596,7 +586,7 @@ fx_status fx_offline_fft_lbp(fx_offline* o, const float* cur, const float* prev,
     unsigned char* d_bits = bits; float* d_hi = highest_ratio; float* d_act = activity_ratio;
     const size_t bits_bytes = (size_t) o->C * num_bins, bits_pad = (bits_bytes + 15) & ~(size_t) 15;
     if (mem_kind == FX_MEM_HOST) {
-        if ((st = grow_bytes(&o->d_out, &o->out_cap, bits_pad + 2 * sizeof(float) * (size_t) o->C)) != FX_OK) return st;
+        if ((st = fx_grow(&o->d_out, &o->out_cap, bits_pad + 2 * sizeof(float) * (size_t) o->C)) != FX_OK) return st;
         d_bits = static_cast<unsigned char*>(o->d_out);
         d_hi = reinterpret_cast<float*>(d_bits + bits_pad);
         d_act = d_hi + o->C;
@@ -621,7 +611,7 @@ fx_status fx_offline_harmonic_characteristics(fx_offline* o, const float* magnit
     const void *da, *db;
     if ((st = stage_in(o, mem_kind, magnitudes, in_bytes, nullptr, 0, &da, &db)) != FX_OK) return st;
     float* d_out = out3;
-    if (mem_kind == FX_MEM_HOST) { if ((st = grow_bytes(&o->d_out, &o->out_cap, out_bytes)) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
+    if (mem_kind == FX_MEM_HOST) { if ((st = fx_grow(&o->d_out, &o->out_cap, out_bytes)) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
     hipLaunchKernelGGL(harmonic_characteristics_kernel, dim3((unsigned) o->C), dim3(NT), harmonic_lds_bytes(num_bins), o->stream,
                        static_cast<const float*>(da), num_bins, o->nyquist, o->d_prev_f0, d_out);
     HIP_TRY(hipGetLastError());
@@ -646,7 +636,7 @@ fx_status fx_offline_spectral_characteristics(fx_offline* o, const float* magnit
     const void *da, *db;
     if ((st = stage_in(o, mem_kind, magnitudes, in_bytes, nullptr, 0, &da, &db)) != FX_OK) return st;
     float* d_out = out4;
-    if (mem_kind == FX_MEM_HOST) { if ((st = grow_bytes(&o->d_out, &o->out_cap, out_bytes)) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
+    if (mem_kind == FX_MEM_HOST) { if ((st = fx_grow(&o->d_out, &o->out_cap, out_bytes)) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
     hipLaunchKernelGGL(spectral_characteristics_kernel, dim3((unsigned) o->C), dim3(NT), SPECTRAL_LDS_PER_BIN * (size_t) num_bins, o->stream,
                        static_cast<const float*>(da), num_bins, o->nyquist, o->d_prev_bins, d_out);
     HIP_TRY(hipGetLastError());
@@ -673,7 +663,7 @@ fx_status fx_offline_spectral_slope(fx_offline* o, const float* magnitudes, int 
     const void *da, *db;
     if ((st = stage_in(o, mem_kind, magnitudes, in_bytes, nullptr, 0, &da, &db)) != FX_OK) return st;
     float* d_out = out;
-    if (mem_kind == FX_MEM_HOST) { if ((st = grow_bytes(&o->d_out, &o->out_cap, out_bytes)) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
+    if (mem_kind == FX_MEM_HOST) { if ((st = fx_grow(&o->d_out, &o->out_cap, out_bytes)) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
     hipLaunchKernelGGL(spectral_slope_kernel, dim3((unsigned) o->C), dim3(NT), SLOPE_LDS_PER_BIN * (size_t) num_bins, o->stream, static_cast<const float*>(da), num_bins, d_out);
     HIP_TRY(hipGetLastError());
     if (mem_kind == FX_MEM_HOST) { HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, o->stream)); HIP_TRY(hipStreamSynchronize(o->stream)); }
@@ -691,7 +681,7 @@ fx_status fx_offline_auto_correlation(fx_offline* o, float* data, int num_items,
     float* d_data = const_cast<float*>(static_cast<const float*>(da));
     int* d_peak = peak_bin; double* d_freq = frequency;
     if (mem_kind == FX_MEM_HOST) {
-        if ((st = grow_bytes(&o->d_out, &o->out_cap, (sizeof(double) + sizeof(double)) * (size_t) o->C)) != FX_OK) return st;
+        if ((st = fx_grow(&o->d_out, &o->out_cap, (sizeof(double) + sizeof(double)) * (size_t) o->C)) != FX_OK) return st;
         d_freq = static_cast<double*>(o->d_out);
         d_peak = reinterpret_cast<int*>(d_freq + o->C);
     }

@@ -10,7 +10,7 @@
 // multiply-add) one butterfly per thread and level through LDS, and the serial parts (the low-pass, the fp32 running sum, the lag walk)
 // on one lane.  Off the hot path: clarity before speed.
 //
-// Nothing in fx_capi.cpp refers to this unit: fx_request_taps installs the context's two hooks (fx_context.h), and the analysis entry
+// Nothing in the shim's host units (build.py, HOST_SOURCES) refers to this unit: fx_request_taps installs the context's two hooks (fx_context.h), and the analysis entry
 // points call them only when channels are armed.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>

@@ -11,7 +11,7 @@
 // fx_reset_channels_kernel zeroes the listed tracks' rows of the flux state, of the window tail and of the pending samples the next
 // call reads, and of the latest vector; fx_clear_pending_channels is the same launch with the pending rows alone.
 //
-// Nothing in fx_capi.cpp refers to this unit: the first call installs the context's release hook (fx_context.h).  The kernel is
+// Nothing in the shim's host units (build.py, HOST_SOURCES) refers to this unit: the first call installs the context's release hook (fx_context.h).  The kernel is
 // compiled by hipcc only; a host-only build of this file (tests/cpp/track_reset_host.cpp) brings its own launch_reset_channels_kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -110,7 +110,7 @@ fx_status reserve_list(fx_context* c, size_t n)
     }
     fx_tracks* t = c->tracks;
     if (n <= t->cap) return FX_OK;
-    // grows by at least half again, as fx_capi.cpp's grow(): a host whose lists get longer does not pay a free (it waits for the device)
+    // grows by at least half again, as fx_grow() (fx_context.h): a host whose lists get longer does not pay a free (it waits for the device)
     // and a pinned allocation per call.  The new pair is allocated first, so a failed allocation leaves the old lists in place.
     size_t want = n;
     if (want < t->cap + t->cap / 2) want = t->cap + t->cap / 2;

@@ -1,5 +1,5 @@
 // A FAKE hip_runtime.h for sanitizer builds of the host shim on the CPU (tests/test_host_sanitized_cpu.py): the types, constants and
-// entry points fx_capi.cpp / fx_comm.cpp use, backed by malloc in fake_hip.cpp, every call countable and failable on demand.
+// entry points the shim's host units (fx_capi.cpp, fx_plan.cpp, fx_stream.cpp, fx_comm.cpp) use, backed by malloc in fake_hip.cpp, every call countable and failable on demand.
 // Nothing here is HIP and nothing here ships: the product is built against the real runtime by feature-extractor_amd/build.py.
 #ifndef FX_FAKE_HIP_RUNTIME_H
 #define FX_FAKE_HIP_RUNTIME_H

@@ -1,4 +1,4 @@
-// host_sanitize.cpp -- the host shim (csrc/fx_capi.cpp, csrc/fx_comm.cpp: ring, captured steps, fill pool, re-blocking plumbing, RCCL
+// host_sanitize.cpp -- the host shim (csrc/fx_capi.cpp, fx_plan.cpp, fx_stream.cpp, fx_comm.cpp: ring, captured steps, fill pool, re-blocking plumbing, RCCL
 // gather) built for the CPU against the fake runtime of tests/cpp/fake_hip/ with -fsanitize=address,undefined (and, as a second
 // binary, -fsanitize=thread), then walked through every HIP call site with an injected failure.
 //
@@ -159,6 +159,10 @@ bool scenario_batch(World& w)
     STEP(fx_set_onset_window(w.ctx, 9));
     STEP(fx_set_gain(w.ctx, 0.5f));
     STEP(fx_sync(w.ctx));
+    // every track's OSC message to host memory: the staging buffer is allocated, then grows with the stride
+    std::vector<unsigned char> grams((size_t) 8 * 96);
+    int lengths[8];
+    for (int stride : {80, 96}) STEP(fx_get_osc_datagrams(w.ctx, "/t", 0, grams.data(), stride, lengths, FX_MEM_HOST));
     return true;
 }
 

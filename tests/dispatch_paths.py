@@ -1,7 +1,7 @@
 """The table of analysis dispatch paths: each row is an entry point, a configuration and the launch sequence the library must make
-for it (fx_last_launches_internal, BatchAnalyser.last_launches()).  The rows are derived from csrc/fx_capi.cpp -- plan_call (workgroup
-shape, work units, hop kernel, one launch or two, two-hop calls as one-frame launches, the ring's fixed routes), fx_push_samples (block
-feed or re-blocking) and fx_stream_submit (hop kernel, captured step or the three-queue path) -- and from the launchers of csrc/fx_kernels.hip, fx_hop_kernel.hip.h
+for it (fx_last_launches_internal, BatchAnalyser.last_launches()).  The rows are derived from csrc/fx_plan.cpp -- plan_call (workgroup
+shape, work units, hop kernel, one launch or two, two-hop calls as one-frame launches, the ring's fixed routes), csrc/fx_capi.cpp -- fx_push_samples (block
+feed or re-blocking) -- and csrc/fx_stream.cpp -- fx_stream_submit (hop kernel, captured step or the three-queue path) -- and from the launchers of csrc/fx_kernels.hip, fx_hop_kernel.hip.h
 and fx_reblock.hip.  The union of the rows covers every launch form those files build, at every window size where it exists
 (tests/test_dispatch_cpu.py holds it to that); tests/test_gpu_dispatch.py runs every row on the device.
 
@@ -220,8 +220,8 @@ ROWS += [
         rule="ring, captured step without the hop kernel"),
     row("ring-graph-256", 256, "ring", 1, 50, {1: [frame(256, 1, 5, 1, direct=1), epi(256, 1)]}, rule="ring, captured step (no hop kernel at 256)"),
     row("ring-graph-4-512", 512, "ring", 4, 13, {4: [frame(512, 4, 1, 4), epi(512, 4)]}, rule="ring, captured step of four hops"),
-    # the three-queue path (no capture): the step run() makes
-    row("ring-queues-hop-2048", 2048, "ring", 1, 50, {1: [hop(2048)]}, tuning={"stream_graph": 0}, rule="ring, no capture: run()'s hop kernel"),
+    # the three-queue path (no capture): the step fx_run() makes
+    row("ring-queues-hop-2048", 2048, "ring", 1, 50, {1: [hop(2048)]}, tuning={"stream_graph": 0}, rule="ring, no capture: fx_run()'s hop kernel"),
     row("ring-queues-1024", 1024, "ring", 1, 50, {1: [frame_tail(1024, 5)]}, tuning={"stream_graph": 0, "one_hop_kernel": 0},
         rule="ring, no capture, no hop kernel"),
     row("ring-queues-12-2048", 2048, "ring", 12, 5, {12: [frame(2048, 12, 1, 4), epi(2048, 12)]}, tuning={"stream_graph": 0},

@@ -1,4 +1,4 @@
-"""Per-track settings without a GPU: the entries are declared, exported and bound; their host code (csrc/fx_capi.cpp) validates
+"""Per-track settings without a GPU: the entries are declared, exported and bound; their host code (csrc/fx_capi.cpp, built with the rest of build.HOST_SOURCES) validates
 arguments before any device use -- a null context, a bad entry names its track and changes nothing -- and, built against
 tests/cpp/fake_hip/ under ASan + UBSan with every HIP call failed once (tests/cpp/channel_settings_host.cpp), a failed table upload
 leaves the old settings in force and reports FX_ERR_HIP; sharded.py cuts a global per-track array by the shard's channel range."""
@@ -53,10 +53,12 @@ def test_python_wrappers_check_the_array_length(fx):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not installed")
 def test_host_code_sanitized_with_every_hip_call_failed_once(tmp_path):
+    from importlib import import_module
+    build = import_module("feature-extractor_amd.build")
     exe = str(tmp_path / "channel_settings_host")
     cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
            "-I", FAKE, "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-           os.path.join(CSRC, "fx_capi.cpp"), os.path.join(CSRC, "fx_comm.cpp"), os.path.join(FAKE, "fake_hip.cpp"),
+           *[os.path.join(CSRC, s) for s in build.HOST_SOURCES], os.path.join(FAKE, "fake_hip.cpp"),
            os.path.join(ROOT, "tests", "cpp", "channel_settings_host.cpp"), "-o", exe, "-ldl", "-lpthread"]
     p = subprocess.run(cmd, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -1,12 +1,12 @@
 """The host shim under sanitizers, with every HIP call site failed once (CPU build only: GPU sanitizers are not available).
 
-csrc/fx_capi.cpp and csrc/fx_comm.cpp -- ring slots, captured steps, the fill pool's threads, the re-blocking plumbing of fx_push_samples,
+The shim's host units (build.py, HOST_SOURCES: csrc/fx_capi.cpp, fx_plan.cpp, fx_stream.cpp, fx_comm.cpp, fx_osc_sender.cpp) -- ring slots, captured steps, the fill pool's threads, the re-blocking plumbing of fx_push_samples,
 the RCCL gather -- are compiled UNCHANGED for the host against tests/cpp/fake_hip/ (a malloc-backed hip_runtime.h whose every call can be
 made to fail, launch stubs for csrc/fx_kernels.h, a librccl.so.1 whose ranks are processes that meet in POSIX shared memory) with -fsanitize=address,undefined, and tests/cpp/host_sanitize.cpp
 walks six scenarios once per HIP call with that call failing: no crash, no overrun, no leak, no wedged ring, the next call works; a seventh checks
 fx_push_samples' arithmetic on the host (random block lengths x formats x windows: the hops handed to the kernels, put end to end, are the stream).  A second
 build with -fsanitize=thread runs the fill pool (1 .. 64 threads, resized up and down, jobs back to back).
-What this found when it was written (round 5): grow() freed a scratch buffer twice when hipFree itself reported a failure.
+What this found when it was written (round 5): grow() (now fx_grow) freed a scratch buffer twice when hipFree itself reported a failure.
 
 Round 6: the world > 1 branches of csrc/fx_comm.cpp -- the exchange of channel counts, the per-source receive offsets, ranks that are not the
 sink, the double-buffered staging -- run here for the first time anywhere: tests/cpp/comm_ranks.cpp forks 2 / 4 / 8 rank processes (fake HIP,
@@ -14,6 +14,7 @@ fake RCCL, ASan + UBSan) with ragged shards, sinks other than rank 0, host and d
 then every RCCL call and every HIP call of a sink and of a non-sink rank is failed once: no hang, no crash, no leak, the context analyses
 again.  What this cannot show is xGMI: the transport is memcpy."""
 import glob
+import importlib
 import os
 import shutil
 import subprocess
@@ -24,6 +25,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "feature-extractor_amd", "csrc")
 FAKE = os.path.join(ROOT, "tests", "cpp", "fake_hip")
 
+
+def _host_sources(comm_source=None):
+    """the shim's host units, from the build's own list; comm_source: a file that stands in for fx_comm.cpp"""
+    build = importlib.import_module("feature-extractor_amd.build")
+    assert "fx_comm.cpp" in build.HOST_SOURCES
+    return [comm_source if comm_source and s == "fx_comm.cpp" else os.path.join(CSRC, s) for s in build.HOST_SOURCES]
+
+
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not installed")
 
 
@@ -31,7 +40,7 @@ def _build(tmp, sanitizer, exe):
     out = os.path.join(tmp, exe)
     cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=" + sanitizer, "-fno-omit-frame-pointer", "-Wno-tsan",
            "-I", FAKE, "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-           os.path.join(CSRC, "fx_capi.cpp"), os.path.join(CSRC, "fx_comm.cpp"), os.path.join(CSRC, "fx_osc_sender.cpp"), os.path.join(FAKE, "fake_hip.cpp"),
+           *_host_sources(), os.path.join(FAKE, "fake_hip.cpp"),
            os.path.join(ROOT, "tests", "cpp", "host_sanitize.cpp"), "-o", out, "-ldl", "-lpthread"]
     p = subprocess.run(cmd, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -49,7 +58,7 @@ def _build_comm_ranks(tmp, comm_source=None):
     out = os.path.join(tmp, "comm_ranks_asan")
     cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-rdynamic",
            "-I", FAKE, "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-           os.path.join(CSRC, "fx_capi.cpp"), comm_source or os.path.join(CSRC, "fx_comm.cpp"), os.path.join(FAKE, "fake_hip.cpp"),
+           *_host_sources(comm_source), os.path.join(FAKE, "fake_hip.cpp"),
            os.path.join(ROOT, "tests", "cpp", "comm_ranks.cpp"), "-o", out, "-ldl", "-lpthread"]
     p = subprocess.run(cmd, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -89,6 +98,16 @@ def _run(exe, mode, lib_dir, extra_env=None):
     env["TSAN_OPTIONS"] = "halt_on_error=1"
     env.update(extra_env or {})
     return subprocess.run([exe, mode], capture_output=True, text=True, env=env, timeout=900)
+
+
+def test_the_ring_depends_on_the_planner_and_not_the_other_way_round():
+    """csrc/fx_stream.cpp uses the planner (fx_plan.h) and the context; the entry points and the planner name nothing of the ring (the
+    public fx_stream_* prototypes come from include/fx.h)"""
+    for source in ("fx_capi.cpp", "fx_plan.cpp"):
+        text = open(os.path.join(CSRC, source)).read()
+        for name in ("fx_stream", "FillPool", "SlotGuard", "submit_large"):
+            assert name not in text, (source, name)
+    assert '#include "fx_plan.h"' in open(os.path.join(CSRC, "fx_stream.cpp")).read()
 
 
 def test_every_hip_call_site_failed_once_under_asan_and_ubsan(tmp_path, fake_rccl):

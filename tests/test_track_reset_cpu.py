@@ -1,6 +1,6 @@
 """Per-track reset and clear without a GPU: the three entries are declared, exported and bound and the ABI number stays; the Python
 and C++ names exist; lists are refused before any device use with the entry named; the host code (csrc/fx_tracks.hip compiled as C++
-with its kernel left out, csrc/fx_capi.cpp) built against tests/cpp/fake_hip/ under ASan + UBSan with every HIP call failed once
+with its kernel left out, the shim's host units of build.HOST_SOURCES) built against tests/cpp/fake_hip/ under ASan + UBSan with every HIP call failed once
 (tests/cpp/track_reset_host.cpp) keeps the unlisted tracks' rows through every failure; the unit is part of the gfx950 build and
 the source tree holds none of the scalar-store instructions the kernels must not use."""
 import ctypes
@@ -80,10 +80,11 @@ def test_sharded_cuts_a_global_track_list_to_local_indices(fx):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not installed")
 def test_host_code_sanitized_with_every_hip_call_failed_once(tmp_path):
+    build = __import__("importlib").import_module("feature-extractor_amd.build")
     exe = str(tmp_path / "track_reset_host")
     cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
            "-I", FAKE, "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-           os.path.join(CSRC, "fx_capi.cpp"), os.path.join(CSRC, "fx_comm.cpp"), os.path.join(FAKE, "fake_hip.cpp"),
+           *[os.path.join(CSRC, s) for s in build.HOST_SOURCES], os.path.join(FAKE, "fake_hip.cpp"),
            "-x", "c++", os.path.join(CSRC, "fx_tracks.hip"), "-x", "none",
            os.path.join(ROOT, "tests", "cpp", "track_reset_host.cpp"), "-o", exe, "-ldl", "-lpthread"]
     p = subprocess.run(cmd, capture_output=True, text=True)
@@ -100,9 +101,10 @@ def test_the_unit_is_built_for_gfx950_and_capi_names_no_symbol_of_it(fx):
     fx.load_library()
     blob = open(fx.library_path(), "rb").read()
     assert b"fx_reset_channels_kernel" in blob and b"gfx950" in blob
-    capi_src = open(os.path.join(CSRC, "fx_capi.cpp")).read()
-    for name in ENTRIES + ("launch_reset_channels_kernel", "ResetParams"):
-        assert name not in capi_src, name
+    for source in build.HOST_SOURCES:
+        text = open(os.path.join(CSRC, source)).read()
+        for name in ENTRIES + ("launch_reset_channels_kernel", "ResetParams"):
+            assert name not in text, (source, name)
 
 
 def test_no_scalar_store_instruction_in_the_source_tree():

@@ -70,7 +70,7 @@ def kernels_of(library=None):
 
 def table(kernels):
     lines = ["kernel resources of feature-extractor_amd/lib/libfx_hip.so as built (tools/kernel_resources.py; gfx950 code objects' metadata)",
-             "static LDS only: the frame / pair / hop kernels take their LDS dynamically (FrameLds<N>::bytes, fx_capi.cpp picks the shape)", "",
+             "static LDS only: the frame / pair / hop kernels take their LDS dynamically (FrameLds<N>::bytes, fx_plan.cpp picks the shape)", "",
              "%-72s %5s %5s %5s %8s %8s %8s" % ("kernel", "VGPR", "AGPR", "SGPR", "scratch", "LDS", "threads")]
     for k in kernels:
         lines.append("%-72s %5d %5d %5d %7dB %7dB %8d" % (k["pretty"][:72], k["vgpr"], k.get("agpr", 0), k.get("sgpr", 0), k.get("scratch", 0),
