@@ -188,7 +188,7 @@ class BatchAnalyser:
 
     def last_launches(self):
         """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
-        (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events)."""
+        (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events, osc_table)."""
         fn = self._lib.fx_last_launches_internal
         fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int], ctypes.c_int
         cap = capi.LAUNCH_RECORD_CAP
@@ -542,9 +542,32 @@ class BatchAnalyser:
         capi.check(self._lib.fx_get_smoothed(self._h, out.ctypes.data_as(ctypes.c_void_p), capi.MEM_HOST))
         return out
 
-    def osc_datagrams(self, prefix="/Audio/A", first_channel=0, stride=None):
+    def set_osc_addresses(self, addresses):
+        """fx_set_osc_addresses: every track's own OSC address (the reference's per-track bundleAddress, AnalyserTrackController.h:17,146),
+        one str / bytes per track, or None to drop the table.  A setting: resets keep it.  Synchronises the context's stream."""
+        if addresses is None:
+            capi.check(self._lib.fx_set_osc_addresses(self._h, None))
+            return
+        addresses = list(addresses)
+        if len(addresses) != self.num_channels:
+            raise ValueError("one OSC address per track (%d), not %d" % (self.num_channels, len(addresses)))
+        capi.check(self._lib.fx_set_osc_addresses(self._h, capi.c_strings(addresses)))
+
+    def osc_address_stride(self):
+        """fx_osc_address_stride: the longest message of the address table, or -1 without one"""
+        return self._lib.fx_osc_address_stride(self._h)
+
+    def osc_datagrams(self, prefix="/Audio/A", first_channel=0, stride=None, addressed=False):
         """fx_get_osc_datagrams: every channel's wire-ready OSC feature message, written on the device from the latest smoothed vectors
-        (ref OSCFeatureAnalysisOutput.h:89-113, MainComponent.cpp:170).  Returns (datagrams uint8 [C][stride], lengths int32 [C])."""
+        (ref OSCFeatureAnalysisOutput.h:89-113, MainComponent.cpp:170).  Returns (datagrams uint8 [C][stride], lengths int32 [C]).
+        addressed=True: fx_get_osc_datagrams_addressed, the addresses of set_osc_addresses instead of prefix and first_channel."""
+        if addressed:
+            stride = self.osc_address_stride() if stride is None else int(stride)
+            out = np.empty((self.num_channels, max(stride, 0)), np.uint8)
+            lengths = np.empty(self.num_channels, np.int32)
+            capi.check(self._lib.fx_get_osc_datagrams_addressed(self._h, out.ctypes.data_as(ctypes.c_void_p), stride,
+                                                                lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), capi.MEM_HOST))
+            return out, lengths
         stride = capi.osc_stride(prefix, first_channel, self.num_channels) if stride is None else int(stride)
         out = np.empty((self.num_channels, stride), np.uint8)
         lengths = np.empty(self.num_channels, np.int32)

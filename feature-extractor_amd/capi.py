@@ -35,7 +35,8 @@ EXPORTS = ["fx_create", "fx_destroy", "fx_reset_state", "fx_set_sample_rate", "f
            "fx_request_taps", "fx_get_taps", "fx_set_channel_map", "fx_push_interleaved",
            "fx_set_channel_gains", "fx_set_channel_onset", "fx_get_channel_settings",
            "fx_enable_onset_events", "fx_get_onset_events",
-           "fx_reset_channels", "fx_clear_pending_channels", "fx_get_channel_frames"]
+           "fx_reset_channels", "fx_clear_pending_channels", "fx_get_channel_frames",
+           "fx_set_osc_addresses", "fx_osc_address_stride", "fx_get_osc_datagrams_addressed", "fx_osc_encode_addressed", "fx_osc_sender_set_routes"]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
 MAX_UNITS = 24
@@ -43,8 +44,10 @@ MAX_UNITS = 24
 LAUNCH_FIELDS = ["kind", "window", "analysers", "T", "direct_state", "block_mode", "num_chunks", "ch_per_wg", "waves_per_ch", "hop_pairs",
                  "ep_T", "out_stride", "ep_form", "reblock"]
 LAUNCH_KINDS = {1: "frame", 2: "frame_tail", 3: "hop", 4: "hop_pair", 5: "pair", 6: "epilogue", 7: "reblock", 8: "osc", 9: "taps",
-                10: "deinterleave", 11: "onset_events"}
+                10: "deinterleave", 11: "onset_events", 12: "osc_table"}
 MAX_TAP_CHANNELS = 64
+OSC_ADDRESS_MAX = 124               # FX_OSC_ADDRESS_MAX
+OSC_SENDER_MAX_TARGETS = 64         # FX_OSC_SENDER_MAX_TARGETS
 LAUNCH_RECORD_CAP = 8
 
 
@@ -210,6 +213,12 @@ def load_library(build_if_missing=True):
     L.fx_osc_message_bytes.argtypes = [ctypes.c_char_p, i]
     L.fx_osc_encode_batch.argtypes = [ctypes.c_char_p, i, i, fp, vp, i, ip]
     L.fx_get_osc_datagrams.argtypes = [vp, ctypes.c_char_p, i, vp, i, ip, i]
+    strings = ctypes.POINTER(ctypes.c_char_p)
+    L.fx_set_osc_addresses.argtypes = [vp, strings]
+    L.fx_osc_address_stride.argtypes = [vp]
+    L.fx_get_osc_datagrams_addressed.argtypes = [vp, vp, i, ip, i]
+    L.fx_osc_encode_addressed.argtypes = [strings, i, fp, vp, i, ip]
+    L.fx_osc_sender_set_routes.argtypes = [vp, strings, i, ip, ip, i]
     L.fx_osc_sender_create.argtypes = [ctypes.POINTER(vp), ctypes.c_char_p, ctypes.c_char_p, i, u]
     L.fx_osc_sender_destroy.argtypes = [vp]
     L.fx_osc_sender_update.argtypes = [vp, vp, i, ip, i]
@@ -296,6 +305,34 @@ def osc_encode_batch(prefix, first_channel, smoothed, stride=None):
     return out, lengths
 
 
+def c_strings(strings):
+    """a list of str / bytes as the `const char* const*` the address and target entries take (keep the result alive over the call)"""
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in strings]
+    return (ctypes.c_char_p * len(raw))(*raw)
+
+
+def osc_address_bytes(address):
+    """bytes of the message of this address: address + NUL padded to 4, 16 bytes of type tags, 48 of floats"""
+    return ((len(address.encode() if isinstance(address, str) else address) + 4) & ~3) + 64
+
+
+def osc_encode_addressed(addresses, smoothed, stride=None):
+    """fx_osc_encode_addressed: (datagrams uint8 [n][stride], lengths int32 [n]) for smoothed [n][12] and one address per track;
+    stride None = the smallest legal one, the longest message."""
+    v = np.ascontiguousarray(smoothed, np.float32).reshape(-1, 12)
+    addresses = list(addresses)
+    if len(addresses) != v.shape[0]:
+        raise ValueError("one address per track (%d), not %d" % (v.shape[0], len(addresses)))
+    stride = max([osc_address_bytes(a) for a in addresses] + [4]) if stride is None else int(stride)
+    out = np.empty((v.shape[0], max(stride, 0)), np.uint8)
+    lengths = np.empty(v.shape[0], np.int32)
+    n = load_library().fx_osc_encode_addressed(c_strings(addresses), v.shape[0], _fp(v), out.ctypes.data_as(ctypes.c_void_p), stride,
+                                               lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+    if n != v.shape[0]:
+        raise FxError(FX_ERR_INVALID_ARGUMENT, load_library().fx_last_error().decode(errors="replace"))
+    return out, lengths
+
+
 class OscSender:
     """fx_osc_sender: sendmmsg batches from `threads` threads to a primary and an optional secondary target, paced by start(rate_hz)."""
 
@@ -310,6 +347,20 @@ class OscSender:
         if d.ndim != 2 or n.shape != (d.shape[0],):
             raise ValueError("datagrams [count][stride] and lengths [count]")
         check(self._lib.fx_osc_sender_update(self._h, d.ctypes.data_as(ctypes.c_void_p), d.shape[1], n.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), d.shape[0]))
+
+    def set_routes(self, targets, primary=None, secondary=None):
+        """fx_osc_sender_set_routes: message i goes to targets[primary[i]] and, where secondary[i] >= 0, to targets[secondary[i]];
+        targets None restores the create-time pair."""
+        if targets is None:
+            check(self._lib.fx_osc_sender_set_routes(self._h, None, 0, None, None, 0))
+            return
+        ip = ctypes.POINTER(ctypes.c_int)
+        p = np.ascontiguousarray(primary, np.int32).ravel()
+        q = None if secondary is None else np.ascontiguousarray(secondary, np.int32).ravel()
+        if q is not None and q.shape != p.shape:
+            raise ValueError("primary and secondary have one entry per message")
+        check(self._lib.fx_osc_sender_set_routes(self._h, c_strings(targets), len(targets), p.ctypes.data_as(ip),
+                                                 q.ctypes.data_as(ip) if q is not None else None, p.size))
 
     def send(self):
         sent = ctypes.c_longlong(0)

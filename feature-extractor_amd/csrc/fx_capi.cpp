@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "fx_plan.h"
+#include "fx_osc_words.h"
 
 thread_local std::string g_fx_err;
 
@@ -362,6 +363,7 @@ fx_status fx_destroy(fx_context* c)
     if (c->interleave_release) c->interleave_release(c);
     if (c->events_release) c->events_release(c);
     if (c->tracks_release) c->tracks_release(c);
+    if (c->osc_table_release) c->osc_table_release(c);
     void* bufs[] = {c->d_tw, c->d_prev, c->d_tail[0], c->d_tail[1], c->d_hist, c->d_latest,
                     c->d_raw, c->d_part, c->d_in, c->d_out_raw, c->d_queue, c->d_carry[0], c->d_carry[1], c->d_hops, c->d_osc, c->d_chan};
     for (void* b : bufs) if (b) (void) hipFree(b);
@@ -811,6 +813,28 @@ int fx_osc_encode_batch(const char* prefix, int first_channel, int num_channels,
         if (lengths) lengths[c] = n;
     }
     return num_channels;
+}
+
+// fx_osc_encode for n tracks with addresses of their own: the host twin of the device call of fx_osc_table.hip, which holds the same
+// address rules (fx_osc_words.h)
+int fx_osc_encode_addressed(const char* const* addresses, int n, const float* smoothed, unsigned char* out, int stride, int* lengths)
+{
+    if (n < 0 || (stride & 3) || (n > 0 && (!addresses || !smoothed || !out))) { (void) fx_fail(FX_ERR_INVALID_ARGUMENT, "null argument, a negative count or a stride that is no multiple of 4"); return -1; }
+    int longest = 0;
+    for (int c = 0; c < n; c++) {
+        int alen = 0;
+        if (const char* fault = fxk::osc_address_fault(addresses[c], &alen)) { (void) fx_fail(FX_ERR_INVALID_ARGUMENT, "track %d: the OSC address %s", c, fault); return -1; }
+        if (fxk::osc_addressed_bytes(alen) > longest) longest = fxk::osc_addressed_bytes(alen);
+    }
+    if (stride < longest) { (void) fx_fail(FX_ERR_INVALID_ARGUMENT, "stride %d does not hold the longest message (%d bytes)", stride, longest); return -1; }
+    for (int c = 0; c < n; c++) {
+        unsigned char* slot = out + (size_t) c * (size_t) stride;
+        const int len = fx_osc_encode(addresses[c], smoothed + (size_t) c * FX_NUM_FEATURES, slot, stride);
+        if (len < 0) return -1;
+        memset(slot + len, 0, (size_t) (stride - len));
+        if (lengths) lengths[c] = len;
+    }
+    return n;
 }
 
 } // extern "C"

@@ -1,5 +1,6 @@
 // fx_context.h -- the context behind the C ABI (include/fx.h), shared by the shim's host units (fx_capi.cpp, fx_plan.cpp, fx_stream.cpp,
-// fx_comm.cpp) and the units that attach through its hooks (fx_taps.hip, fx_interleave.hip, fx_events.hip, fx_tracks.hip).  Internal.
+// fx_comm.cpp) and the units that attach through its hooks (fx_taps.hip, fx_interleave.hip, fx_events.hip, fx_tracks.hip,
+// fx_osc_table.hip).  Internal.
 #ifndef FX_CONTEXT_H
 #define FX_CONTEXT_H
 
@@ -59,6 +60,7 @@ struct fx_taps;
 struct fx_interleave;   // fx_interleave.hip
 struct fx_events;       // fx_events.hip
 struct fx_tracks;       // fx_tracks.hip
+struct fx_osc_table;    // fx_osc_table.hip
 // Where an analysis call reads its FIRST frame, as the kernels read it: `in` (device) holds rows of in_row_bytes per channel; hop_mode 1:
 // hops of N/2 samples, the window is [the channel's tail | hop 0 x gain]; 0: whole frames, frame 0 as given.  carry != null: the hop is
 // the first N/2 samples of [pending | block] (fx_blocks.hip.h, BlockStream), the pending row of the channel at carry + c * carry_row_bytes.
@@ -166,6 +168,11 @@ struct fx_context {
     // fx_clear_pending_channels, which installs the hook fx_destroy calls.  The tracks' first frames live in `chan` (first_frame).
     fx_tracks* tracks = nullptr;
     void (*tracks_release)(fx_context*) = nullptr;
+
+    // per-track OSC addresses (fx_osc_table.hip): the address table on the device and the messages' lengths; null while no table is
+    // set.  fx_set_osc_addresses installs the hook fx_destroy calls.  A setting: no reset touches it.
+    fx_osc_table* osc_table = nullptr;
+    void (*osc_table_release)(fx_context*) = nullptr;
 };
 
 // The per-track rows (fx_capi.cpp), for the units that change them.  fx_channel_rows: what every track runs with now -- the table's rows,

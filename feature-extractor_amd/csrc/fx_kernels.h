@@ -335,6 +335,8 @@ enum { FX_LAUNCH_FRAME = 1, FX_LAUNCH_FRAME_TAIL, FX_LAUNCH_HOP, FX_LAUNCH_HOP_P
 // The onset event list's step (fx_events.hip), the last entry of an analysis call on a context with events enabled: ONE entry and one
 // launch per call (counts, scan and records in one kernel), T = the frames per channel the call analysed.
 constexpr int FX_LAUNCH_ONSET_EVENTS = 11;
+// fx_get_osc_datagrams_addressed (fx_osc_table.hip): one launch of fx_osc_table_kernel; it starts a new record, as fx_get_osc_datagrams does.
+constexpr int FX_LAUNCH_OSC_TABLE = 12;
 struct fx_launch_record {
     int kind;               // FX_LAUNCH_*
     int window, analysers;  // window size, analysers mask (bit 0 spectral, bit 1 harmonic)

@@ -8,6 +8,11 @@
 // hands them to the kernel in batches: `threads` sender threads, each owning a contiguous slice of the tracks and one connected UDP
 // socket per target, sendmmsg of up to 1024 messages per call -- or, with FX_OSC_SENDER_GSO, runs of equal-length messages as segmented
 // sends (UDP_SEGMENT: one trip through the stack per 64 datagrams; the datagrams on the wire are the same).
+//
+// Per-track targets (fx_osc_sender_set_routes; ref AnalyserTrackController.h:17,22-23: every track has its own ip and secondaryIP):
+// a Routes object holds up to 64 targets and, per sender thread, the message indices of its slice ordered by target, made once when
+// the routes are set.  A tick then sends each target's list exactly as it sends a slice: the senders below walk positions [lo, hi) of
+// an index list, or of the identity where there is none.
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <netinet/udp.h>
@@ -79,6 +84,31 @@ struct Batch {
 constexpr int kChunk = 1024;         // messages per sendmmsg (UIO_MAXIOV is the limit of one message's iov, not of this)
 constexpr int kSegments = 64;        // UDP_MAX_SEGMENTS: datagrams per segmented send
 
+int connected_socket(const sockaddr_in& target)
+{
+    const int fd = socket(AF_INET, SOCK_DGRAM, 0);
+    int sndbuf = 8 << 20;
+    if (fd >= 0) (void) setsockopt(fd, SOL_SOCKET, SO_SNDBUF, &sndbuf, sizeof sndbuf);
+    if (fd < 0 || connect(fd, reinterpret_cast<const sockaddr*>(&target), sizeof target) != 0) {
+        const int e = errno;
+        if (fd >= 0) close(fd);
+        errno = e;
+        return -1;
+    }
+    return fd;
+}
+
+// fx_osc_sender_set_routes: what a tick needs, made once.  Immutable after it is published; the last tick that uses it closes its sockets.
+struct Routes {
+    struct List { int fd = -1; std::vector<int> index; };      // one target's messages within a thread's slice, ascending
+    int count = 0;
+    std::vector<std::vector<List>> per_thread;                 // [thread]: the targets that thread serves, in target order
+    ~Routes() { for (std::vector<List>& lists : per_thread) for (List& l : lists) if (l.fd >= 0) close(l.fd); }
+};
+
+// position k of an index list, or of the identity
+inline int message_at(const int* index, int k) { return index ? index[k] : k; }
+
 } // namespace
 
 struct fx_osc_sender {
@@ -90,6 +120,7 @@ struct fx_osc_sender {
 
     std::mutex pub;                               // `current` and the pool of spare batches
     std::shared_ptr<Batch> current;
+    std::shared_ptr<const Routes> routes;         // (under `pub` too) null: every message to every create-time target
     std::vector<std::unique_ptr<Batch>> spare;
 
     std::mutex tick_lock;                         // one tick at a time (the timer against fx_osc_sender_send)
@@ -98,6 +129,7 @@ struct fx_osc_sender {
     unsigned long long tick_seq = 0;
     int pending = 0;
     std::shared_ptr<Batch> tick_batch;
+    std::shared_ptr<const Routes> tick_routes;
     bool quit = false;
     std::vector<std::thread> workers;             // threads - 1 of them: the thread that runs the tick sends slice 0
 
@@ -111,8 +143,8 @@ struct fx_osc_sender {
 
 namespace {
 
-// messages [lo, hi) of the batch to one socket, plain: sendmmsg, one message per datagram
-void send_plain(fx_osc_sender* s, int fd, const Batch& b, int lo, int hi)
+// messages index[lo .. hi) of the batch (index null: messages lo .. hi) to one socket, plain: sendmmsg, one message per datagram
+void send_plain(fx_osc_sender* s, int fd, const Batch& b, const int* index, int lo, int hi)
 {
     static thread_local std::vector<mmsghdr> msgs(kChunk);
     static thread_local std::vector<iovec> iov(kChunk);
@@ -120,8 +152,9 @@ void send_plain(fx_osc_sender* s, int fd, const Batch& b, int lo, int hi)
     for (int at = lo; at < hi;) {
         const int n = hi - at < kChunk ? hi - at : kChunk;
         for (int i = 0; i < n; i++) {
-            iov[(size_t) i].iov_base = const_cast<unsigned char*>(b.data.data()) + (size_t) (at + i) * (size_t) b.stride;
-            iov[(size_t) i].iov_len = (size_t) b.len[(size_t) (at + i)];
+            const int m = message_at(index, at + i);
+            iov[(size_t) i].iov_base = const_cast<unsigned char*>(b.data.data()) + (size_t) m * (size_t) b.stride;
+            iov[(size_t) i].iov_len = (size_t) b.len[(size_t) m];
             msgs[(size_t) i] = mmsghdr();
             msgs[(size_t) i].msg_hdr.msg_iov = &iov[(size_t) i];
             msgs[(size_t) i].msg_hdr.msg_iovlen = 1;
@@ -142,7 +175,7 @@ void send_plain(fx_osc_sender* s, int fd, const Batch& b, int lo, int hi)
 
 // the same with UDP_SEGMENT: a run of equal-length messages (at most 64, at most 65 507 bytes) is ONE send whose payload the
 // stack cuts back into the datagrams; up to 16 runs per sendmmsg.  false: the kernel does not do it (the caller falls back for good).
-bool send_segmented(fx_osc_sender* s, int fd, const Batch& b, int lo, int hi)
+bool send_segmented(fx_osc_sender* s, int fd, const Batch& b, const int* index, int lo, int hi)
 {
     constexpr int kRuns = 16;
     static thread_local std::vector<mmsghdr> msgs(kRuns);
@@ -155,15 +188,15 @@ bool send_segmented(fx_osc_sender* s, int fd, const Batch& b, int lo, int hi)
         int runs = 0, first_of_run[kRuns + 1];
         int k = at;
         while (k < hi && runs < kRuns) {
-            const int len = b.len[(size_t) k];
+            const int len = b.len[(size_t) message_at(index, k)];
             int n = 1;
-            while (k + n < hi && n < kSegments && b.len[(size_t) (k + n)] == len && (n + 1) * len <= 65507) n++;
+            while (k + n < hi && n < kSegments && b.len[(size_t) message_at(index, k + n)] == len && (n + 1) * len <= 65507) n++;
             first_of_run[runs] = k;
             mmsghdr& m = msgs[(size_t) runs];
             m = mmsghdr();
             for (int i = 0; i < n; i++) {
                 iovec& v = iov[(size_t) runs * kSegments + (size_t) i];
-                v.iov_base = const_cast<unsigned char*>(b.data.data()) + (size_t) (k + i) * (size_t) b.stride;
+                v.iov_base = const_cast<unsigned char*>(b.data.data()) + (size_t) message_at(index, k + i) * (size_t) b.stride;
                 v.iov_len = (size_t) len;
             }
             m.msg_hdr.msg_iov = &iov[(size_t) runs * kSegments];
@@ -201,18 +234,25 @@ bool send_segmented(fx_osc_sender* s, int fd, const Batch& b, int lo, int hi)
     return true;
 }
 
-void send_slice(fx_osc_sender* s, int t, const Batch& b)
+void send_list(fx_osc_sender* s, int fd, const Batch& b, const int* index, int lo, int hi)
 {
+    if (s->gso.load(std::memory_order_relaxed)) {
+        if (send_segmented(s, fd, b, index, lo, hi)) return;
+        s->gso.store(false, std::memory_order_relaxed);
+    }
+    send_plain(s, fd, b, index, lo, hi);
+}
+
+void send_slice(fx_osc_sender* s, int t, const Batch& b, const Routes* routes)
+{
+    if (routes) {
+        if (routes->count != b.count) return;       // (never published together: fx_osc_sender_update and _set_routes refuse the other count)
+        for (const Routes::List& l : routes->per_thread[(size_t) t]) send_list(s, l.fd, b, l.index.data(), 0, (int) l.index.size());
+        return;
+    }
     const int lo = (int) ((long long) b.count * t / s->threads), hi = (int) ((long long) b.count * (t + 1) / s->threads);
     if (lo >= hi) return;
-    for (size_t k = 0; k < s->targets.size(); k++) {
-        const int fd = s->fds[(size_t) t * s->targets.size() + k];
-        if (s->gso.load(std::memory_order_relaxed)) {
-            if (send_segmented(s, fd, b, lo, hi)) continue;
-            s->gso.store(false, std::memory_order_relaxed);
-        }
-        send_plain(s, fd, b, lo, hi);
-    }
+    for (size_t k = 0; k < s->targets.size(); k++) send_list(s, s->fds[(size_t) t * s->targets.size() + k], b, nullptr, lo, hi);
 }
 
 void worker(fx_osc_sender* s, int t)
@@ -220,14 +260,16 @@ void worker(fx_osc_sender* s, int t)
     unsigned long long seen = 0;
     for (;;) {
         std::shared_ptr<Batch> b;
+        std::shared_ptr<const Routes> routes;
         {
             std::unique_lock<std::mutex> g(s->wm);
             s->wake.wait(g, [&] { return s->quit || s->tick_seq != seen; });
             if (s->quit) return;
             seen = s->tick_seq;
             b = s->tick_batch;
+            routes = s->tick_routes;
         }
-        if (b) send_slice(s, t, *b);
+        if (b) send_slice(s, t, *b, routes.get());
         {
             std::lock_guard<std::mutex> g(s->wm);
             if (--s->pending == 0) s->done.notify_all();
@@ -240,7 +282,8 @@ long long run_tick(fx_osc_sender* s)
 {
     std::lock_guard<std::mutex> one(s->tick_lock);
     std::shared_ptr<Batch> b;
-    { std::lock_guard<std::mutex> g(s->pub); b = s->current; }
+    std::shared_ptr<const Routes> routes;
+    { std::lock_guard<std::mutex> g(s->pub); b = s->current; routes = s->routes; }      // a publication and the routes it goes by, as one
     s->ticks++;
     if (!b || b->count == 0) return 0;
     const long long before = s->datagrams.load();
@@ -248,15 +291,17 @@ long long run_tick(fx_osc_sender* s)
     if (s->threads > 1) {
         std::lock_guard<std::mutex> g(s->wm);
         s->tick_batch = b;
+        s->tick_routes = routes;
         s->pending = s->threads - 1;
         s->tick_seq++;
         s->wake.notify_all();
     }
-    send_slice(s, 0, *b);
+    send_slice(s, 0, *b, routes.get());
     if (s->threads > 1) {
         std::unique_lock<std::mutex> g(s->wm);
         s->done.wait(g, [&] { return s->pending == 0; });
         s->tick_batch.reset();
+        s->tick_routes.reset();
     }
     const double ms = now_ms() - t0;
     {
@@ -296,12 +341,9 @@ fx_status fx_osc_sender_create(fx_osc_sender** out, const char* primary, const c
     }
     for (int t = 0; t < threads; t++)
         for (const sockaddr_in& target : s->targets) {
-            const int fd = socket(AF_INET, SOCK_DGRAM, 0);
-            int sndbuf = 8 << 20;
-            if (fd >= 0) (void) setsockopt(fd, SOL_SOCKET, SO_SNDBUF, &sndbuf, sizeof sndbuf);
-            if (fd < 0 || connect(fd, reinterpret_cast<const sockaddr*>(&target), sizeof target) != 0) {
+            const int fd = connected_socket(target);
+            if (fd < 0) {
                 const int e = errno;
-                if (fd >= 0) close(fd);
                 for (int f : s->fds) close(f);
                 delete s;
                 return fx_fail(FX_ERR_INVALID_ARGUMENT, "UDP socket for the sender: %s", strerror(e));
@@ -321,6 +363,7 @@ fx_status fx_osc_sender_destroy(fx_osc_sender* s)
     for (std::thread& w : s->workers) w.join();
     for (int f : s->fds) close(f);
     s->current.reset();            // (its deleter files the batch in `spare`, which goes with the object)
+    s->routes.reset();
     delete s;
     return FX_OK;
 }
@@ -334,6 +377,7 @@ fx_status fx_osc_sender_update(fx_osc_sender* s, const unsigned char* datagrams,
     std::unique_ptr<Batch> b;
     {
         std::lock_guard<std::mutex> g(s->pub);
+        if (s->routes && s->routes->count != count) return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d messages published while routes for %d are set", count, s->routes->count);
         if (!s->spare.empty()) { b = std::move(s->spare.back()); s->spare.pop_back(); }
     }
     if (!b) b.reset(new (std::nothrow) Batch());
@@ -350,12 +394,66 @@ fx_status fx_osc_sender_update(fx_osc_sender* s, const unsigned char* datagrams,
         if (s->spare.size() < 3) s->spare.emplace_back(p); else delete p;
     });
     std::shared_ptr<Batch> old;
+    int routed = -1;
     {
         std::lock_guard<std::mutex> g(s->pub);
-        old.swap(s->current);
-        s->current = std::move(shared);
+        if (s->routes && s->routes->count != count) routed = s->routes->count;      // (routes set since the check above)
+        else { old.swap(s->current); s->current = std::move(shared); }
     }
-    return FX_OK;              // (`old` is released here, outside the lock its deleter takes)
+    if (routed >= 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d messages published while routes for %d are set", count, routed);
+    return FX_OK;              // (`old`, or the refused batch, is released here, outside the lock its deleter takes)
+}
+
+fx_status fx_osc_sender_set_routes(fx_osc_sender* s, const char* const* targets, int num_targets, const int* primary, const int* secondary, int count)
+{
+    if (!s) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null sender");
+    std::shared_ptr<const Routes> old;
+    if (!targets) {                                 // back to the create-time pair
+        std::lock_guard<std::mutex> g(s->pub);
+        old.swap(s->routes);
+        return FX_OK;
+    }
+    // everything is checked and built before anything changes
+    if (num_targets < 1 || num_targets > FX_OSC_SENDER_MAX_TARGETS) return fx_fail(FX_ERR_INVALID_ARGUMENT, "1 .. %d targets, not %d", FX_OSC_SENDER_MAX_TARGETS, num_targets);
+    if (count < 0 || (count > 0 && !primary)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "routes for %d messages without a primary list", count);
+    for (int i = 0; i < count; i++) {
+        if (primary[i] < 0 || primary[i] >= num_targets) return fx_fail(FX_ERR_INVALID_ARGUMENT, "message %d: primary target %d out of range [0,%d)", i, primary[i], num_targets);
+        if (secondary && (secondary[i] < -1 || secondary[i] >= num_targets)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "message %d: secondary target %d out of range [-1,%d)", i, secondary[i], num_targets);
+    }
+    std::vector<sockaddr_in> parsed((size_t) num_targets);
+    for (int k = 0; k < num_targets; k++)
+        if (!targets[k] || !parse_target(targets[k], &parsed[(size_t) k], 9000)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "target %d: cannot parse '%s' (ip[:port])", k, targets[k] ? targets[k] : "(null)");
+    std::shared_ptr<Routes> r;
+    try {
+        r = std::make_shared<Routes>();
+        r->count = count;
+        r->per_thread.resize((size_t) s->threads);
+        std::vector<std::vector<int>> by_target((size_t) num_targets);
+        for (int t = 0; t < s->threads; t++) {
+            const int lo = (int) ((long long) count * t / s->threads), hi = (int) ((long long) count * (t + 1) / s->threads);
+            for (std::vector<int>& list : by_target) list.clear();
+            for (int i = lo; i < hi; i++) {         // ascending track order per target; a track whose two targets are one goes there twice
+                by_target[(size_t) primary[i]].push_back(i);
+                if (secondary && secondary[i] >= 0) by_target[(size_t) secondary[i]].push_back(i);
+            }
+            for (int k = 0; k < num_targets; k++) {
+                if (by_target[(size_t) k].empty()) continue;
+                r->per_thread[(size_t) t].emplace_back();
+                Routes::List& l = r->per_thread[(size_t) t].back();
+                l.index = by_target[(size_t) k];
+                l.fd = connected_socket(parsed[(size_t) k]);
+                if (l.fd < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "UDP socket for target %d ('%s'): %s", k, targets[k], strerror(errno));
+            }
+        }
+    } catch (const std::bad_alloc&) { return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+    int published = -1;
+    {
+        std::lock_guard<std::mutex> g(s->pub);      // the lock a publication takes: a tick sees a batch and the routes it goes by
+        if (s->current && s->current->count != count) published = s->current->count;
+        else { old = std::move(s->routes); s->routes = std::move(r); }
+    }
+    if (published >= 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "routes for %d messages while %d are published", count, published);
+    return FX_OK;              // (the old routes' sockets close with the last tick that uses them)
 }
 
 fx_status fx_osc_sender_send(fx_osc_sender* s, long long* sent)

@@ -549,6 +549,29 @@ int fx_osc_encode_batch(const char* prefix, int first_channel, int num_channels,
 fx_status fx_get_osc_datagrams(fx_context* ctx, const char* prefix, int first_channel, unsigned char* out, int stride,
                                int* lengths, int mem_kind);
 
+/* ---- per-track addresses: every track's own bundleAddress ----
+ * The reference builds each track with (ip, secondaryIP, bundle) (AnalyserTrackController.h:17,22-23) and the GUI edits the three per
+ * track (:140-147); both of a track's senders send `bundleAddress` (OSCFeatureAnalysisOutput.h:107) to their own host (:115-136).
+ * The address is this table; the two hosts are the sender's routes (fx_osc_sender_set_routes below). */
+#define FX_OSC_ADDRESS_MAX 124   /* bytes of an address: padded it is at most 128 bytes, a message at most 192 */
+/* Every track's address (ref AnalyserTrackController.h:17,146 setBundleAddressChangedCallback): addresses [num_channels] C strings in
+ * host memory, copied (the caller may free them on return), or NULL to drop the table.  An address has 1 .. FX_OSC_ADDRESS_MAX bytes,
+ * starts with '/', every byte in 0x21 .. 0x7E; a bad one fails the whole call with FX_ERR_INVALID_ARGUMENT before any device use
+ * (fx_last_error names the track) and nothing changes; a failed allocation or upload leaves the old table in force.  A setting:
+ * fx_reset_state and fx_reset_channels keep it.  Synchronises the context's stream, as the other per-track setters do. */
+fx_status fx_set_osc_addresses(fx_context* ctx, const char* const* addresses);
+/* The smallest legal stride of fx_get_osc_datagrams_addressed: the longest message (OSCFeatureAnalysisOutput.h:107) of the table;
+ * -1 without a table. */
+int fx_osc_address_stride(fx_context* ctx);
+/* fx_get_osc_datagrams with the table's addresses (ref OSCFeatureAnalysisOutput.h:107): message c, at out + c * stride, is byte for
+ * byte fx_osc_encode(address[c], latest[c]) and the rest of its slot zeros; lengths (host, or NULL) come from the table.  Ordering,
+ * FX_MEM_HOST / FX_MEM_DEVICE and the 4-byte alignment of a device buffer as fx_get_osc_datagrams; stride: a multiple of 4,
+ * >= fx_osc_address_stride.  FX_ERR_INVALID_ARGUMENT without a table. */
+fx_status fx_get_osc_datagrams_addressed(fx_context* ctx, unsigned char* out, int stride, int* lengths, int mem_kind);
+/* The same bytes formed on the host (no GPU) for n tracks: addresses [n] under the rules above, smoothed12 [n][12] in AudioFeatures
+ * slot order (ref OSCFeatureAnalysisOutput.h:107).  Returns n, or -1 on a bad argument (fx_last_error names a bad address's track). */
+int fx_osc_encode_addressed(const char* const* addresses, int n, const float* smoothed12, unsigned char* out, int stride, int* lengths);
+
 /* The sender: one UDP socket per target and thread, sendmmsg in chunks, `threads` sender threads each owning a slice of the tracks,
  * a 60 Hz timer (OSCFeatureAnalysisOutput::startTimerHz (60), :133) and a primary plus an optional secondary target
  * (AnalyserTrackController.h:22-23); targets are "ip[:port]", port 9000 by default, parsed as connectToAddress does (:115-123).
@@ -575,6 +598,17 @@ typedef struct fx_osc_sender_stats {
     double    last_tick_ms, max_tick_ms, total_tick_ms;   /* time to hand a tick's datagrams to the kernel */
 } fx_osc_sender_stats;
 fx_status fx_osc_sender_get_stats(fx_osc_sender* s, fx_osc_sender_stats* out);
+/* Per-track targets (ref AnalyserTrackController.h:17,22-23: each track's ip and secondaryIP; :140-145 the GUI's address callbacks;
+ * OSCFeatureAnalysisOutput.h:115-136 connectToAddress): targets [num_targets <= FX_OSC_SENDER_MAX_TARGETS] "ip[:port]" strings parsed
+ * as at create; message i of a publication goes to targets[primary[i]] and, where secondary is not NULL and secondary[i] >= 0, to
+ * targets[secondary[i]] as well; `count` = the messages of a publication.  targets == NULL restores the create-time pair.  Each
+ * sender thread keeps one connected socket per target it serves and orders its slice's messages by target HERE, not per tick; per
+ * target the messages keep ascending track order.  While routes are set, a publication (fx_osc_sender_update) of another count is
+ * FX_ERR_INVALID_ARGUMENT, and so are routes of another count than what is published.  Bad indices or unparsable targets change
+ * nothing.  Safe while the timer runs. */
+#define FX_OSC_SENDER_MAX_TARGETS 64
+fx_status fx_osc_sender_set_routes(fx_osc_sender* s, const char* const* targets, int num_targets, const int* primary,
+                                   const int* secondary /* or NULL */, int count);
 
 /* A counting receiver for tests, benchmarks and soak runs of the sender (loopback diagnostics, not part of the analysis path):
  * `threads` sockets bound to bind_address ("127.0.0.1:0" = any free port) with SO_REUSEPORT, drained by recvmmsg.  With

@@ -666,6 +666,7 @@ private:
 // The sink at scale: ONE object for all tracks.  A tick's messages arrive formed -- fx_get_osc_datagrams writes them on the GPU from the
 // context's latest vectors, fx_osc_encode_batch on the host -- and go out in sendmmsg batches from `threads` sender threads to a primary
 // and an optional secondary target, paced by a 60 Hz timer (ref OSCFeatureAnalysisOutput.h:84-136, AnalyserTrackController.h:22-23).
+// A track's own address and targets (the reference's per-track ip, secondaryIP, bundle): setBundleAddresses, setRoutes.
 // Thin wrapper of the fx_osc_sender_* entries of include/fx.h.
 class OSCBatchSender
 {
@@ -691,9 +692,41 @@ public:
             throw Error (FX_ERR_INVALID_ARGUMENT, "fx_osc_encode_batch refused its arguments");
         updateDatagrams (scratch.data(), stride, lengths.data(), count);
     }
-    // publish the context's latest vectors, formed on the device (the copy to the host is the datagrams)
+    // Every track's own bundleAddress (ref AnalyserTrackController.h:17,146 setBundleAddressChangedCallback): one address per track of
+    // the context, or an empty list to go back to "<prefix><channel>".  fx_set_osc_addresses: call it where the context's other calls are
+    // made (with a LiveAnalyser: callOnWorker).  From then on updateFromContext publishes the table's messages.
+    void setBundleAddresses (fx_context* ctx, const std::vector<std::string>& addresses)
+    {
+        std::vector<const char*> list;
+        for (const std::string& a : addresses) list.push_back (a.c_str());
+        check (fx_set_osc_addresses (ctx, list.empty() ? nullptr : list.data()));
+        addressStride = &fx_osc_address_stride;                 // (a host that never calls this needs no symbol of the address table)
+        addressedDatagrams = &fx_get_osc_datagrams_addressed;
+    }
+    // Every track's own targets (ref AnalyserTrackController.h:17,22-23 ip / secondaryIP, :140-145 the GUI's two address callbacks):
+    // message i goes to targets[primary[i]] and, where secondary[i] >= 0, to targets[secondary[i]] (secondary may be empty: none).
+    // An empty target list restores the constructor's pair.  Safe while the timer runs.
+    void setRoutes (const std::vector<std::string>& targets, const std::vector<int>& primary, const std::vector<int>& secondary = std::vector<int>())
+    {
+        if (! secondary.empty() && secondary.size() != primary.size()) throw Error (FX_ERR_INVALID_ARGUMENT, "primary and secondary have one entry per track");
+        std::vector<const char*> list;
+        for (const std::string& t : targets) list.push_back (t.c_str());
+        check (fx_osc_sender_set_routes (sender, list.empty() ? nullptr : list.data(), (int) list.size(), primary.data(),
+                                         secondary.empty() ? nullptr : secondary.data(), (int) primary.size()));
+    }
+    // publish the context's latest vectors, formed on the device (the copy to the host is the datagrams): with the addresses of
+    // setBundleAddresses where a table is set, else "<prefix><firstChannel + i>"
     void updateFromContext (fx_context* ctx, int numChannels, const std::string& prefix, int firstChannel)
     {
+        const int tableStride = addressStride != nullptr ? addressStride (ctx) : -1;
+        if (tableStride >= 0)
+        {
+            scratch.resize ((std::size_t) numChannels * (std::size_t) tableStride);
+            lengths.resize ((std::size_t) numChannels);
+            check (addressedDatagrams (ctx, scratch.data(), tableStride, lengths.data(), FX_MEM_HOST));
+            updateDatagrams (scratch.data(), tableStride, lengths.data(), numChannels);
+            return;
+        }
         const int stride = fx_osc_message_bytes (prefix.c_str(), firstChannel + (numChannels > 0 ? numChannels - 1 : 0));
         if (stride < 0) throw Error (FX_ERR_INVALID_ARGUMENT, "OSC prefix too long or a negative channel number");
         scratch.resize ((std::size_t) numChannels * (std::size_t) stride);
@@ -711,6 +744,8 @@ private:
     fx_osc_sender* sender = nullptr;
     std::vector<unsigned char> scratch;
     std::vector<int> lengths;
+    int (*addressStride) (fx_context*) = nullptr;
+    fx_status (*addressedDatagrams) (fx_context*, unsigned char*, int, int*, int) = nullptr;
 };
 
 // The live engine.  The reference's audio callback copies the device block into the collector's ring and notify()s the analysis thread
