@@ -29,6 +29,57 @@ def pack_s24(values):
 
 
 _FORMAT_NAMES = {"f32": capi.SAMPLE_F32, "f16": capi.SAMPLE_F16, "s16": capi.SAMPLE_S16, "s24": capi.SAMPLE_S24}
+# THE dtype-to-format table (torch's dtypes go by the same names): uint8 is packed 24-bit PCM, three bytes per sample, and only where
+# the caller says so; int16 is 16-bit PCM, v / 32768 in the kernels' load stage (include/fx_wav.hpp's scaling)
+_DTYPE_FORMATS = {np.dtype(np.float32): capi.SAMPLE_F32, np.dtype(np.float16): capi.SAMPLE_F16, np.dtype(np.int16): capi.SAMPLE_S16,
+                  np.dtype(np.uint8): capi.SAMPLE_S24}
+_torch_formats = {}                              # the same by torch's dtypes, filled when the first tensor arrives
+
+
+def _describe_input(x, sample_format, device, align=16):
+    """What an analysis call needs of its input x -- a numpy array (host memory) or a torch CUDA tensor on cuda:`device` whose data starts
+    on an `align`-byte boundary (fx.h: 16 for whole hops and frames, 4 for blocks) -- as the tuple (ptr c_void_p, fmt capi.SAMPLE_*,
+    mem capi.MEM_*, count of SAMPLES: a third of the bytes of s24, keep: what holds the memory, alive over the call, and the torch device
+    of a device block, else None).  ValueError for what the library would misread, before any use of it."""
+    if sample_format is not None and sample_format not in _FORMAT_NAMES:
+        raise ValueError("sample_format must be one of %s" % ", ".join(sorted(_FORMAT_NAMES)))
+    want = None if sample_format is None else _FORMAT_NAMES[sample_format]
+    torch_input = _is_torch(x)
+    if torch_input:
+        if not x.is_cuda:
+            raise ValueError("torch input must live on the GPU (use numpy for host buffers)")
+        if not x.is_contiguous():
+            raise ValueError("device input must be contiguous")
+        if not _torch_formats:
+            import torch
+            _torch_formats.update((getattr(torch, dt.name), f) for dt, f in _DTYPE_FORMATS.items())
+        fmt = _torch_formats.get(x.dtype)
+        if fmt is None:                          # (a tensor is refused, not converted: the conversion would be a hidden kernel and copy)
+            raise ValueError("samples must be float32, float16, int16 (16-bit PCM) or uint8 (packed 24-bit PCM)")
+        tagged, size = False, x.numel()
+    else:
+        tagged = isinstance(x, PackedS24)
+        x = np.ascontiguousarray(x)
+        fmt = _DTYPE_FORMATS.get(x.dtype)
+        if fmt is None:                          # float64, int32 ...: their values as float32
+            x, fmt = np.ascontiguousarray(x, np.float32), capi.SAMPLE_F32
+        size = x.size
+    if fmt == capi.SAMPLE_S24:
+        if not (tagged or want == capi.SAMPLE_S24):
+            raise ValueError('uint8 samples are taken as packed 24-bit PCM only with sample_format="s24" (or as a PackedS24 array from pack_s24)')
+        if size % 3:
+            raise ValueError("input size is not a multiple of 3 bytes, the size of a packed 24-bit sample")
+        size //= 3
+    if want is not None and want != fmt:
+        raise ValueError("sample_format=%r does not describe a %s %s" % (sample_format, x.dtype, "tensor" if torch_input else "array"))
+    if not torch_input:
+        return x.ctypes.data_as(ctypes.c_void_p), fmt, capi.MEM_HOST, size, x, None
+    ptr, where = x.data_ptr(), x.device
+    if ptr % align:
+        raise ValueError("device input must start on a %d-byte boundary (an offset view of a tensor may not)" % align)
+    if where.index != device:
+        raise ValueError("input lives on %s, the analyser on cuda:%d" % (where, device))
+    return ctypes.c_void_p(ptr), fmt, capi.MEM_DEVICE, size, x, where
 
 
 def interleaved_dims(shape, size, fmt, num_source_channels=None):
@@ -182,18 +233,14 @@ class BatchAnalyser:
 
     def set_test_hooks(self, bits):
         """fx_set_tuning_internal (csrc/fx_kernels.h, FX_HOOK_*): tests only, not part of include/fx.h."""
-        fn = self._lib.fx_set_tuning_internal
-        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_uint], ctypes.c_int
-        capi.check(fn(self._h, int(bits)))
+        capi.check(self._lib.fx_set_tuning_internal(self._h, int(bits)))
 
     def last_launches(self):
         """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
         (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events, osc_table)."""
-        fn = self._lib.fx_last_launches_internal
-        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int], ctypes.c_int
         cap = capi.LAUNCH_RECORD_CAP
         buf = (ctypes.c_int * (cap * len(capi.LAUNCH_FIELDS)))()
-        n = fn(self._h, buf, cap)
+        n = self._lib.fx_last_launches_internal(self._h, buf, cap)
         if n > cap:
             raise RuntimeError("the last call made %d launches; the record keeps %d" % (n, cap))
         out = []
@@ -265,92 +312,60 @@ class BatchAnalyser:
         return s.value
 
     # ---- analysis ----
-    def _run(self, fn, x, per_frame, want_raw, want_smoothed, out_raw=None, out_smoothed=None, sample_format=None):
-        """Sample formats by dtype: float32, float16, int16 (16-bit PCM); packed 24-bit PCM (three bytes per sample) is a PackedS24
-        array (pack_s24) or any uint8 buffer passed with sample_format="s24" -- never inferred from dtype uint8 alone.  The integer
-        formats are widened in the kernels' load stage to exactly the floats a WAV reader would produce.  Device buffers must start
-        on a 16-byte boundary (fx.h)."""
-        C = self.num_channels
-        if sample_format is not None and sample_format not in _FORMAT_NAMES:
-            raise ValueError("sample_format must be one of %s" % ", ".join(sorted(_FORMAT_NAMES)))
-        want = None if sample_format is None else _FORMAT_NAMES[sample_format]
-        s24_error = 'uint8 samples are taken as packed 24-bit PCM only with sample_format="s24" (or as a PackedS24 array from pack_s24)'
-        if _is_torch(x):
-            import torch
-            if not x.is_cuda:
-                raise ValueError("torch input must live on the GPU (use numpy for host buffers)")
-            if not x.is_contiguous():
-                raise ValueError("device input must be contiguous")
-            if x.dtype == torch.float32:
-                fmt = capi.SAMPLE_F32
-            elif x.dtype == torch.float16:
-                fmt = capi.SAMPLE_F16
-            elif x.dtype == torch.int16:
-                fmt = capi.SAMPLE_S16            # 16-bit PCM: v / 32768 in the kernels' load stage (include/fx_wav.hpp's scaling)
-            elif x.dtype == torch.uint8:
-                if want != capi.SAMPLE_S24:
-                    raise ValueError(s24_error)
-                fmt = capi.SAMPLE_S24            # packed 24-bit PCM: three bytes per sample
-                per_frame = 3 * per_frame
-            else:
-                raise ValueError("samples must be float32, float16, int16 (16-bit PCM) or uint8 (packed 24-bit PCM)")
-            if want is not None and want != fmt:
-                raise ValueError("sample_format=%r does not describe a %s tensor" % (sample_format, x.dtype))
-            if x.data_ptr() % 16:
-                raise ValueError("device input must start on a 16-byte boundary (an offset view of a tensor may not)")
-            if x.numel() % (C * per_frame):
-                raise ValueError("input size is not a multiple of channels x samples per frame")
-            T = x.numel() // (C * per_frame)
-            if x.device.index != self.device:
-                raise ValueError("input lives on %s, the analyser on cuda:%d" % (x.device, self.device))
-            for name, o in (("out_raw", out_raw), ("out_smoothed", out_smoothed)):
+    def _ordered(self, device, fn, *args):
+        """capi.check(fn(*args)) for a call whose buffers are torch's device memory, ordered against torch's current stream."""
+        # The library enqueues on its own HIP stream.  Order it after the producer of the input on torch's current
+        # stream, and torch's current stream after the call, both on the device (no host sync).  Because
+        # the current stream waits for the analysis, anything torch later does with these blocks on that
+        # stream -- reading the results, freeing and recycling the input -- is ordered after the kernels that use
+        # them.  (Tensor.record_stream is deliberately not used: the allocator would record events on the
+        # library's stream when the tensors die, possibly after fx_destroy has destroyed that stream.)
+        # A caller that works ON the library's stream (`with torch.cuda.stream(analyser.torch_stream()):`) needs no ordering
+        # at all -- and the two waits are half of a one-hop call's cost from Python (25 of 56 us: tools/py_call_overhead.py).
+        import torch
+        cur = torch.cuda.current_stream(device)
+        lib = self._torch_stream(device)
+        foreign = cur.cuda_stream != lib.cuda_stream
+        if foreign:
+            lib.wait_stream(cur)
+        capi.check(fn(*args))
+        if foreign:
+            cur.wait_stream(lib)
+
+    def _analyse(self, entry, d, counts, frames, want_raw, want_smoothed, out_raw=None, out_smoothed=None, block=False):
+        """Results, ordering, call -- for every analysis entry point: library entry `entry` on the input d (_describe_input) with the
+        counts fx.h puts between the pointer and the format; raw / smoothed [C][frames][12] are numpy for host input and torch for a
+        device block (where out_raw / out_smoothed are used instead when given).  block: the entry takes any number of samples
+        (fx_push_samples, fx_push_interleaved) -- it reports its frames, which must be `frames`, and gets no result pointer for none."""
+        ptr, fmt, mem, _, _, device = d
+        shape = (self.num_channels, frames, 12)
+        if mem == capi.MEM_DEVICE:
+            raw, sm = out_raw, out_smoothed
+            for name, o in (("out_raw", raw), ("out_smoothed", sm)):
                 if o is not None:
-                    self._check_out(o, C * T * 12, name)
-            raw = out_raw if out_raw is not None else (torch.empty((C, T, 12), dtype=torch.float32, device=x.device) if want_raw else None)
-            sm = out_smoothed if out_smoothed is not None else (torch.empty((C, T, 12), dtype=torch.float32, device=x.device) if want_smoothed else None)
-            # The library enqueues on its own HIP stream.  Order it after the producer of x on torch's current
-            # stream, and torch's current stream after the analysis, both on the device (no host sync).  Because
-            # the current stream waits for the analysis, anything torch later does with these blocks on that
-            # stream -- reading the results, freeing and recycling x -- is ordered after the kernels that use
-            # them.  (Tensor.record_stream is deliberately not used: the allocator would record events on the
-            # library's stream when the tensors die, possibly after fx_destroy has destroyed that stream.)
-            # A caller that works ON the library's stream (`with torch.cuda.stream(analyser.torch_stream()):`) needs no ordering
-            # at all -- and the two waits are half of a one-hop call's cost from Python (25 of 56 us: tools/py_call_overhead.py).
-            cur = torch.cuda.current_stream(x.device)
-            lib = self._torch_stream(x.device)
-            foreign = cur.cuda_stream != lib.cuda_stream
-            if foreign:
-                lib.wait_stream(cur)
-            capi.check(fn(self._h, ctypes.c_void_p(x.data_ptr()), T, fmt, capi.MEM_DEVICE,
-                          ctypes.c_void_p(raw.data_ptr()) if raw is not None else None,
-                          ctypes.c_void_p(sm.data_ptr()) if sm is not None else None))
-            if foreign:
-                cur.wait_stream(lib)
-            return raw, sm
-        tagged = isinstance(x, PackedS24)
-        x = np.ascontiguousarray(x)
-        if x.dtype == np.float16:
-            fmt = capi.SAMPLE_F16
-        elif x.dtype == np.int16:
-            fmt = capi.SAMPLE_S16
-        elif x.dtype == np.uint8:
-            if not (tagged or want == capi.SAMPLE_S24):
-                raise ValueError(s24_error)
-            fmt = capi.SAMPLE_S24
-            per_frame = 3 * per_frame
+                    self._check_out(o, shape[0] * frames * 12, name)
+            if (raw is None and want_raw) or (sm is None and want_smoothed):
+                import torch
+                raw = torch.empty(shape, dtype=torch.float32, device=device) if raw is None and want_raw else raw
+                sm = torch.empty(shape, dtype=torch.float32, device=device) if sm is None and want_smoothed else sm
+            results = [ctypes.c_void_p(r.data_ptr()) if r is not None else None for r in (raw, sm)]
         else:
-            x = np.ascontiguousarray(x, np.float32)
-            fmt = capi.SAMPLE_F32
-        if want is not None and want != fmt:
-            raise ValueError("sample_format=%r does not describe a %s array" % (sample_format, x.dtype))
-        if x.size % (C * per_frame):
-            raise ValueError("input size is not a multiple of channels x samples per frame")
-        T = x.size // (C * per_frame)
-        raw = np.empty((C, T, 12), np.float32) if want_raw else None
-        sm = np.empty((C, T, 12), np.float32) if want_smoothed else None
-        capi.check(fn(self._h, x.ctypes.data_as(ctypes.c_void_p), T, fmt, capi.MEM_HOST,
-                      raw.ctypes.data_as(ctypes.c_void_p) if raw is not None else None,
-                      sm.ctypes.data_as(ctypes.c_void_p) if sm is not None else None))
+            raw = np.empty(shape, np.float32) if want_raw else None
+            sm = np.empty(shape, np.float32) if want_smoothed else None
+            results = [r.ctypes.data_as(ctypes.c_void_p) if r is not None else None for r in (raw, sm)]
+        if block and not frames:
+            results = [None, None]
+        args = (self._h, ptr) + counts + (fmt, mem, results[0], results[1])
+        if block:
+            frames_out = ctypes.c_int(0)
+            args += (ctypes.byref(frames_out),)
+        fn = getattr(self._lib, entry)
+        if mem == capi.MEM_DEVICE:
+            self._ordered(device, fn, *args)
+        else:
+            capi.check(fn(*args))
+        if block:
+            assert frames_out.value == frames
         return raw, sm
 
     def torch_stream(self):
@@ -362,23 +377,35 @@ class BatchAnalyser:
 
     def _torch_stream(self, device):
         """The library's hipStream_t as a torch stream (for device-side ordering against torch's streams)."""
-        import torch
-        if getattr(self, "_ext_stream", None) is None:
-            self._ext_stream = torch.cuda.ExternalStream(self.stream(), device=device)
-        return self._ext_stream
+        s = getattr(self, "_ext_stream", None)
+        if s is None:
+            import torch
+            s = self._ext_stream = torch.cuda.ExternalStream(self.stream(), device=device)
+        return s
 
     def _check_out(self, o, numel, name):
         if not (_is_torch(o) and o.is_cuda and o.device.index == self.device and o.is_contiguous()
                 and str(o.dtype) == "torch.float32" and o.numel() == numel):
             raise ValueError("%s must be a contiguous float32 CUDA tensor on cuda:%d with %d elements" % (name, self.device, numel))
 
+    def _frames(self, entry, x, per_frame, want_raw, want_smoothed, out_raw, out_smoothed, sample_format):
+        """Sample formats by dtype: float32, float16, int16 (16-bit PCM); packed 24-bit PCM (three bytes per sample) is a PackedS24
+        array (pack_s24) or any uint8 buffer passed with sample_format="s24" -- never inferred from dtype uint8 alone.  The integer
+        formats are widened in the kernels' load stage to exactly the floats a WAV reader would produce.  Device buffers must start
+        on a 16-byte boundary (fx.h)."""
+        d = _describe_input(x, sample_format, self.device, 16)
+        T, rest = divmod(d[3], self.num_channels * per_frame)
+        if rest:
+            raise ValueError("input size is not a multiple of channels x samples per frame")
+        return self._analyse(entry, d, (T,), T, want_raw, want_smoothed, out_raw, out_smoothed)
+
     def push_hops(self, hops, want_raw=True, want_smoothed=True, out_raw=None, out_smoothed=None, sample_format=None):
         """hops [C][T][N/2] -> (raw [C][T][12], smoothed [C][T][12])."""
-        return self._run(self._lib.fx_push_hops, hops, self.window_size // 2, want_raw, want_smoothed, out_raw, out_smoothed, sample_format)
+        return self._frames("fx_push_hops", hops, self.window_size // 2, want_raw, want_smoothed, out_raw, out_smoothed, sample_format)
 
     def process_frames(self, frames, want_raw=True, want_smoothed=True, out_raw=None, out_smoothed=None, sample_format=None):
         """frames [C][T][N] -> (raw [C][T][12], smoothed [C][T][12])."""
-        return self._run(self._lib.fx_process_frames, frames, self.window_size, want_raw, want_smoothed, out_raw, out_smoothed, sample_format)
+        return self._frames("fx_process_frames", frames, self.window_size, want_raw, want_smoothed, out_raw, out_smoothed, sample_format)
 
     # ---- the collector's interface: device blocks of any length (ref AudioDataCollector.h:36-94) ----
     def pending_samples(self):
@@ -391,68 +418,13 @@ class BatchAnalyser:
     def push_samples(self, samples, want_raw=True, want_smoothed=True, sample_format=None):
         """samples [C][n] for ANY n >= 0 (a device block: 441, 480, 512 ... samples per channel) -> (raw [C][frames][12], smoothed
         [C][frames][12]) with frames = (pending + n) // (window_size / 2); what is left over stays pending in device memory.  Same bits
-        as push_hops on the same stream cut into hops.  numpy (host) or torch CUDA tensors, formats as push_hops."""
-        C, H = self.num_channels, self.window_size // 2
-        if sample_format is not None and sample_format not in _FORMAT_NAMES:
-            raise ValueError("sample_format must be one of %s" % ", ".join(sorted(_FORMAT_NAMES)))
-        want = None if sample_format is None else _FORMAT_NAMES[sample_format]
-        frames_out = ctypes.c_int(0)
-        if _is_torch(samples):
-            import torch
-            x = samples
-            if not x.is_cuda or not x.is_contiguous() or x.device.index != self.device:
-                raise ValueError("torch input must be a contiguous tensor on cuda:%d" % self.device)
-            fmt = {torch.float32: capi.SAMPLE_F32, torch.float16: capi.SAMPLE_F16, torch.int16: capi.SAMPLE_S16, torch.uint8: capi.SAMPLE_S24}.get(x.dtype)
-            if fmt is None or (fmt == capi.SAMPLE_S24 and want != capi.SAMPLE_S24) or (want is not None and want != fmt):
-                raise ValueError("samples must be float32, float16, int16, or uint8 with sample_format=\"s24\"")
-            per = 3 if fmt == capi.SAMPLE_S24 else 1
-            if x.numel() % (C * per):
-                raise ValueError("input size is not a multiple of the channel count")
-            n = x.numel() // (C * per)
-            if x.data_ptr() % 4:
-                raise ValueError("device input must start on a 4-byte boundary")
-            frames = (self.pending_samples() + n) // H
-            raw = torch.empty((C, frames, 12), dtype=torch.float32, device=x.device) if want_raw else None
-            sm = torch.empty((C, frames, 12), dtype=torch.float32, device=x.device) if want_smoothed else None
-            cur = torch.cuda.current_stream(x.device)
-            lib = self._torch_stream(x.device)
-            foreign = cur.cuda_stream != lib.cuda_stream
-            if foreign:
-                lib.wait_stream(cur)
-            capi.check(self._lib.fx_push_samples(self._h, ctypes.c_void_p(x.data_ptr()), n, fmt, capi.MEM_DEVICE,
-                                                 ctypes.c_void_p(raw.data_ptr()) if raw is not None and frames else None,
-                                                 ctypes.c_void_p(sm.data_ptr()) if sm is not None and frames else None, ctypes.byref(frames_out)))
-            if foreign:
-                cur.wait_stream(lib)
-            assert frames_out.value == frames
-            return raw, sm
-        tagged = isinstance(samples, PackedS24)
-        x = np.ascontiguousarray(samples)
-        if x.dtype == np.float16:
-            fmt = capi.SAMPLE_F16
-        elif x.dtype == np.int16:
-            fmt = capi.SAMPLE_S16
-        elif x.dtype == np.uint8:
-            if not (tagged or want == capi.SAMPLE_S24):
-                raise ValueError('uint8 samples are packed 24-bit PCM only with sample_format="s24" (or as a PackedS24 array)')
-            fmt = capi.SAMPLE_S24
-        else:
-            x = np.ascontiguousarray(x, np.float32)
-            fmt = capi.SAMPLE_F32
-        if want is not None and want != fmt:
-            raise ValueError("sample_format=%r does not describe a %s array" % (sample_format, x.dtype))
-        per = 3 if fmt == capi.SAMPLE_S24 else 1
-        if x.size % (C * per):
+        as push_hops on the same stream cut into hops.  numpy (host) or torch CUDA tensors (from a 4-byte boundary), formats as push_hops."""
+        d = _describe_input(samples, sample_format, self.device, 4)
+        n, rest = divmod(d[3], self.num_channels)
+        if rest:
             raise ValueError("input size is not a multiple of the channel count")
-        n = x.size // (C * per)
-        frames = (self.pending_samples() + n) // H
-        raw = np.empty((C, frames, 12), np.float32) if want_raw else None
-        sm = np.empty((C, frames, 12), np.float32) if want_smoothed else None
-        capi.check(self._lib.fx_push_samples(self._h, x.ctypes.data_as(ctypes.c_void_p), n, fmt, capi.MEM_HOST,
-                                             raw.ctypes.data_as(ctypes.c_void_p) if raw is not None and frames else None,
-                                             sm.ctypes.data_as(ctypes.c_void_p) if sm is not None and frames else None, ctypes.byref(frames_out)))
-        assert frames_out.value == frames
-        return raw, sm
+        frames = (self.pending_samples() + n) // (self.window_size // 2)
+        return self._analyse("fx_push_samples", d, (n,), frames, want_raw, want_smoothed, block=True)
 
     # ---- interleaved input through a per-track channel map (include/fx.h, fx_set_channel_map / fx_push_interleaved) ----
     def set_channel_map(self, channel_map):
@@ -469,74 +441,19 @@ class BatchAnalyser:
     def push_interleaved(self, block, want_raw=True, want_smoothed=True, sample_format=None, num_source_channels=None):
         """block [n][K] of K source channels per frame (uint8 [n][3K] for s24; a flat block needs num_source_channels) -> (raw, smoothed)
         as push_samples returns them for the planar block [c][i] = block[i][map[c]].  numpy (host) or torch CUDA tensors."""
-        C, H = self.num_channels, self.window_size // 2
-        if sample_format is not None and sample_format not in _FORMAT_NAMES:
-            raise ValueError("sample_format must be one of %s" % ", ".join(sorted(_FORMAT_NAMES)))
-        want = None if sample_format is None else _FORMAT_NAMES[sample_format]
-        frames_out = ctypes.c_int(0)
-        if _is_torch(block):
-            import torch
-            x = block
-            if not x.is_cuda or not x.is_contiguous() or x.device.index != self.device:
-                raise ValueError("torch input must be a contiguous tensor on cuda:%d" % self.device)
-            fmt = {torch.float32: capi.SAMPLE_F32, torch.float16: capi.SAMPLE_F16, torch.int16: capi.SAMPLE_S16, torch.uint8: capi.SAMPLE_S24}.get(x.dtype)
-            if fmt is None or (fmt == capi.SAMPLE_S24 and want != capi.SAMPLE_S24) or (want is not None and want != fmt):
-                raise ValueError("samples must be float32, float16, int16, or uint8 with sample_format=\"s24\"")
-            n, K = interleaved_dims(tuple(x.shape), x.numel(), fmt, num_source_channels)
-            if x.data_ptr() % 4:
-                raise ValueError("device input must start on a 4-byte boundary")
-            frames = (self.pending_samples() + n) // H
-            raw = torch.empty((C, frames, 12), dtype=torch.float32, device=x.device) if want_raw else None
-            sm = torch.empty((C, frames, 12), dtype=torch.float32, device=x.device) if want_smoothed else None
-            cur = torch.cuda.current_stream(x.device)
-            lib = self._torch_stream(x.device)
-            foreign = cur.cuda_stream != lib.cuda_stream
-            if foreign:
-                lib.wait_stream(cur)
-            capi.check(self._lib.fx_push_interleaved(self._h, ctypes.c_void_p(x.data_ptr()), n, K, fmt, capi.MEM_DEVICE,
-                                                     ctypes.c_void_p(raw.data_ptr()) if raw is not None and frames else None,
-                                                     ctypes.c_void_p(sm.data_ptr()) if sm is not None and frames else None, ctypes.byref(frames_out)))
-            if foreign:
-                cur.wait_stream(lib)
-            assert frames_out.value == frames
-            return raw, sm
-        tagged = isinstance(block, PackedS24)
-        x = np.ascontiguousarray(block)
-        if x.dtype == np.float16:
-            fmt = capi.SAMPLE_F16
-        elif x.dtype == np.int16:
-            fmt = capi.SAMPLE_S16
-        elif x.dtype == np.uint8:
-            if not (tagged or want == capi.SAMPLE_S24):
-                raise ValueError('uint8 samples are packed 24-bit PCM only with sample_format="s24" (or as a PackedS24 array)')
-            fmt = capi.SAMPLE_S24
-        else:
-            x = np.ascontiguousarray(x, np.float32)
-            fmt = capi.SAMPLE_F32
-        if want is not None and want != fmt:
-            raise ValueError("sample_format=%r does not describe a %s array" % (sample_format, x.dtype))
-        n, K = interleaved_dims(x.shape, x.size, fmt, num_source_channels)
-        frames = (self.pending_samples() + n) // H
-        raw = np.empty((C, frames, 12), np.float32) if want_raw else None
-        sm = np.empty((C, frames, 12), np.float32) if want_smoothed else None
-        capi.check(self._lib.fx_push_interleaved(self._h, x.ctypes.data_as(ctypes.c_void_p), n, K, fmt, capi.MEM_HOST,
-                                                 raw.ctypes.data_as(ctypes.c_void_p) if raw is not None and frames else None,
-                                                 sm.ctypes.data_as(ctypes.c_void_p) if sm is not None and frames else None, ctypes.byref(frames_out)))
-        assert frames_out.value == frames
-        return raw, sm
+        d = _describe_input(block, sample_format, self.device, 4)
+        _, fmt, _, count, keep, _ = d
+        n, K = interleaved_dims(tuple(keep.shape), count * (3 if fmt == capi.SAMPLE_S24 else 1), fmt, num_source_channels)
+        frames = (self.pending_samples() + n) // (self.window_size // 2)
+        return self._analyse("fx_push_interleaved", d, (n, K), frames, want_raw, want_smoothed, block=True)
 
     def get_features(self, out=None):
         """Latest AudioFeatures::getValue of every slot, [C][12]: a host array, or -- with `out`, a contiguous
         float32 CUDA tensor of that shape -- an asynchronous device copy on the library's stream (what the OSC
         sink of a sharded run gathers)."""
         if out is not None:
-            import torch
             self._check_out(out, self.num_channels * 12, "out")
-            cur = torch.cuda.current_stream(out.device)
-            lib = self._torch_stream(out.device)
-            lib.wait_stream(cur)
-            capi.check(self._lib.fx_get_smoothed(self._h, ctypes.c_void_p(out.data_ptr()), capi.MEM_DEVICE))
-            cur.wait_stream(lib)
+            self._ordered(out.device, self._lib.fx_get_smoothed, self._h, ctypes.c_void_p(out.data_ptr()), capi.MEM_DEVICE)
             return out
         out = np.empty((self.num_channels, 12), np.float32)
         capi.check(self._lib.fx_get_smoothed(self._h, out.ctypes.data_as(ctypes.c_void_p), capi.MEM_HOST))
@@ -636,9 +553,9 @@ class HopStream:
         self.hops = int(hops_per_batch)
         self.slots = int(slots)
         self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float16), np.dtype(np.int16), np.dtype(np.uint8)):
+        fmt = _DTYPE_FORMATS.get(self.dtype)
+        if fmt is None:
             raise ValueError("HopStream samples are float32, float16, int16 (16-bit PCM) or uint8 (packed 24-bit PCM, three bytes per sample)")
-        fmt = {np.dtype(np.float16): capi.SAMPLE_F16, np.dtype(np.int16): capi.SAMPLE_S16, np.dtype(np.uint8): capi.SAMPLE_S24}.get(self.dtype, capi.SAMPLE_F32)
         h = ctypes.c_void_p()
         capi.check(self._lib.fx_stream_create(analyser._h, self.hops, self.slots, fmt, ctypes.byref(h)))
         self._h = h

@@ -17,26 +17,6 @@ MEM_HOST, MEM_DEVICE = 0, 1
 SAMPLE_F32, SAMPLE_F16, SAMPLE_S16, SAMPLE_S24 = 0, 1, 2, 3
 FX_OK, FX_ERR_INVALID_ARGUMENT, FX_ERR_NO_DEVICE, FX_ERR_HIP, FX_ERR_OUT_OF_MEMORY, FX_ERR_UNSUPPORTED = range(6)
 
-# every symbol include/fx.h declares
-EXPORTS = ["fx_create", "fx_destroy", "fx_reset_state", "fx_set_sample_rate", "fx_set_onset_sensitivity",
-           "fx_set_onset_window", "fx_set_onset_type", "fx_set_gain", "fx_push_hops", "fx_process_frames",
-           "fx_push_samples", "fx_pending_samples", "fx_clear_pending", "fx_stream_submit_samples", "fx_stream_push_samples", "fx_stream_collect_samples",
-           "fx_get_smoothed", "fx_sync", "fx_get_stream", "fx_last_kernel_ms", "fx_profile_begin", "fx_profile_end",
-           "fx_stream_create", "fx_stream_destroy", "fx_stream_acquire", "fx_stream_submit", "fx_stream_push", "fx_stream_collect", "fx_stream_in_flight", "fx_pack_osc12",
-           "fx_pack_osc10", "fx_osc_encode", "fx_last_error", "fx_abi_version",
-           "fx_host_alloc", "fx_host_free", "fx_osc_message_bytes", "fx_osc_encode_batch", "fx_get_osc_datagrams", "fx_osc_sender_create", "fx_osc_sender_destroy", "fx_osc_sender_update",
-           "fx_osc_sender_send", "fx_osc_sender_start", "fx_osc_sender_stop", "fx_osc_sender_get_stats", "fx_osc_receiver_create", "fx_osc_receiver_destroy",
-           "fx_osc_receiver_port", "fx_osc_receiver_get_stats", "fx_osc_receiver_last",
-           "fx_comm_unique_id", "fx_comm_create", "fx_comm_destroy", "fx_comm_layout", "fx_gather_smoothed", "fx_comm_sync", "fx_comm_stats",
-           "fx_plan_units", "fx_twiddle_symmetry", "fx_tuning_defaults", "fx_tuning_from_env", "fx_get_tuning", "fx_set_tuning",
-           "fx_offline_create", "fx_offline_destroy", "fx_offline_reset", "fx_offline_sync", "fx_offline_get_previous_f0", "fx_offline_zero_crosses",
-           "fx_offline_log_attack_time", "fx_offline_fft_lbp", "fx_offline_harmonic_characteristics", "fx_offline_spectral_characteristics",
-           "fx_offline_get_previous_bins", "fx_offline_spectral_slope", "fx_offline_auto_correlation",
-           "fx_request_taps", "fx_get_taps", "fx_set_channel_map", "fx_push_interleaved",
-           "fx_set_channel_gains", "fx_set_channel_onset", "fx_get_channel_settings",
-           "fx_enable_onset_events", "fx_get_onset_events",
-           "fx_reset_channels", "fx_clear_pending_channels", "fx_get_channel_frames",
-           "fx_set_osc_addresses", "fx_osc_address_stride", "fx_get_osc_datagrams_addressed", "fx_osc_encode_addressed", "fx_osc_sender_set_routes"]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
 MAX_UNITS = 24
@@ -97,6 +77,60 @@ class Tuning(ctypes.Structure):
         return self
 
 
+def _prototypes():
+    vp, i, u, f, d, ll, cp = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_double, ctypes.c_longlong, ctypes.c_char_p
+    P = ctypes.POINTER
+    vpp, ip, fp, dp, llp, tp, strings = P(vp), P(i), P(f), P(d), P(ll), P(Tuning), P(cp)
+    st = i                  # fx_status and int: ctypes' default restype
+    return [
+        ("fx_create", [vpp, i, i, i, d, u], st), ("fx_destroy", [vp], st), ("fx_reset_state", [vp], st),
+        ("fx_set_sample_rate", [vp, d], st), ("fx_set_onset_sensitivity", [vp, f], st), ("fx_set_onset_window", [vp, i], st),
+        ("fx_set_onset_type", [vp, i], st), ("fx_set_gain", [vp, f], st),
+        ("fx_set_channel_gains", [vp, fp], st), ("fx_set_channel_onset", [vp, fp, ip, ip], st), ("fx_get_channel_settings", [vp, fp, fp, ip, ip], st),
+        ("fx_reset_channels", [vp, ip, i], st), ("fx_clear_pending_channels", [vp, ip, i], st), ("fx_get_channel_frames", [vp, llp], st),
+        ("fx_push_hops", [vp, vp, i, i, i, vp, vp], st), ("fx_push_samples", [vp, vp, i, i, i, vp, vp, ip], st),
+        ("fx_set_channel_map", [vp, ip], st), ("fx_push_interleaved", [vp, vp, i, i, i, i, vp, vp, ip], st),
+        ("fx_pending_samples", [vp], st), ("fx_clear_pending", [vp], st), ("fx_process_frames", [vp, vp, i, i, i, vp, vp], st),
+        ("fx_get_smoothed", [vp, vp, i], st), ("fx_host_alloc", [vpp, ctypes.c_size_t], st), ("fx_host_free", [vp], st),
+        ("fx_sync", [vp], st), ("fx_get_stream", [vp, vpp], st), ("fx_last_kernel_ms", [vp, fp, fp], st),
+        ("fx_request_taps", [vp, ip, i], st), ("fx_get_taps", [vp, i, fp, fp, fp, fp, fp, fp, llp], st),
+        ("fx_enable_onset_events", [vp, i], st), ("fx_get_onset_events", [vp, vp, i, ip, llp], st),
+        ("fx_stream_create", [vp, i, i, i, vpp], st), ("fx_stream_destroy", [vp], st), ("fx_stream_acquire", [vp, vpp], st),
+        ("fx_stream_submit", [vp], st), ("fx_stream_push", [vp, vp, i], st), ("fx_stream_collect", [vp, vp, vp], st),
+        ("fx_stream_submit_samples", [vp, i], st), ("fx_stream_push_samples", [vp, vp, i, i], st),
+        ("fx_stream_collect_samples", [vp, vp, vp, ip], st), ("fx_stream_in_flight", [vp], st),
+        ("fx_tuning_defaults", [tp], None), ("fx_tuning_from_env", [tp], None), ("fx_get_tuning", [vp, tp], st), ("fx_set_tuning", [vp, tp], st),
+        ("fx_plan_units", [i, u, i, i, tp, ip, i], st), ("fx_twiddle_symmetry", [i], st),
+        ("fx_profile_begin", [vp], st), ("fx_profile_end", [vp, dp, dp, ip], st),
+        ("fx_comm_unique_id", [vp, i], st), ("fx_comm_create", [vp, i, i, vp, i], st), ("fx_comm_destroy", [vp], st),
+        ("fx_comm_layout", [vp, ip, ip], st), ("fx_gather_smoothed", [vp, i, vp, i], st), ("fx_comm_sync", [vp], st),
+        ("fx_comm_stats", [vp, ip, ip, ip, dp, dp], st),
+        ("fx_offline_create", [vpp, i, i, d], st), ("fx_offline_destroy", [vp], st), ("fx_offline_reset", [vp], st), ("fx_offline_sync", [vp], st),
+        ("fx_offline_get_previous_f0", [vp, dp], st), ("fx_offline_zero_crosses", [vp, vp, i, i, vp, i], st),
+        ("fx_offline_log_attack_time", [vp, vp, i, i, i, i, vp, i], st), ("fx_offline_fft_lbp", [vp, vp, vp, i, vp, vp, vp, i], st),
+        ("fx_offline_harmonic_characteristics", [vp, vp, i, vp, i], st), ("fx_offline_spectral_characteristics", [vp, vp, i, vp, i], st),
+        ("fx_offline_get_previous_bins", [vp, dp, i], st), ("fx_offline_spectral_slope", [vp, vp, i, vp, i], st),
+        ("fx_offline_auto_correlation", [vp, vp, i, vp, vp, i], st),
+        ("fx_pack_osc12", [fp, fp], None), ("fx_pack_osc10", [fp, fp], None), ("fx_osc_encode", [cp, fp, P(ctypes.c_ubyte), i], st),
+        ("fx_osc_message_bytes", [cp, i], st), ("fx_osc_encode_batch", [cp, i, i, fp, vp, i, ip], st),
+        ("fx_get_osc_datagrams", [vp, cp, i, vp, i, ip, i], st),
+        ("fx_set_osc_addresses", [vp, strings], st), ("fx_osc_address_stride", [vp], st), ("fx_get_osc_datagrams_addressed", [vp, vp, i, ip, i], st),
+        ("fx_osc_encode_addressed", [strings, i, fp, vp, i, ip], st),
+        ("fx_osc_sender_create", [vpp, cp, cp, i, u], st), ("fx_osc_sender_destroy", [vp], st), ("fx_osc_sender_update", [vp, vp, i, ip, i], st),
+        ("fx_osc_sender_send", [vp, llp], st), ("fx_osc_sender_start", [vp, d], st), ("fx_osc_sender_stop", [vp], st),
+        ("fx_osc_sender_get_stats", [vp, P(OscSenderStats)], st), ("fx_osc_sender_set_routes", [vp, strings, i, ip, ip, i], st),
+        ("fx_osc_receiver_create", [vpp, cp, i, cp, i, u], st), ("fx_osc_receiver_destroy", [vp], st), ("fx_osc_receiver_port", [vp], st),
+        ("fx_osc_receiver_get_stats", [vp, llp, llp, llp], st), ("fx_osc_receiver_last", [vp, i, vp, i, ip], st),
+        ("fx_last_error", [], cp), ("fx_abi_version", [], st),
+    ], [("fx_set_tuning_internal", [vp, u], st), ("fx_last_launches_internal", [vp, vp, i], st)]
+
+
+# (name, argument types, restype) of every symbol include/fx.h declares, in its order -- and, apart, of the two test entries of
+# csrc/fx_kernels.h; load_library() gives each function of the library its prototype from here
+PROTOTYPES, INTERNAL_PROTOTYPES = _prototypes()
+EXPORTS = [name for name, _, _ in PROTOTYPES]
+
+
 class FxError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("fx error %d: %s" % (code, message))
@@ -131,107 +165,9 @@ def load_library(build_if_missing=True):
     except ImportError:
         pass
     L = ctypes.CDLL(library_path())
-    vp, fp, i, d, f, u = ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.c_uint
-    L.fx_create.argtypes = [ctypes.POINTER(vp), i, i, i, d, u]
-    L.fx_destroy.argtypes = [vp]
-    L.fx_reset_state.argtypes = [vp]
-    L.fx_set_sample_rate.argtypes = [vp, d]
-    L.fx_set_onset_sensitivity.argtypes = [vp, f]
-    L.fx_set_onset_window.argtypes = [vp, i]
-    L.fx_set_onset_type.argtypes = [vp, i]
-    L.fx_set_gain.argtypes = [vp, f]
-    L.fx_push_hops.argtypes = [vp, vp, i, i, i, vp, vp]
-    L.fx_process_frames.argtypes = [vp, vp, i, i, i, vp, vp]
-    L.fx_push_samples.argtypes = [vp, vp, i, i, i, vp, vp, ctypes.POINTER(i)]
-    L.fx_pending_samples.argtypes = [vp]
-    L.fx_clear_pending.argtypes = [vp]
-    L.fx_stream_submit_samples.argtypes = [vp, i]
-    L.fx_stream_push_samples.argtypes = [vp, vp, i, i]
-    L.fx_stream_collect_samples.argtypes = [vp, vp, vp, ctypes.POINTER(i)]
-    L.fx_get_smoothed.argtypes = [vp, vp, i]
-    L.fx_sync.argtypes = [vp]
-    L.fx_get_stream.argtypes = [vp, ctypes.POINTER(vp)]
-    L.fx_last_kernel_ms.argtypes = [vp, fp, fp]
-    L.fx_stream_create.argtypes = [vp, i, i, i, ctypes.POINTER(vp)]
-    L.fx_stream_destroy.argtypes = [vp]
-    L.fx_stream_acquire.argtypes = [vp, ctypes.POINTER(vp)]
-    L.fx_stream_submit.argtypes = [vp]
-    L.fx_stream_push.argtypes = [vp, vp, i]
-    L.fx_stream_collect.argtypes = [vp, vp, vp]
-    L.fx_stream_in_flight.argtypes = [vp]
-    L.fx_profile_begin.argtypes = [vp]
-    L.fx_profile_end.argtypes = [vp, ctypes.POINTER(d), ctypes.POINTER(d), ctypes.POINTER(i)]
-    L.fx_comm_unique_id.argtypes = [vp, i]
-    L.fx_comm_create.argtypes = [vp, i, i, vp, i]
-    L.fx_comm_destroy.argtypes = [vp]
-    L.fx_comm_layout.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(i)]
-    L.fx_gather_smoothed.argtypes = [vp, i, vp, i]
-    L.fx_comm_sync.argtypes = [vp]
-    L.fx_comm_stats.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(d), ctypes.POINTER(d)]
-    L.fx_request_taps.argtypes = [vp, ctypes.POINTER(i), i]
-    L.fx_set_channel_map.argtypes = [vp, ctypes.POINTER(i)]
-    L.fx_set_channel_gains.argtypes = [vp, fp]
-    L.fx_set_channel_onset.argtypes = [vp, fp, ctypes.POINTER(i), ctypes.POINTER(i)]
-    L.fx_get_channel_settings.argtypes = [vp, fp, fp, ctypes.POINTER(i), ctypes.POINTER(i)]
-    L.fx_push_interleaved.argtypes = [vp, vp, i, i, i, i, vp, vp, ctypes.POINTER(i)]
-    L.fx_reset_channels.argtypes = [vp, ctypes.POINTER(i), i]
-    L.fx_clear_pending_channels.argtypes = [vp, ctypes.POINTER(i), i]
-    L.fx_get_channel_frames.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
-    L.fx_enable_onset_events.argtypes = [vp, i]
-    L.fx_get_onset_events.argtypes = [vp, vp, i, ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
-    L.fx_get_taps.argtypes = [vp, i, fp, fp, fp, fp, fp, fp, ctypes.POINTER(ctypes.c_longlong)]
-    L.fx_plan_units.argtypes = [i, u, i, i, ctypes.POINTER(Tuning), ctypes.POINTER(i), i]
-    L.fx_twiddle_symmetry.argtypes = [i]
-    L.fx_tuning_defaults.argtypes = [ctypes.POINTER(Tuning)]
-    L.fx_tuning_defaults.restype = None
-    L.fx_tuning_from_env.argtypes = [ctypes.POINTER(Tuning)]
-    L.fx_tuning_from_env.restype = None
-    L.fx_get_tuning.argtypes = [vp, ctypes.POINTER(Tuning)]
-    L.fx_set_tuning.argtypes = [vp, ctypes.POINTER(Tuning)]
-    L.fx_offline_create.argtypes = [ctypes.POINTER(vp), i, i, d]
-    L.fx_offline_destroy.argtypes = [vp]
-    L.fx_offline_reset.argtypes = [vp]
-    L.fx_offline_sync.argtypes = [vp]
-    L.fx_offline_get_previous_f0.argtypes = [vp, ctypes.POINTER(d)]
-    L.fx_offline_zero_crosses.argtypes = [vp, vp, i, i, vp, i]
-    L.fx_offline_log_attack_time.argtypes = [vp, vp, i, i, i, i, vp, i]
-    L.fx_offline_fft_lbp.argtypes = [vp, vp, vp, i, vp, vp, vp, i]
-    L.fx_offline_harmonic_characteristics.argtypes = [vp, vp, i, vp, i]
-    L.fx_offline_spectral_characteristics.argtypes = [vp, vp, i, vp, i]
-    L.fx_offline_get_previous_bins.argtypes = [vp, ctypes.POINTER(d), i]
-    L.fx_offline_spectral_slope.argtypes = [vp, vp, i, vp, i]
-    L.fx_offline_auto_correlation.argtypes = [vp, vp, i, vp, vp, i]
-    L.fx_pack_osc12.argtypes = [fp, fp]
-    L.fx_pack_osc12.restype = None
-    L.fx_pack_osc10.argtypes = [fp, fp]
-    L.fx_pack_osc10.restype = None
-    L.fx_osc_encode.argtypes = [ctypes.c_char_p, fp, ctypes.POINTER(ctypes.c_ubyte), i]
-    ip = ctypes.POINTER(i)
-    ll = ctypes.c_longlong
-    L.fx_host_alloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
-    L.fx_host_free.argtypes = [vp]
-    L.fx_osc_message_bytes.argtypes = [ctypes.c_char_p, i]
-    L.fx_osc_encode_batch.argtypes = [ctypes.c_char_p, i, i, fp, vp, i, ip]
-    L.fx_get_osc_datagrams.argtypes = [vp, ctypes.c_char_p, i, vp, i, ip, i]
-    strings = ctypes.POINTER(ctypes.c_char_p)
-    L.fx_set_osc_addresses.argtypes = [vp, strings]
-    L.fx_osc_address_stride.argtypes = [vp]
-    L.fx_get_osc_datagrams_addressed.argtypes = [vp, vp, i, ip, i]
-    L.fx_osc_encode_addressed.argtypes = [strings, i, fp, vp, i, ip]
-    L.fx_osc_sender_set_routes.argtypes = [vp, strings, i, ip, ip, i]
-    L.fx_osc_sender_create.argtypes = [ctypes.POINTER(vp), ctypes.c_char_p, ctypes.c_char_p, i, u]
-    L.fx_osc_sender_destroy.argtypes = [vp]
-    L.fx_osc_sender_update.argtypes = [vp, vp, i, ip, i]
-    L.fx_osc_sender_send.argtypes = [vp, ctypes.POINTER(ll)]
-    L.fx_osc_sender_start.argtypes = [vp, d]
-    L.fx_osc_sender_stop.argtypes = [vp]
-    L.fx_osc_sender_get_stats.argtypes = [vp, ctypes.POINTER(OscSenderStats)]
-    L.fx_osc_receiver_create.argtypes = [ctypes.POINTER(vp), ctypes.c_char_p, i, ctypes.c_char_p, i, u]
-    L.fx_osc_receiver_destroy.argtypes = [vp]
-    L.fx_osc_receiver_port.argtypes = [vp]
-    L.fx_osc_receiver_get_stats.argtypes = [vp, ctypes.POINTER(ll), ctypes.POINTER(ll), ctypes.POINTER(ll)]
-    L.fx_osc_receiver_last.argtypes = [vp, i, vp, i, ip]
-    L.fx_last_error.restype = ctypes.c_char_p
+    for name, argtypes, restype in PROTOTYPES + INTERNAL_PROTOTYPES:
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = argtypes, restype
     _lib = L
     return L
 
