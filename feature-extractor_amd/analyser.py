@@ -237,7 +237,8 @@ class BatchAnalyser:
 
     def last_launches(self):
         """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
-        (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events, osc_table)."""
+        (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events, osc_table,
+        osc_bundle)."""
         cap = capi.LAUNCH_RECORD_CAP
         buf = (ctypes.c_int * (cap * len(capi.LAUNCH_FIELDS)))()
         n = self._lib.fx_last_launches_internal(self._h, buf, cap)
@@ -490,6 +491,34 @@ class BatchAnalyser:
         lengths = np.empty(self.num_channels, np.int32)
         capi.check(self._lib.fx_get_osc_datagrams(self._h, prefix.encode(), int(first_channel), out.ctypes.data_as(ctypes.c_void_p), stride,
                                                   lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), capi.MEM_HOST))
+        return out, lengths
+
+    def osc_bundles(self, prefix="/Audio/A", first_channel=0, addressed=False, timetag=capi.OSC_TIMETAG_IMMEDIATE, max_datagram_bytes=1472, device=False):
+        """fx_get_osc_bundles: the same messages as OSC 1.0 bundles, K tracks per datagram (capi.osc_bundle_plan), formed on the device in
+        one launch.  Returns (bundles uint8 [B][stride], lengths int32 [B]); datagram b = bundles[b, :lengths[b]].  addressed=True:
+        fx_get_osc_bundles_addressed, the addresses of set_osc_addresses.  device=True: the bundles stay on the GPU, a torch uint8
+        tensor written asynchronously on the library's stream."""
+        longest = self.osc_address_stride() if addressed else capi.osc_stride(prefix, first_channel, self.num_channels)
+        if longest < 0:
+            raise capi.FxError(capi.FX_ERR_INVALID_ARGUMENT, "the context has no OSC address table (set_osc_addresses)")
+        _, bundles, stride = capi.osc_bundle_plan(longest, self.num_channels, max_datagram_bytes)
+        lengths = np.empty(bundles, np.int32)
+        lp = lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        if device:
+            import torch
+            out = torch.empty((bundles, stride), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            ptr, kind = ctypes.c_void_p(out.data_ptr()), capi.MEM_DEVICE
+        else:
+            out = np.empty((bundles, stride), np.uint8)
+            ptr, kind = out.ctypes.data_as(ctypes.c_void_p), capi.MEM_HOST
+        if addressed:
+            args = (self._lib.fx_get_osc_bundles_addressed, self._h, int(timetag), int(max_datagram_bytes), ptr, stride, lp, kind)
+        else:
+            args = (self._lib.fx_get_osc_bundles, self._h, prefix.encode(), int(first_channel), int(timetag), int(max_datagram_bytes), ptr, stride, lp, kind)
+        if device:
+            self._ordered(out.device, *args)
+        else:
+            capi.check(args[0](*args[1:]))
         return out, lengths
 
     # ---- multi-GPU: gather of the latest smoothed vectors to the OSC sink rank (RCCL, through the C ABI) ----

@@ -24,10 +24,12 @@ MAX_UNITS = 24
 LAUNCH_FIELDS = ["kind", "window", "analysers", "T", "direct_state", "block_mode", "num_chunks", "ch_per_wg", "waves_per_ch", "hop_pairs",
                  "ep_T", "out_stride", "ep_form", "reblock"]
 LAUNCH_KINDS = {1: "frame", 2: "frame_tail", 3: "hop", 4: "hop_pair", 5: "pair", 6: "epilogue", 7: "reblock", 8: "osc", 9: "taps",
-                10: "deinterleave", 11: "onset_events", 12: "osc_table"}
+                10: "deinterleave", 11: "onset_events", 12: "osc_table", 13: "osc_bundle"}
 MAX_TAP_CHANNELS = 64
 OSC_ADDRESS_MAX = 124               # FX_OSC_ADDRESS_MAX
 OSC_SENDER_MAX_TARGETS = 64         # FX_OSC_SENDER_MAX_TARGETS
+OSC_BUNDLE_MAX_ELEMENTS = 1024      # FX_OSC_BUNDLE_MAX_ELEMENTS
+OSC_TIMETAG_IMMEDIATE = 1           # FX_OSC_TIMETAG_IMMEDIATE
 LAUNCH_RECORD_CAP = 8
 
 
@@ -81,6 +83,7 @@ def _prototypes():
     vp, i, u, f, d, ll, cp = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_double, ctypes.c_longlong, ctypes.c_char_p
     P = ctypes.POINTER
     vpp, ip, fp, dp, llp, tp, strings = P(vp), P(i), P(f), P(d), P(ll), P(Tuning), P(cp)
+    ull = ctypes.c_ulonglong
     st = i                  # fx_status and int: ctypes' default restype
     return [
         ("fx_create", [vpp, i, i, i, d, u], st), ("fx_destroy", [vp], st), ("fx_reset_state", [vp], st),
@@ -116,11 +119,15 @@ def _prototypes():
         ("fx_get_osc_datagrams", [vp, cp, i, vp, i, ip, i], st),
         ("fx_set_osc_addresses", [vp, strings], st), ("fx_osc_address_stride", [vp], st), ("fx_get_osc_datagrams_addressed", [vp, vp, i, ip, i], st),
         ("fx_osc_encode_addressed", [strings, i, fp, vp, i, ip], st),
+        ("fx_osc_bundle_plan", [i, i, i, ip, ip, ip], st), ("fx_osc_timetag", [d], st),
+        ("fx_osc_encode_bundles", [cp, i, i, fp, ull, i, vp, i, ip], st), ("fx_osc_encode_bundles_addressed", [strings, i, fp, ull, i, vp, i, ip], st),
+        ("fx_get_osc_bundles", [vp, cp, i, ull, i, vp, i, ip, i], st), ("fx_get_osc_bundles_addressed", [vp, ull, i, vp, i, ip, i], st),
         ("fx_osc_sender_create", [vpp, cp, cp, i, u], st), ("fx_osc_sender_destroy", [vp], st), ("fx_osc_sender_update", [vp, vp, i, ip, i], st),
         ("fx_osc_sender_send", [vp, llp], st), ("fx_osc_sender_start", [vp, d], st), ("fx_osc_sender_stop", [vp], st),
         ("fx_osc_sender_get_stats", [vp, P(OscSenderStats)], st), ("fx_osc_sender_set_routes", [vp, strings, i, ip, ip, i], st),
         ("fx_osc_receiver_create", [vpp, cp, i, cp, i, u], st), ("fx_osc_receiver_destroy", [vp], st), ("fx_osc_receiver_port", [vp], st),
-        ("fx_osc_receiver_get_stats", [vp, llp, llp, llp], st), ("fx_osc_receiver_last", [vp, i, vp, i, ip], st),
+        ("fx_osc_receiver_get_stats", [vp, llp, llp, llp], st), ("fx_osc_receiver_get_bundle_stats", [vp, llp, llp, P(ull)], st),
+        ("fx_osc_receiver_last", [vp, i, vp, i, ip], st),
         ("fx_last_error", [], cp), ("fx_abi_version", [], st),
     ], [("fx_set_tuning_internal", [vp, u], st), ("fx_last_launches_internal", [vp, vp, i], st)]
 
@@ -214,6 +221,7 @@ def osc_encode(address, features12):
 
 OSC_SENDER_GSO = 1
 OSC_RECEIVER_NO_GRO = 1
+OSC_RECEIVER_BUNDLES = 2
 
 
 def osc_message_bytes(prefix, channel):
@@ -265,6 +273,57 @@ def osc_encode_addressed(addresses, smoothed, stride=None):
     n = load_library().fx_osc_encode_addressed(c_strings(addresses), v.shape[0], _fp(v), out.ctypes.data_as(ctypes.c_void_p), stride,
                                                lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
     if n != v.shape[0]:
+        raise FxError(FX_ERR_INVALID_ARGUMENT, load_library().fx_last_error().decode(errors="replace"))
+    return out, lengths
+
+
+def osc_bundle_plan(longest_message_bytes, num_tracks, max_datagram_bytes=1472):
+    """fx_osc_bundle_plan: (tracks per bundle K, number of bundles, stride) of a call's bundles"""
+    k, b, stride = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(load_library().fx_osc_bundle_plan(int(longest_message_bytes), int(num_tracks), int(max_datagram_bytes), ctypes.byref(k), ctypes.byref(b), ctypes.byref(stride)))
+    return k.value, b.value, stride.value
+
+
+_timetag_fn = None
+
+
+def osc_timetag(unix_seconds):
+    """fx_osc_timetag: the OSC 1.0 time tag (NTP seconds since 1900 << 32 | fraction) of a Unix time.  The one entry of fx.h that
+    returns 64 bits: the prototype table's restype column is int for every status-returning entry (tests/test_binding_inputs_cpu.py
+    holds it to that), so this call goes through a foreign-function object of its own with the true return type."""
+    global _timetag_fn
+    if _timetag_fn is None:
+        _timetag_fn = ctypes.CFUNCTYPE(ctypes.c_ulonglong, ctypes.c_double)(("fx_osc_timetag", load_library()))
+    return int(_timetag_fn(float(unix_seconds)))
+
+
+def _bundle_buffers(longest, num_tracks, max_datagram_bytes, stride):
+    _, bundles, need = osc_bundle_plan(longest, num_tracks, max_datagram_bytes)
+    stride = need if stride is None else int(stride)
+    return np.empty((bundles, max(stride, 0)), np.uint8), np.empty(bundles, np.int32), stride
+
+
+def osc_encode_bundles(prefix, first_channel, smoothed, timetag=OSC_TIMETAG_IMMEDIATE, max_datagram_bytes=1472, stride=None):
+    """fx_osc_encode_bundles: (bundles uint8 [B][stride], lengths int32 [B]) for smoothed [n][12]; datagram b = bundles[b, :lengths[b]]"""
+    v = np.ascontiguousarray(smoothed, np.float32).reshape(-1, 12)
+    out, lengths, stride = _bundle_buffers(osc_stride(prefix, first_channel, v.shape[0]), v.shape[0], max_datagram_bytes, stride)
+    n = load_library().fx_osc_encode_bundles(prefix.encode(), int(first_channel), v.shape[0], _fp(v), int(timetag), int(max_datagram_bytes),
+                                             out.ctypes.data_as(ctypes.c_void_p), stride, lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+    if n != out.shape[0]:
+        raise FxError(FX_ERR_INVALID_ARGUMENT, load_library().fx_last_error().decode(errors="replace"))
+    return out, lengths
+
+
+def osc_encode_bundles_addressed(addresses, smoothed, timetag=OSC_TIMETAG_IMMEDIATE, max_datagram_bytes=1472, stride=None):
+    """fx_osc_encode_bundles_addressed: the same with one address per track"""
+    v = np.ascontiguousarray(smoothed, np.float32).reshape(-1, 12)
+    addresses = list(addresses)
+    if len(addresses) != v.shape[0]:
+        raise ValueError("one address per track (%d), not %d" % (v.shape[0], len(addresses)))
+    out, lengths, stride = _bundle_buffers(max(osc_address_bytes(a) for a in addresses), v.shape[0], max_datagram_bytes, stride)
+    n = load_library().fx_osc_encode_bundles_addressed(c_strings(addresses), v.shape[0], _fp(v), int(timetag), int(max_datagram_bytes),
+                                                       out.ctypes.data_as(ctypes.c_void_p), stride, lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+    if n != out.shape[0]:
         raise FxError(FX_ERR_INVALID_ARGUMENT, load_library().fx_last_error().decode(errors="replace"))
     return out, lengths
 
@@ -329,17 +388,23 @@ class OscSender:
 class OscReceiver:
     """fx_osc_receiver: counts OSC feature messages arriving on a local UDP port (tests, benchmarks, soak runs)."""
 
-    def __init__(self, bind="127.0.0.1:0", threads=1, prefix=None, keep_channels=0, gro=True):
+    def __init__(self, bind="127.0.0.1:0", threads=1, prefix=None, keep_channels=0, gro=True, bundles=False):
         self._lib = load_library()
         self._h = ctypes.c_void_p()
         check(self._lib.fx_osc_receiver_create(ctypes.byref(self._h), bind.encode(), int(threads), prefix.encode() if prefix else None, int(keep_channels),
-                                               0 if gro else OSC_RECEIVER_NO_GRO))
+                                               (0 if gro else OSC_RECEIVER_NO_GRO) | (OSC_RECEIVER_BUNDLES if bundles else 0)))
         self.port = self._lib.fx_osc_receiver_port(self._h)
 
     def stats(self):
         a, b, c = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_longlong(0)
         check(self._lib.fx_osc_receiver_get_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return {"datagrams": a.value, "bytes": b.value, "malformed": c.value}
+
+    def bundle_stats(self):
+        """fx_osc_receiver_get_bundle_stats (a receiver made with bundles=True)"""
+        a, b, t = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_ulonglong(0)
+        check(self._lib.fx_osc_receiver_get_bundle_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(t)))
+        return {"bundles": a.value, "elements": b.value, "last_timetag": t.value}
 
     def last(self, channel):
         buf = (ctypes.c_ubyte * 160)()

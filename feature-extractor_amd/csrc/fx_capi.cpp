@@ -837,4 +837,97 @@ int fx_osc_encode_addressed(const char* const* addresses, int n, const float* sm
     return n;
 }
 
+// ---- bundles (ref OSCFeatureAnalysisOutput.h:107 messages as the elements of OSC 1.0 bundles; fx_osc_words.h holds the layout) ----
+fx_status fx_osc_bundle_plan(int longest_message_bytes, int num_tracks, int max_datagram_bytes, int* tracks_per_bundle, int* num_bundles, int* stride)
+{
+    if (num_tracks < 1) return fx_fail(FX_ERR_INVALID_ARGUMENT, "a bundle plan for %d tracks", num_tracks);
+    if (max_datagram_bytes > 65507) return fx_fail(FX_ERR_INVALID_ARGUMENT, "max_datagram_bytes %d: a UDP datagram carries at most 65507 bytes", max_datagram_bytes);
+    const int K = fxk::osc_bundle_tracks(longest_message_bytes, num_tracks, max_datagram_bytes);
+    if (K < 1) return fx_fail(FX_ERR_INVALID_ARGUMENT, "max_datagram_bytes %d does not hold a bundle of one message of %d bytes (16 + 4 + the message)", max_datagram_bytes, longest_message_bytes);
+    if (tracks_per_bundle) *tracks_per_bundle = K;
+    if (num_bundles) *num_bundles = (num_tracks + K - 1) / K;
+    if (stride) *stride = 16 + K * (4 + longest_message_bytes);
+    return FX_OK;
+}
+
+unsigned long long fx_osc_timetag(double unix_seconds)
+{
+    const double ntp = unix_seconds + 2208988800.0;            // 1900-01-01 to 1970-01-01 in seconds
+    if (!(ntp >= 0.0) || ntp >= 4294967296.0) return FX_OSC_TIMETAG_IMMEDIATE;
+    const double whole = std::floor(ntp);
+    unsigned long long fraction = (unsigned long long) ((ntp - whole) * 4294967296.0);
+    if (fraction > 0xFFFFFFFFull) fraction = 0xFFFFFFFFull;
+    return ((unsigned long long) whole << 32) | fraction;
+}
+
+// The bundles of `p` (host pointers; C, latest and the address source filled in), one word at a time through osc_bundle_word: the host
+// twin of fx_osc_bundle_kernel.  Returns the number of bundles, or -1.
+static int encode_bundles(fxk::OscBundleParams& p, int longest, unsigned long long timetag, int max_datagram_bytes, int stride, int* lengths)
+{
+    int K = 0, bundles = 0, need = 0;
+    if (fx_osc_bundle_plan(longest, p.C, max_datagram_bytes, &K, &bundles, &need) != FX_OK) return -1;
+    if (stride < need || (stride & 3)) { (void) fx_fail(FX_ERR_INVALID_ARGUMENT, "stride %d: must be a multiple of 4 and hold the fullest bundle (%d bytes)", stride, need); return -1; }
+    p.K = K;
+    p.stride = stride;
+    p.timetag_hi = (unsigned) (timetag >> 32);
+    p.timetag_lo = (unsigned) timetag;
+    std::vector<int> off;
+    try { off.resize((size_t) K + 1); } catch (const std::bad_alloc&) { (void) fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed"); return -1; }
+    for (int b = 0; b < bundles; b++) {
+        const int count = p.C - b * K < K ? p.C - b * K : K;
+        off[0] = fxk::FX_OSC_BUNDLE_HEADER_WORDS;
+        for (int e = 0; e < count; e++) off[(size_t) e + 1] = off[(size_t) e] + 1 + fxk::osc_bundle_element_words(p, b * K + e);
+        unsigned char* slot = p.out + (size_t) b * (size_t) stride;
+        for (int w = 0; w < stride >> 2; w++) {
+            const unsigned v = fxk::osc_bundle_word(p, b, off.data(), count, w);
+            memcpy(slot + 4 * (size_t) w, &v, 4);
+        }
+        if (lengths) lengths[b] = 4 * off[(size_t) count];
+    }
+    return bundles;
+}
+
+int fx_osc_encode_bundles(const char* prefix, int first_channel, int n, const float* smoothed, unsigned long long timetag, int max_datagram_bytes,
+                          unsigned char* out, int stride, int* lengths)
+{
+    if (!prefix || !smoothed || !out || n < 0 || first_channel < 0) { (void) fx_fail(FX_ERR_INVALID_ARGUMENT, "null argument, a negative count or a negative channel number"); return -1; }
+    if (n == 0) return 0;
+    const int longest = first_channel > 0x7fffffff - n ? -1 : fx_osc_message_bytes(prefix, first_channel + n - 1);
+    if (longest < 0) { (void) fx_fail(FX_ERR_INVALID_ARGUMENT, "OSC prefix longer than %d bytes, or a channel number out of range", fxk::FX_OSC_PREFIX_MAX); return -1; }
+    fxk::OscBundleParams p = {};
+    p.latest = smoothed;
+    p.out = out;
+    p.C = n;
+    p.first_channel = first_channel;
+    p.prefix_len = (int) strlen(prefix);
+    memcpy(p.prefix, prefix, (size_t) p.prefix_len);
+    return encode_bundles(p, longest, timetag, max_datagram_bytes, stride, lengths);
+}
+
+int fx_osc_encode_bundles_addressed(const char* const* addresses, int n, const float* smoothed, unsigned long long timetag, int max_datagram_bytes,
+                                    unsigned char* out, int stride, int* lengths)
+{
+    if (n < 0 || (n > 0 && (!addresses || !smoothed || !out))) { (void) fx_fail(FX_ERR_INVALID_ARGUMENT, "null argument or a negative count"); return -1; }
+    if (n == 0) return 0;
+    // an address table's image as osc_table_word reads it: zero-padded rows and the lengths
+    std::vector<unsigned> rows;
+    std::vector<int> len;
+    try { rows.assign((size_t) n * fxk::FX_OSC_ROW_WORDS, 0u); len.resize((size_t) n); } catch (const std::bad_alloc&) { (void) fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed"); return -1; }
+    int longest = 0;
+    for (int c = 0; c < n; c++) {
+        int alen = 0;
+        if (const char* fault = fxk::osc_address_fault(addresses[c], &alen)) { (void) fx_fail(FX_ERR_INVALID_ARGUMENT, "track %d: the OSC address %s", c, fault); return -1; }
+        memcpy(rows.data() + (size_t) c * fxk::FX_OSC_ROW_WORDS, addresses[c], (size_t) alen);
+        len[(size_t) c] = alen;
+        if (fxk::osc_addressed_bytes(alen) > longest) longest = fxk::osc_addressed_bytes(alen);
+    }
+    fxk::OscBundleParams p = {};
+    p.latest = smoothed;
+    p.rows = rows.data();
+    p.len = len.data();
+    p.out = out;
+    p.C = n;
+    return encode_bundles(p, longest, timetag, max_datagram_bytes, stride, lengths);
+}
+
 } // extern "C"

@@ -1,6 +1,6 @@
 // fx_context.h -- the context behind the C ABI (include/fx.h), shared by the shim's host units (fx_capi.cpp, fx_plan.cpp, fx_stream.cpp,
 // fx_comm.cpp) and the units that attach through its hooks (fx_taps.hip, fx_interleave.hip, fx_events.hip, fx_tracks.hip,
-// fx_osc_table.hip).  Internal.
+// fx_osc_table.hip, fx_osc_bundle.hip).  Internal.
 #ifndef FX_CONTEXT_H
 #define FX_CONTEXT_H
 
@@ -60,7 +60,13 @@ struct fx_taps;
 struct fx_interleave;   // fx_interleave.hip
 struct fx_events;       // fx_events.hip
 struct fx_tracks;       // fx_tracks.hip
-struct fx_osc_table;    // fx_osc_table.hip
+// The OSC address table in force (fx_osc_table.hip makes and frees it; fx_osc_bundle.hip reads it): one device allocation, [C][128]
+// bytes of rows, then int len[C]; the messages' lengths on the host.
+struct fx_osc_table {
+    unsigned char*   d_table = nullptr;
+    std::vector<int> message_bytes;     // [C]
+    int              longest = 0;       // the smallest legal stride
+};
 // Where an analysis call reads its FIRST frame, as the kernels read it: `in` (device) holds rows of in_row_bytes per channel; hop_mode 1:
 // hops of N/2 samples, the window is [the channel's tail | hop 0 x gain]; 0: whole frames, frame 0 as given.  carry != null: the hop is
 // the first N/2 samples of [pending | block] (fx_blocks.hip.h, BlockStream), the pending row of the channel at carry + c * carry_row_bytes.

@@ -337,6 +337,9 @@ enum { FX_LAUNCH_FRAME = 1, FX_LAUNCH_FRAME_TAIL, FX_LAUNCH_HOP, FX_LAUNCH_HOP_P
 constexpr int FX_LAUNCH_ONSET_EVENTS = 11;
 // fx_get_osc_datagrams_addressed (fx_osc_table.hip): one launch of fx_osc_table_kernel; it starts a new record, as fx_get_osc_datagrams does.
 constexpr int FX_LAUNCH_OSC_TABLE = 12;
+// fx_get_osc_bundles / fx_get_osc_bundles_addressed (fx_osc_bundle.hip): one launch of fx_osc_bundle_kernel; it starts a new record too.
+// T = the tracks per bundle.
+constexpr int FX_LAUNCH_OSC_BUNDLE = 13;
 struct fx_launch_record {
     int kind;               // FX_LAUNCH_*
     int window, analysers;  // window size, analysers mask (bit 0 spectral, bit 1 harmonic)

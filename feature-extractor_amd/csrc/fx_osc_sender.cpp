@@ -4,7 +4,8 @@
 // The reference builds two OSCFeatureAnalysisOutput objects per track (AnalyserTrackController.h:22-23), each a 60 Hz juce::Timer whose
 // callback formats and sends ONE message (OSCFeatureAnalysisOutput.h:84-113,133).  At the channel counts this library analyses --
 // 8192 per GPU, 65 536 per node -- that shape is 131 072 timers and 7.9e6 system calls a second.  Here the messages of a tick arrive
-// already formatted ([count][stride] bytes: fx_get_osc_datagrams writes them on the GPU, fx_osc_encode_batch on the host), and a tick
+// already formatted ([count][stride] bytes: fx_get_osc_datagrams writes them on the GPU, fx_osc_encode_batch on the host; a "message"
+// may as well be an OSC bundle of many tracks' messages, fx_get_osc_bundles: nothing here assumes a size below 65 507 bytes), and a tick
 // hands them to the kernel in batches: `threads` sender threads, each owning a contiguous slice of the tracks and one connected UDP
 // socket per target, sendmmsg of up to 1024 messages per call -- or, with FX_OSC_SENDER_GSO, runs of equal-length messages as segmented
 // sends (UDP_SEGMENT: one trip through the stack per 64 datagrams; the datagrams on the wire are the same).
@@ -514,6 +515,9 @@ struct fx_osc_receiver {
     std::vector<std::thread> threads;
     std::atomic<bool> quit{false};
     std::atomic<long long> datagrams{0}, bytes{0}, malformed{0};
+    bool bundles = false;                              // FX_OSC_RECEIVER_BUNDLES
+    std::atomic<long long> bundles_seen{0}, elements{0};
+    std::atomic<unsigned long long> last_timetag{0};
     int port = 0;
     bool gro = false;                                  // UDP_GRO taken by the sockets (see receive())
     std::string prefix;
@@ -556,11 +560,42 @@ void take(fx_osc_receiver* r, const unsigned char* m, int len, long long* bad)
     }
 }
 
+inline unsigned be32(const unsigned char* p) { return (unsigned) p[0] << 24 | (unsigned) p[1] << 16 | (unsigned) p[2] << 8 | (unsigned) p[3]; }
+
+bool is_bundle(const unsigned char* m, int len) { return len >= 8 && memcmp(m, "#bundle", 8) == 0; }
+
+// FX_OSC_RECEIVER_BUNDLES: a datagram that starts with "#bundle\0" (OSC 1.0: the 64-bit time tag, then (int32 size, element) until the
+// end).  Checked whole before anything is taken -- every size a multiple of 4 that stays inside, at least one element, no element a
+// bundle, every element a twelve-float message -- so a bad bundle counts once and leaves nothing behind; then each element goes
+// through take().
+void take_bundle(fx_osc_receiver* r, const unsigned char* m, int len, long long* bad)
+{
+    int elements = 0;
+    bool ok = len >= 16 && (len & 3) == 0;
+    for (int at = 16; ok && at < len;) {
+        const unsigned size = be32(m + at);             // (len and at are multiples of 4: the four bytes are there)
+        int alen = 0;
+        ok = size <= (unsigned) (len - at - 4) && (size & 3u) == 0 && !is_bundle(m + at + 4, (int) size) && well_formed(m + at + 4, (int) size, &alen);
+        if (ok) { at += 4 + (int) size; elements++; }
+    }
+    if (!ok || elements == 0) { ++*bad; return; }
+    for (int at = 16; at < len;) {
+        const int size = (int) be32(m + at);
+        long long none = 0;
+        take(r, m + at + 4, size, &none);
+        at += 4 + size;
+    }
+    r->bundles_seen.fetch_add(1, std::memory_order_relaxed);
+    r->elements.fetch_add(elements, std::memory_order_relaxed);
+    r->last_timetag.store((unsigned long long) be32(m + 8) << 32 | be32(m + 12), std::memory_order_relaxed);
+}
+
 // With UDP_GRO on the socket a segmented send that never left the host (loopback) arrives as it was sent: one buffer of up to 64
 // datagrams and a control message with their length -- the receiver then costs one trip through the stack per 64 datagrams as well.
 void receive(fx_osc_receiver* r, int fd, bool gro)
 {
-    const int kBatch = gro ? 32 : 256, kRoom = gro ? 65536 : 256;
+    const bool big = gro || r->bundles;                // (a bundle is a datagram of up to 65 507 bytes)
+    const int kBatch = big ? 32 : 256, kRoom = big ? 65536 : 256;
     std::vector<unsigned char> room((size_t) kBatch * (size_t) kRoom);
     std::vector<mmsghdr> msgs((size_t) kBatch);
     std::vector<iovec> iov((size_t) kBatch);
@@ -587,7 +622,11 @@ void receive(fx_osc_receiver* r, int fd, bool gro)
             if (gro)
                 for (cmsghdr* cm = CMSG_FIRSTHDR(&msgs[(size_t) i].msg_hdr); cm; cm = CMSG_NXTHDR(&msgs[(size_t) i].msg_hdr, cm))
                     if (cm->cmsg_level == SOL_UDP && cm->cmsg_type == UDP_GRO) { int v = 0; memcpy(&v, CMSG_DATA(cm), sizeof v); if (v > 0) segment = v; }
-            for (int at = 0; at < len; at += segment) { take(r, m + at, len - at < segment ? len - at : segment, &bad); count++; }
+            for (int at = 0; at < len; at += segment) {
+                const int n = len - at < segment ? len - at : segment;
+                if (r->bundles && is_bundle(m + at, n)) take_bundle(r, m + at, n, &bad); else take(r, m + at, n, &bad);
+                count++;
+            }
             if (len == 0) { bad++; count++; }
         }
         r->datagrams += count; r->bytes += b; r->malformed += bad;
@@ -610,6 +649,7 @@ fx_status fx_osc_receiver_create(fx_osc_receiver** out, const char* bind_address
     if (!r) return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
     r->prefix = prefix ? prefix : "";
     r->keep = keep_channels;
+    r->bundles = (flags & FX_OSC_RECEIVER_BUNDLES) != 0;
     if (keep_channels > 0) {
         r->last.assign((size_t) keep_channels * fx_osc_receiver::kSlot, 0);
         r->busy.reset(new std::atomic_flag[(size_t) keep_channels]);
@@ -661,6 +701,15 @@ fx_status fx_osc_receiver_get_stats(fx_osc_receiver* r, long long* datagrams, lo
     if (datagrams) *datagrams = r->datagrams.load();
     if (bytes) *bytes = r->bytes.load();
     if (malformed) *malformed = r->malformed.load();
+    return FX_OK;
+}
+
+fx_status fx_osc_receiver_get_bundle_stats(fx_osc_receiver* r, long long* bundles, long long* elements, unsigned long long* last_timetag)
+{
+    if (!r) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null receiver");
+    if (bundles) *bundles = r->bundles_seen.load();
+    if (elements) *elements = r->elements.load();
+    if (last_timetag) *last_timetag = r->last_timetag.load();
     return FX_OK;
 }
 

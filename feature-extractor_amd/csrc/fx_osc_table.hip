@@ -54,13 +54,6 @@ static hipError_t launch_osc_table_kernel(const OscTableParams& p, hipStream_t s
 
 } // namespace fxk
 
-// The table in force: one device allocation, [C][128] bytes of rows, then int len[C]; the messages' lengths on the host.
-struct fx_osc_table {
-    unsigned char*   d_table = nullptr;
-    std::vector<int> message_bytes;     // [C]
-    int              longest = 0;       // the smallest legal stride
-};
-
 namespace {
 
 void osc_table_release(fx_context* c)

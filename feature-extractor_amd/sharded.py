@@ -140,9 +140,14 @@ class OscSink:
     Scale-shaped since round 6: the messages of a tick are formed in ONE call (fx_osc_encode_batch on the host, or handed over
     ready-made by BatchAnalyser.osc_datagrams, which writes them on the GPU) and go to the kernel in sendmmsg batches from the
     library's sender threads (fx_osc_sender, csrc/fx_osc_sender.cpp), which also run the timer: no Python in a tick.
-    `encode` (the per-message encoder of earlier rounds) is accepted and ignored."""
+    `encode` (the per-message encoder of earlier rounds) is accepted and ignored.
 
-    def __init__(self, encode=None, target="127.0.0.1:9000", secondary=None, bundle_prefix="/Audio/A", rate_hz=60.0, first_channel=0, threads=1, gso=False):
+    bundle_bytes > 0: update() publishes OSC 1.0 bundles of at most that many bytes, many tracks' messages per datagram, stamped
+    "immediately" (fx_osc_encode_bundles; BatchAnalyser.osc_bundles makes the same on the GPU for update_datagrams).  0: one message per
+    datagram, as the reference sends them."""
+
+    def __init__(self, encode=None, target="127.0.0.1:9000", secondary=None, bundle_prefix="/Audio/A", rate_hz=60.0, first_channel=0, threads=1, gso=False,
+                 bundle_bytes=0):
         from . import capi
         self._capi = capi
         self.targets = [parse_osc_target(target)] + ([parse_osc_target(secondary)] if secondary else [])
@@ -150,15 +155,20 @@ class OscSink:
         self.first_channel = first_channel
         self.rate_hz = rate_hz
         self.sender = capi.OscSender(target, secondary, threads=threads, gso=gso)
+        self.bundle_bytes = int(bundle_bytes)
         self._have = False
 
     def update(self, smoothed):
         """Publish the newest AudioFeatures::getValue vectors [C][12] (what the timer will sample)."""
-        d, n = self._capi.osc_encode_batch(self.prefix, self.first_channel, np.asarray(smoothed, np.float32).reshape(-1, 12))
+        v = np.asarray(smoothed, np.float32).reshape(-1, 12)
+        if self.bundle_bytes > 0:
+            d, n = self._capi.osc_encode_bundles(self.prefix, self.first_channel, v, max_datagram_bytes=self.bundle_bytes)
+        else:
+            d, n = self._capi.osc_encode_batch(self.prefix, self.first_channel, v)
         self.update_datagrams(d, n)
 
     def update_datagrams(self, datagrams, lengths):
-        """Publish messages that are already formed ([C][stride] bytes + lengths: BatchAnalyser.osc_datagrams)."""
+        """Publish messages that are already formed ([C][stride] bytes + lengths: BatchAnalyser.osc_datagrams or .osc_bundles)."""
         self.sender.update(datagrams, lengths)
         self._have = True
 

@@ -572,6 +572,49 @@ fx_status fx_get_osc_datagrams_addressed(fx_context* ctx, unsigned char* out, in
  * slot order (ref OSCFeatureAnalysisOutput.h:107).  Returns n, or -1 on a bad argument (fx_last_error names a bad address's track). */
 int fx_osc_encode_addressed(const char* const* addresses, int n, const float* smoothed12, unsigned char* out, int stride, int* lengths);
 
+/* ---- bundles: many tracks' messages per datagram ----
+ * One message per track per tick (OSCFeatureAnalysisOutput.h:107) is one datagram, one trip through the network stack and one receiver
+ * wake-up per track; OSC 1.0 has the #bundle for that.  A bundle datagram here is "#bundle\0" (8 bytes), a 64-bit big-endian NTP time
+ * tag, then per element a big-endian int32 size and that many bytes (OSC 1.0, "OSC Bundles"); every element is byte for byte the message
+ * fx_osc_encode makes for its track (OSCFeatureAnalysisOutput.h:107).  Bundle b of a call holds tracks [b * K, min(n, (b + 1) * K)) in
+ * ascending order, K the same for every bundle of the call (so which tracks share a datagram depends on K alone and the sender's
+ * per-datagram routes keep their meaning); the last bundle may be short; bundles are never nested.  Opt-in: the entries above keep their
+ * bytes and their launches. */
+#define FX_OSC_BUNDLE_MAX_ELEMENTS 1024
+#define FX_OSC_TIMETAG_IMMEDIATE 1ull   /* OSC 1.0: "immediately" */
+/* The layout of a call's bundles (host arithmetic): K = min(num_tracks, FX_OSC_BUNDLE_MAX_ELEMENTS, (max_datagram_bytes - 16) /
+ * (4 + longest_message_bytes)) tracks per bundle (OSCFeatureAnalysisOutput.h:107 messages as the elements of an OSC 1.0 bundle),
+ * num_bundles = ceil(num_tracks / K), stride = 16 + K * (4 + longest) bytes per output slot.  longest_message_bytes: from
+ * fx_osc_message_bytes(prefix, first + n - 1) or fx_osc_address_stride (a multiple of 4, 68 .. 192).  FX_ERR_INVALID_ARGUMENT when K would
+ * be 0, max_datagram_bytes > 65507 or num_tracks < 1.  Any output pointer may be NULL. */
+fx_status fx_osc_bundle_plan(int longest_message_bytes, int num_tracks, int max_datagram_bytes, int* tracks_per_bundle, int* num_bundles, int* stride);
+/* The OSC 1.0 bundle time tag of a Unix time: NTP seconds since 1900 in the high word, the fraction of a second in the low word
+ * (what marks the OSCFeatureAnalysisOutput.h:107 messages of many tracks as one analysis instant). */
+unsigned long long fx_osc_timetag(double unix_seconds);
+/* fx_osc_encode_batch as bundles, on the host: tracks "<prefix><first_channel + c>" with smoothed12 [n][12] (OSCFeatureAnalysisOutput.h:107
+ * messages in OSC 1.0 bundles, laid out by fx_osc_bundle_plan for the longest of these messages); bundle b at out + b * stride,
+ * lengths[b] (may be NULL) its bytes, the rest of each slot zeros.  stride: a multiple of 4, >= the plan's.  Returns the number of
+ * bundles, or -1 on a bad argument. */
+int fx_osc_encode_bundles(const char* prefix, int first_channel, int n, const float* smoothed12, unsigned long long timetag,
+                          int max_datagram_bytes, unsigned char* out, int stride, int* lengths);
+/* fx_osc_encode_addressed as bundles (OSCFeatureAnalysisOutput.h:107 messages with the tracks' own addresses in OSC 1.0 bundles); the
+ * plan is made for the longest message of `addresses`. */
+int fx_osc_encode_bundles_addressed(const char* const* addresses, int n, const float* smoothed12, unsigned long long timetag,
+                                    int max_datagram_bytes, unsigned char* out, int stride, int* lengths);
+/* The same bundles for every channel of the context, formed ON THE DEVICE from `latest` in one launch (OSCFeatureAnalysisOutput.h:107
+ * messages, OSC 1.0 bundle layout), ordered after the analysis calls made so far.  out: [num_bundles][stride] bytes as
+ * fx_osc_bundle_plan(fx_osc_message_bytes(prefix, first_channel + num_channels - 1), num_channels, max_datagram_bytes) lays them out;
+ * stride: a multiple of 4, >= the plan's; not one byte past num_bundles * stride is written.  FX_MEM_HOST returns when the bytes are
+ * there; FX_MEM_DEVICE needs a 4-byte-aligned buffer and is asynchronous on the context's stream.  lengths: host array [num_bundles] or
+ * NULL.  Nothing is kept between calls: timetag, max_datagram_bytes and the prefix may change from call to call at no cost.  Bad
+ * arguments are refused before any device use. */
+fx_status fx_get_osc_bundles(fx_context* ctx, const char* prefix, int first_channel, unsigned long long timetag, int max_datagram_bytes,
+                             unsigned char* out, int stride, int* lengths, int mem_kind);
+/* fx_get_osc_bundles with the addresses of fx_set_osc_addresses (OSCFeatureAnalysisOutput.h:107 bundleAddress per track, OSC 1.0
+ * bundle layout): the plan is made for fx_osc_address_stride.  FX_ERR_INVALID_ARGUMENT without a table. */
+fx_status fx_get_osc_bundles_addressed(fx_context* ctx, unsigned long long timetag, int max_datagram_bytes, unsigned char* out, int stride,
+                                       int* lengths, int mem_kind);
+
 /* The sender: one UDP socket per target and thread, sendmmsg in chunks, `threads` sender threads each owning a slice of the tracks,
  * a 60 Hz timer (OSCFeatureAnalysisOutput::startTimerHz (60), :133) and a primary plus an optional secondary target
  * (AnalyserTrackController.h:22-23); targets are "ip[:port]", port 9000 by default, parsed as connectToAddress does (:115-123).
@@ -581,7 +624,9 @@ typedef struct fx_osc_sender fx_osc_sender;
                                   kernel supports it; the datagrams on the wire are the same */
 fx_status fx_osc_sender_create(fx_osc_sender** out, const char* primary, const char* secondary /* or NULL */, int threads, unsigned flags);
 fx_status fx_osc_sender_destroy(fx_osc_sender* s);
-/* Publish the datagrams the next ticks send: `count` messages, message i at datagrams + i * stride, lengths[i] bytes.  Copied. */
+/* Publish the datagrams the next ticks send: `count` messages, message i at datagrams + i * stride, lengths[i] bytes.  Copied.
+ * A "message" is whatever one datagram carries, up to 65507 bytes: a bundle of fx_get_osc_bundles is published as it is, count =
+ * num_bundles. */
 fx_status fx_osc_sender_update(fx_osc_sender* s, const unsigned char* datagrams, int stride, const int* lengths, int count);
 /* One tick, now, on the caller's thread + the sender's threads: every published message to every target; *sent (may be NULL) =
  * datagrams the kernel accepted. */
@@ -605,7 +650,7 @@ fx_status fx_osc_sender_get_stats(fx_osc_sender* s, fx_osc_sender_stats* out);
  * sender thread keeps one connected socket per target it serves and orders its slice's messages by target HERE, not per tick; per
  * target the messages keep ascending track order.  While routes are set, a publication (fx_osc_sender_update) of another count is
  * FX_ERR_INVALID_ARGUMENT, and so are routes of another count than what is published.  Bad indices or unparsable targets change
- * nothing.  Safe while the timer runs. */
+ * nothing.  Safe while the timer runs.  Where bundles are published the routes are per bundle: bundle b holds tracks [b * K, (b + 1) * K). */
 #define FX_OSC_SENDER_MAX_TARGETS 64
 fx_status fx_osc_sender_set_routes(fx_osc_sender* s, const char* const* targets, int num_targets, const int* primary,
                                    const int* secondary /* or NULL */, int count);
@@ -616,11 +661,18 @@ fx_status fx_osc_sender_set_routes(fx_osc_sender* s, const char* const* targets,
 typedef struct fx_osc_receiver fx_osc_receiver;
 #define FX_OSC_RECEIVER_NO_GRO 1u   /* do not ask for UDP_GRO: every datagram makes its own way through the receiving stack, as it would from a
                                        remote sender (with it, a segmented send over loopback arrives whole and is split in user space) */
+#define FX_OSC_RECEIVER_BUNDLES 2u  /* 65 536 bytes of room per datagram, and a datagram that starts with "#bundle\0" is parsed (OSC 1.0 bundle
+                                       layout): each element is taken as a message of its own (OSCFeatureAnalysisOutput.h:107), so that
+                                       fx_osc_receiver_last keeps working.  A bundle counts once as malformed when a size is no multiple of 4
+                                       or runs past the end, when it is nested or empty, or when an element is no twelve-float message. */
 fx_status fx_osc_receiver_create(fx_osc_receiver** out, const char* bind_address, int threads, const char* prefix, int keep_channels, unsigned flags);
 fx_status fx_osc_receiver_destroy(fx_osc_receiver* r);
 int fx_osc_receiver_port(fx_osc_receiver* r);
 /* datagrams and bytes received so far, and those that were not an OSC message of twelve floats; any pointer may be NULL */
 fx_status fx_osc_receiver_get_stats(fx_osc_receiver* r, long long* datagrams, long long* bytes, long long* malformed);
+/* FX_OSC_RECEIVER_BUNDLES: well-formed bundles (OSC 1.0) received so far, the messages (OSCFeatureAnalysisOutput.h:107) they held and
+ * the time tag of the newest one; any pointer may be NULL.  All 0 without the flag. */
+fx_status fx_osc_receiver_get_bundle_stats(fx_osc_receiver* r, long long* bundles, long long* elements, unsigned long long* last_timetag);
 /* newest message kept for `channel`: copied to out (cap bytes), its length to *len (0 = none seen yet) */
 fx_status fx_osc_receiver_last(fx_osc_receiver* r, int channel, unsigned char* out, int cap, int* len);
 

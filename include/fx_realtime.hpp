@@ -581,6 +581,13 @@ private:
 #include <mutex>
 #include <thread>
 
+// The device bundle calls live in a library unit of their own (csrc/fx_osc_bundle.hip).  Weak here: OSCBatchSender::updateFromContext
+// refers to them, and a host built from the library's host units alone (tests/cpp) still links; there the addresses are null.
+extern "C" {
+fx_status fx_get_osc_bundles (fx_context*, const char*, int, unsigned long long, int, unsigned char*, int, int*, int) __attribute__ ((weak));
+fx_status fx_get_osc_bundles_addressed (fx_context*, unsigned long long, int, unsigned char*, int, int*, int) __attribute__ ((weak));
+}
+
 namespace fx
 {
 // OSCFeatureAnalysisOutput, ref Source/OSCFeatureAnalysisOutput.h:23-145: a 60 Hz timer that reads the track's AudioFeatures::getValue of
@@ -686,6 +693,14 @@ public:
     {
         const int stride = fx_osc_message_bytes (prefix.c_str(), firstChannel + (count > 0 ? count - 1 : 0));
         if (stride < 0) throw Error (FX_ERR_INVALID_ARGUMENT, "OSC prefix too long or a negative channel number");
+        if (bundleBytes > 0 && count > 0)
+        {
+            const int bundles = planBundles (stride, count);
+            if (fx_osc_encode_bundles (prefix.c_str(), firstChannel, count, smoothed12, stamp(), bundleBytes, scratch.data(), bundleStride, lengths.data()) != bundles)
+                throw Error (FX_ERR_INVALID_ARGUMENT, fx_last_error());
+            updateDatagrams (scratch.data(), bundleStride, lengths.data(), bundles);
+            return;
+        }
         scratch.resize ((std::size_t) count * (std::size_t) stride);
         lengths.resize ((std::size_t) count);
         if (fx_osc_encode_batch (prefix.c_str(), firstChannel, count, smoothed12, scratch.data(), stride, lengths.data()) != count)
@@ -714,11 +729,33 @@ public:
         check (fx_osc_sender_set_routes (sender, list.empty() ? nullptr : list.data(), (int) list.size(), primary.data(),
                                          secondary.empty() ? nullptr : secondary.data(), (int) primary.size()));
     }
+    // Bundling (OSC 1.0 #bundle): updateFeatures and updateFromContext publish bundles of at most maxDatagramBytes, about 17 tracks'
+    // messages per datagram at 1472, instead of one message per datagram; stampWithNow: the time tag is the time of the publication,
+    // else "immediately".  0 = off, the default: the reference's wire format.  Switch it on where the receiver takes bundles (Max,
+    // SuperCollider, TouchDesigner, liblo, juce::OSCReceiver all do); routes (setRoutes) are then per bundle.
+    void setBundling (int maxDatagramBytes, bool stampWithNow)
+    {
+        if (maxDatagramBytes < 0 || maxDatagramBytes > 65507) throw Error (FX_ERR_INVALID_ARGUMENT, "bundles of 0 (off) .. 65507 bytes");
+        bundleBytes = maxDatagramBytes;
+        bundleStamp = stampWithNow;
+    }
     // publish the context's latest vectors, formed on the device (the copy to the host is the datagrams): with the addresses of
     // setBundleAddresses where a table is set, else "<prefix><firstChannel + i>"
     void updateFromContext (fx_context* ctx, int numChannels, const std::string& prefix, int firstChannel)
     {
         const int tableStride = addressStride != nullptr ? addressStride (ctx) : -1;
+        if (bundleBytes > 0 && numChannels > 0)
+        {
+            // (weak references, declared above: a host linked without the library's bundle unit gets an Error, not a link failure)
+            if (&fx_get_osc_bundles == nullptr || &fx_get_osc_bundles_addressed == nullptr) throw Error (FX_ERR_UNSUPPORTED, "this library has no fx_get_osc_bundles");
+            const int longest = tableStride >= 0 ? tableStride : fx_osc_message_bytes (prefix.c_str(), firstChannel + numChannels - 1);
+            if (longest < 0) throw Error (FX_ERR_INVALID_ARGUMENT, "OSC prefix too long or a negative channel number");
+            const int bundles = planBundles (longest, numChannels);
+            if (tableStride >= 0) check (fx_get_osc_bundles_addressed (ctx, stamp(), bundleBytes, scratch.data(), bundleStride, lengths.data(), FX_MEM_HOST));
+            else check (fx_get_osc_bundles (ctx, prefix.c_str(), firstChannel, stamp(), bundleBytes, scratch.data(), bundleStride, lengths.data(), FX_MEM_HOST));
+            updateDatagrams (scratch.data(), bundleStride, lengths.data(), bundles);
+            return;
+        }
         if (tableStride >= 0)
         {
             scratch.resize ((std::size_t) numChannels * (std::size_t) tableStride);
@@ -741,9 +778,26 @@ public:
     fx_osc_sender* handle() { return sender; }
 
 private:
+    // sizes scratch and lengths for the bundles of `count` tracks whose longest message is `longest` bytes; returns their number
+    int planBundles (int longest, int count)
+    {
+        int perBundle = 0, bundles = 0;
+        check (fx_osc_bundle_plan (longest, count, bundleBytes, &perBundle, &bundles, &bundleStride));
+        scratch.resize ((std::size_t) bundles * (std::size_t) bundleStride);
+        lengths.resize ((std::size_t) bundles);
+        return bundles;
+    }
+    unsigned long long stamp() const
+    {
+        if (! bundleStamp) return FX_OSC_TIMETAG_IMMEDIATE;
+        return fx_osc_timetag (std::chrono::duration<double> (std::chrono::system_clock::now().time_since_epoch()).count());
+    }
+
     fx_osc_sender* sender = nullptr;
     std::vector<unsigned char> scratch;
     std::vector<int> lengths;
+    int bundleBytes = 0, bundleStride = 0;
+    bool bundleStamp = false;
     int (*addressStride) (fx_context*) = nullptr;
     fx_status (*addressedDatagrams) (fx_context*, unsigned char*, int, int*, int) = nullptr;
 };
