@@ -12,7 +12,7 @@
 //   real image   : sample  n at n + 4 * (n >> 4)         (16 B of padding per 16 floats, keeps
 //                                                          16-byte alignment of 4-sample groups)
 // ---------------------------------------------------------------------------------------------
-__host__ __device__ constexpr int cpad(int p) { return p + (p >> 4); }
+#include "fx_lane_exchange.h"      // cpad, item_off; LaneExchange<N>: the second exchange of the 1024-point transform as lane swaps
 
 template <int N> struct Geo {
     static constexpr int M      = N / 2;            // numMagnitudes (ref SpectralCharacteristics.h:104)
@@ -265,9 +265,23 @@ template <int N> struct CompactTw {
 };
 static_assert(CompactTw<4096>::ENTRIES == 3072 && CompactTw<4096>::OFF_S == 240 && CompactTw<4096>::q1_pos(1) == 528 && CompactTw<4096>::q1_pos(1022) == 511, "compact twiddle image");
 
-// offset of element i of an item inside the padded complex image, relative to cpad(base):
-// cpad(base + L0*i) - cpad(base) is a compile-time constant because base = blk*(R*L0) + k, k < L0
-__host__ __device__ constexpr int item_off(int L0, int i) { return L0 * i + (L0 >= 16 ? (L0 / 16) * i : ((L0 * i) >> 4)); }
+// Which transforms of the 1024-point kernels take the in-register second exchange (LaneExchange<N>, second_exchange_regs), by what
+// the transform feeds.  Costing builds (tools/build_variants.py ... name=-DFX_EXP_LDS_EXCHANGE=<mask>) keep the kinds of the mask
+// on the LDS exchange, so that each kind can be measured on its own: 1 forward-to-power, 2 spectral, 4 raw spectrum, 8 inverse
+// (LazyLag); 15 is the kernel without lane swaps.  The value is read as a constant expression, not by the preprocessor: spelled
+// out, the macro's name is what stands here when nothing defines it, and that selects the shipped default.
+enum { XK_POWER = 1, XK_SPECTRAL = 2, XK_RAW = 4, XK_INVERSE = 8 };
+#define FX_XK_TEXT_(x) #x
+#define FX_XK_TEXT(x) FX_XK_TEXT_(x)
+constexpr unsigned lds_exchange_kinds(const char* text, unsigned shipped)
+{
+    if (text[0] < '0' || text[0] > '9') return shipped;
+    unsigned v = 0;
+    for (; *text >= '0' && *text <= '9'; text++) v = 10 * v + (unsigned) (*text - '0');
+    return v;
+}
+constexpr unsigned LDS_EXCHANGE_KINDS = lds_exchange_kinds(FX_XK_TEXT(FX_EXP_LDS_EXCHANGE), 0u);
+static_assert(LDS_EXCHANGE_KINDS <= 15u, "FX_EXP_LDS_EXCHANGE: a mask of the four transform kinds");
 
 // The first exchange of a REAL-input transform need not carry the whole item.  A 16-element first-pass item is a 16-point
 // transform of real data: e[3], e[7], e[11], e[15] are formed as the bitwise conjugates of e[13], e[9], e[5], e[1] (first_pass_item),
@@ -491,12 +505,58 @@ __device__ __forceinline__ void item16_stages_r(f2 (&e)[16], const f2 (&w)[15])
                         twmul<INV>(e[jin + 4], w[3 + 3 * jin]), twmul<INV>(e[jin + 8], w[4 + 3 * jin]), twmul<INV>(e[jin + 12], w[5 + 3 * jin]));
 }
 
+// The second pass of the un-split 1024-point transform (one 16-element item per lane, behind the RealExchange) with the item left in
+// registers: the arithmetic of fft_pass, no store-back.  The wave's buffer is free on return.
+template <int N, bool INV>
+__device__ __forceinline__ void fft_second_pass_regs(const f2* cbuf, const f2* tw, int lane, f2 (&e)[16])
+{
+    typedef Plan<N> PL;
+    static_assert(LaneExchange<N>::AVAILABLE && RealExchange<N>::USE && PL::R1 == 16 && PL::L1 == 16 && N / 16 == 64, "one second-pass item per lane");
+    const int k = lane % 16;
+    const int slot = (int) ((RealExchange<N>::SLOT_OF >> (4 * k)) & 15ull);
+    const unsigned flip = ((RealExchange<N>::TWIN >> k) & 1u) << 31;
+    const f2* src = cbuf + RealExchange<N>::row((lane / 16) * 16) + slot;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const f2 v = src[i * RealExchange<N>::SLOTS];
+        e[i] = f2{v.x, __uint_as_float(__float_as_uint(v.y) ^ flip)};
+    }
+    wave_fence();                 // the wave has read the first exchange's image; the buffer may be rewritten
+    item16_stages<PL::L1, INV>(e, tw + PL::OFF1 + k);
+}
+
+// The second exchange in registers (LaneExchange<N>): in place on the lane's second-pass item; afterwards
+// e[LaneExchange<N>::register_of(g, ip)] is operand ip of last-pass butterfly lane + 64*g.  32 swaps, pure moves.  (The builtins,
+// not inline assembly: the compiler then places the two wait states a swap needs behind a VALU write of its operands.)
+template <bool HALVES> __device__ __forceinline__ void lane_swap(f2& a, f2& b)
+{
+    const auto x = HALVES ? __builtin_amdgcn_permlane32_swap(__float_as_uint(a.x), __float_as_uint(b.x), false, false)
+                          : __builtin_amdgcn_permlane16_swap(__float_as_uint(a.x), __float_as_uint(b.x), false, false);
+    const auto y = HALVES ? __builtin_amdgcn_permlane32_swap(__float_as_uint(a.y), __float_as_uint(b.y), false, false)
+                          : __builtin_amdgcn_permlane16_swap(__float_as_uint(a.y), __float_as_uint(b.y), false, false);
+    a = f2{__uint_as_float(x[0]), __uint_as_float(y[0])};
+    b = f2{__uint_as_float(x[1]), __uint_as_float(y[1])};
+}
+template <int N> __device__ __forceinline__ void second_exchange_regs(f2 (&e)[16])
+{
+    typedef LaneExchange<N> LX;
+#pragma unroll
+    for (int j = 0; j < LX::SWAPS; j++) lane_swap<true>(e[LX::swap(0, j).first], e[LX::swap(0, j).second]);
+#pragma unroll
+    for (int j = 0; j < LX::SWAPS; j++) lane_swap<false>(e[LX::swap(1, j).first], e[LX::swap(1, j).second]);
+}
+
 // What the last pass leaves in the wave's LDS buffer.
 enum { OUT_RE_LOW = 1,        // float re[M] (plain layout): all the harmonic analyser reads (ref HarmonicCharacteristics.h:63)
        OUT_RE_LOW_MAXABS = 2, // the same + max(|re|,|im|) over bins [0, M/2) returned per lane (ref SpectralCharacteristics.h:153)
        OUT_POWER = 3,         // re*re of all N bins (ref PitchAnalyser.h:97-103) as the NEXT transform's first-pass inputs: in registers
                               // (regs_out, one lane permutation) when a lane owns one first-pass item, else in the real image (rpad layout)
        OUT_LAG = 4 };         // v[s] = (re_s/N)^2 * s of the lane's own samples s = lane + 64*m in registers (regs_out[m]); returns v[N], from imag[0], in lane 0: ref :119-123
+
+template <int N, bool INV, int OUT> constexpr bool lane_exchange_used()
+{
+    return LaneExchange<N>::AVAILABLE && !(LDS_EXCHANGE_KINDS & (INV || OUT == OUT_LAG ? XK_INVERSE : OUT == OUT_POWER ? XK_POWER : OUT == OUT_RE_LOW_MAXABS ? XK_SPECTRAL : XK_RAW));
+}
 
 // The two stages of a LAST-pass 16-element item: the second stage forms only what the consumer of the spectrum reads
 // (bfly4_re; OUT as in fft_from_regs; `first_item`: the item whose element 0 is bin 0).  w(i): the item's 15 twiddles.
@@ -630,6 +690,22 @@ __device__ __forceinline__ float fft_last_pass_fused(f2* cbuf, const f2* tw, int
     return fft_last_pass_consume<N, INV, OUT>(e, cbuf, tw, lane, scale, regs_out);
 }
 
+// Second and last pass of the 1024-point transform with the exchange between them done by lane swaps: no complex image at all.
+template <int N, bool INV, int OUT>
+__device__ __forceinline__ float fft_last_passes_lanes(f2* cbuf, const f2* tw, int lane, float scale, float* regs_out)
+{
+    typedef LaneExchange<N> LX;
+    f2 s[16];
+    fft_second_pass_regs<N, INV>(cbuf, tw, lane, s);
+    second_exchange_regs<N>(s);
+    f2 e[4][4];
+#pragma unroll
+    for (int g = 0; g < 4; g++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) e[g][i] = s[LX::register_of(g, i)];
+    return fft_last_pass_consume<N, INV, OUT>(e, cbuf, tw, lane, scale, regs_out);
+}
+
 // What the consumer keeps of a finished 16-element last-pass item (item k: element i is bin k + (N/16)*i).
 template <int N, int OUT>
 __device__ __forceinline__ void last_item_reduce(const f2 (&e)[16], int k, float scale, float (&res)[16], float& aux)
@@ -665,17 +741,27 @@ template <int N> struct LazyLag {
     __device__ __forceinline__ void load(const float (&xin)[Geo<N>::P], f2* cbuf, const f2* tw, const float (&ftw)[18], int lane_, float scale_)
     {
         fft_first_pass<N, true>(xin, cbuf, ftw, lane_);
-        fft_pass<N, PL::R1, PL::L1, PL::OFF1, true, RealExchange<N>::USE>(cbuf, tw, lane_);
         lane = lane_;
         scale = scale_;
         t1 = tw + PL::OFF2 + lane;
+        if constexpr (lane_exchange_used<N, true, OUT_LAG>()) {
+            f2 s[16];
+            fft_second_pass_regs<N, true>(cbuf, tw, lane, s);
+            second_exchange_regs<N>(s);
 #pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const f2* img = cbuf + cpad(lane + 64 * g);
+            for (int g = 0; g < 4; g++)
 #pragma unroll
-            for (int i = 0; i < 4; i++) e[g][i] = img[item_off(L0, i)];
+                for (int i = 0; i < 4; i++) e[g][i] = s[LaneExchange<N>::register_of(g, i)];
+        } else {
+            fft_pass<N, PL::R1, PL::L1, PL::OFF1, true, RealExchange<N>::USE>(cbuf, tw, lane_);
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const f2* img = cbuf + cpad(lane + 64 * g);
+#pragma unroll
+                for (int i = 0; i < 4; i++) e[g][i] = img[item_off(L0, i)];
+            }
+            wave_fence();                 // the wave has read the whole complex image; the buffer may be rewritten
         }
-        wave_fence();                 // the wave has read the whole complex image; the buffer may be rewritten
     }
     __device__ __forceinline__ float head(int g) const          // g: compile-time after unrolling
     {
@@ -855,7 +941,11 @@ __device__ __forceinline__ float fft_from_regs(const float (&xin)[Geo<N>::P], f2
         return fft_split<N, INV, OUT, CTW>(xin, cbuf, tw, ftw, lane, scale, regs_out, twr, tg);
     } else {
         fft_first_pass<N, INV>(xin, cbuf, ftw, lane);
-        fft_pass<N, PL::R1, PL::L1, PL::OFF1, INV, RealExchange<N>::USE>(cbuf, tw, lane);
-        return fft_last_pass_fused<N, INV, OUT>(cbuf, tw, lane, scale, regs_out);
+        if constexpr (lane_exchange_used<N, INV, OUT>()) {
+            return fft_last_passes_lanes<N, INV, OUT>(cbuf, tw, lane, scale, regs_out);
+        } else {
+            fft_pass<N, PL::R1, PL::L1, PL::OFF1, INV, RealExchange<N>::USE>(cbuf, tw, lane);
+            return fft_last_pass_fused<N, INV, OUT>(cbuf, tw, lane, scale, regs_out);
+        }
     }
 }
