@@ -28,7 +28,7 @@ UNITS = [("fx_kernels.hip", "fx_kernels_small.o", ["-DFX_PART=1", "-mllvm", "-am
          ("fx_tracks.hip", "fx_tracks.o", []),
          ("fx_osc_table.hip", "fx_osc_table.o", []),
          ("fx_osc_bundle.hip", "fx_osc_bundle.o", [])] + [(s, s.replace(".cpp", ".o"), []) for s in HOST_SOURCES]
-HEADERS = ["fx_kernels.h", "fx_context.h", "fx_plan.h", "fx_osc_words.h", "fx_wave.hip.h", "fx_lane_exchange.h", "fx_fft.hip.h", "fx_blocks.hip.h", "fx_frame_kernel.hip.h", "fx_pair_kernel.hip.h", "fx_tail_kernels.hip.h", "fx_hop_kernel.hip.h",
+HEADERS = ["fx_kernels.h", "fx_context.h", "fx_plan.h", "fx_osc_words.h", "fx_wave.hip.h", "fx_lane_exchange.h", "fx_lane_consts.hip.h", "fx_fft.hip.h", "fx_blocks.hip.h", "fx_frame_kernel.hip.h", "fx_pair_kernel.hip.h", "fx_tail_kernels.hip.h", "fx_hop_kernel.hip.h",
            os.path.join("..", "..", "include", "fx.h")]
 
 # -ffp-contract=off : the reference FFT never fuses a*b+c; spectra must be bit-identical.

@@ -4,7 +4,8 @@
 
 // (The un-split transforms (N <= 1024) let the compiler hoist their few lane-derived addresses out of the frame loop: +1 %, 126
 // VGPRs.  Everywhere else lane-derived values are re-materialised per frame -- opaque(): hoisting them all spills 85 registers at
-// 1024 points.)
+// 1024 points -- except the ones the 1024-point batch kernel keeps in its per-wavefront record, LaneConsts (fx_lane_consts.hip.h): the
+// transform helpers below take the record as `lc` and read an address, a mask or an index from it where the kernel has one.)
 
 // ---------------------------------------------------------------------------------------------
 // LDS images
@@ -366,7 +367,7 @@ __device__ __forceinline__ void fft_pass(f2* cbuf, const f2* tw, int lane)
 }
 
 // base-4 digit reversal of the low 2*DIGITS bits
-template <int DIGITS> __device__ __forceinline__ int rev4(int x)
+template <int DIGITS> __host__ __device__ __forceinline__ constexpr int rev4(int x)
 {
     unsigned r = __builtin_bitreverse32((unsigned) x) >> (32 - 2 * DIGITS);
     r = ((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u);
@@ -402,6 +403,8 @@ template <int N> __host__ __device__ constexpr int first_pass_rstep(int j)
 }
 static_assert(Geo<256>::ITEMS_A % Geo<256>::RQ == 0 && Geo<512>::ITEMS_A % Geo<512>::RQ == 0 && Geo<1024>::ITEMS_A % Geo<1024>::RQ == 0
               && Geo<2048>::ITEMS_A % Geo<2048>::RQ == 0 && Geo<4096>::ITEMS_A % Geo<4096>::RQ == 0, "the real image splits only at multiples of RQ");
+
+#include "fx_lane_consts.hip.h"    // LaneConsts<N, GROUPS>: the 1024-point batch kernel's per-wavefront record of lane-derived constants
 
 // One first-pass item: R REAL inputs (imag = 0, as in performRealOnlyForwardTransform and in PitchAnalyser's re*re
 // spectrum), already in first_pass_index order.  Stages at length 1 have unit twiddles and real operands; the stage
@@ -445,8 +448,9 @@ __device__ __forceinline__ void first_pass_item(const float* x, const f2 (&ta)[9
 }
 
 // First pass of an un-split transform: the lane's P real inputs -> the complex image.
-template <int N, bool INV>
-__device__ __forceinline__ void fft_first_pass(const float (&xin)[Geo<N>::P], f2* cbuf, const float (&ftw)[18], int lane)
+// LC (here and below): the wavefront's record of lane-derived constants (LaneConsts), where the kernel keeps one.
+template <int N, bool INV, typename LC = LaneConsts<N>>
+__device__ __forceinline__ void fft_first_pass(const float (&xin)[Geo<N>::P], f2* cbuf, const float (&ftw)[18], int lane, const LC* lc = nullptr)
 {
     typedef Geo<N> G;
     constexpr int R = G::RA;
@@ -460,6 +464,7 @@ __device__ __forceinline__ void fft_first_pass(const float (&xin)[Geo<N>::P], f2
         if constexpr (RealExchange<N>::USE) {
             static_assert(R == 16 && G::GA == 1, "one 16-element item per lane");
             f2* img = cbuf + RealExchange<N>::row(lane);
+            if constexpr (LC::TRANSFORM) img = lc->row;
 #pragma unroll
             for (int q = 0; q < RealExchange<N>::SLOTS; q++) img[q] = e[RealExchange<N>::stored(q)];
         } else {
@@ -507,22 +512,24 @@ __device__ __forceinline__ void item16_stages_r(f2 (&e)[16], const f2 (&w)[15])
 
 // The second pass of the un-split 1024-point transform (one 16-element item per lane, behind the RealExchange) with the item left in
 // registers: the arithmetic of fft_pass, no store-back.  The wave's buffer is free on return.
-template <int N, bool INV>
-__device__ __forceinline__ void fft_second_pass_regs(const f2* cbuf, const f2* tw, int lane, f2 (&e)[16])
+template <int N, bool INV, typename LC = LaneConsts<N>>
+__device__ __forceinline__ void fft_second_pass_regs(const f2* cbuf, const f2* tw, int lane, f2 (&e)[16], const LC* lc = nullptr)
 {
     typedef Plan<N> PL;
     static_assert(LaneExchange<N>::AVAILABLE && RealExchange<N>::USE && PL::R1 == 16 && PL::L1 == 16 && N / 16 == 64, "one second-pass item per lane");
     const int k = lane % 16;
     const int slot = (int) ((RealExchange<N>::SLOT_OF >> (4 * k)) & 15ull);
-    const unsigned flip = ((RealExchange<N>::TWIN >> k) & 1u) << 31;
+    unsigned flip = ((RealExchange<N>::TWIN >> k) & 1u) << 31;
     const f2* src = cbuf + RealExchange<N>::row((lane / 16) * 16) + slot;
+    const f2* t1 = tw + PL::OFF1 + k;
+    if constexpr (LC::TRANSFORM) { flip = lc->flip; src = lc->src; t1 = lc->tw1; }
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         const f2 v = src[i * RealExchange<N>::SLOTS];
         e[i] = f2{v.x, __uint_as_float(__float_as_uint(v.y) ^ flip)};
     }
     wave_fence();                 // the wave has read the first exchange's image; the buffer may be rewritten
-    item16_stages<PL::L1, INV>(e, tw + PL::OFF1 + k);
+    item16_stages<PL::L1, INV>(e, t1);
 }
 
 // The second exchange in registers (LaneExchange<N>): in place on the lane's second-pass item; afterwards
@@ -622,8 +629,8 @@ static_assert(qpad<2048>(1023) < Geo<2048>::CSLOTS && qpad<4096>(2047) < Geo<409
 // written back and re-read: the spectral / harmonic analysers only read re of bins < N/2, the pitch analyser only
 // re*re, the lag search only the squared, lag-weighted real part.  The wave's buffer must be free (every lane has read
 // its inputs) when this is called.
-template <int N, bool INV, int OUT>
-__device__ __forceinline__ float fft_last_pass_consume(f2 (&e)[(N / Plan<N>::R2) / 64][Plan<N>::R2], f2* cbuf, const f2* tw, int lane, float scale, float* regs_out)
+template <int N, bool INV, int OUT, typename LC = LaneConsts<N>>
+__device__ __forceinline__ float fft_last_pass_consume(f2 (&e)[(N / Plan<N>::R2) / 64][Plan<N>::R2], f2* cbuf, const f2* tw, int lane, float scale, float* regs_out, const LC* lc = nullptr)
 {
     typedef Plan<N> PL;
     constexpr int R = PL::R2, L0 = PL::L2, GI = (N / R) / 64, TWOFF = PL::OFF2;
@@ -633,6 +640,7 @@ __device__ __forceinline__ float fft_last_pass_consume(f2 (&e)[(N / Plan<N>::R2)
     for (int g = 0; g < GI; g++) {
         const int k = lane + 64 * g;
         const f2* t1 = tw + TWOFF + k;
+        if constexpr (LC::TRANSFORM) t1 = lc->tw2 + 64 * g;
         if constexpr (R == 16) {
             item16_stages<L0, INV>(e[g], t1);
         } else {
@@ -646,7 +654,8 @@ __device__ __forceinline__ float fft_last_pass_consume(f2 (&e)[(N / Plan<N>::R2)
         for (int i = 0; i < R; i++) {
             const int bin = k + L0 * i;
             if (OUT == OUT_RE_LOW || OUT == OUT_RE_LOW_MAXABS) {
-                if (i < R / 2) fbuf[bimg<N>(lane) + bimg_step<N>(64 * g + L0 * i)] = e[g][i].x;     // bins >= N/2 are never read
+                if constexpr (LC::IMAGES) { if (i < R / 2) lc->bin_lane[bimg_step<N>(64 * g + L0 * i)] = e[g][i].x; }
+                else if (i < R / 2) fbuf[bimg<N>(lane) + bimg_step<N>(64 * g + L0 * i)] = e[g][i].x;     // bins >= N/2 are never read
                 if (OUT == OUT_RE_LOW_MAXABS && i < R / 4) aux = fmaxf(aux, fmaxf(fabsf(e[g][i].x), fabsf(e[g][i].y)));
             } else if (OUT == OUT_POWER) {
                 if constexpr (Geo<N>::GA == 1) {
@@ -657,8 +666,9 @@ __device__ __forceinline__ float fft_last_pass_consume(f2 (&e)[(N / Plan<N>::R2)
                     const int m = g + (L0 / 64) * i;
                     // j with r(j) == m  (r is its own inverse up to the digit swap used by first_pass_index)
                     const int j = (RA == 4) ? m : (RA == 8) ? (2 * (m & 3) + (m >> 2)) : (4 * (m & 3) + (m >> 2));
-                    regs_out[j] = __int_as_float(__builtin_amdgcn_ds_bpermute(
-                        rev4<Geo<N>::IDIG>(lane) << 2, __float_as_int(e[g][i].x * e[g][i].x)));
+                    int from = rev4<Geo<N>::IDIG>(lane) << 2;
+                    if constexpr (LC::REV) from = lc->bperm;
+                    regs_out[j] = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(e[g][i].x * e[g][i].x)));
                 } else {
                     fbuf[rimg<N>(lane) + rimg_step<N>(64 * g + L0 * i)] = e[g][i].x * e[g][i].x;
                 }
@@ -691,19 +701,19 @@ __device__ __forceinline__ float fft_last_pass_fused(f2* cbuf, const f2* tw, int
 }
 
 // Second and last pass of the 1024-point transform with the exchange between them done by lane swaps: no complex image at all.
-template <int N, bool INV, int OUT>
-__device__ __forceinline__ float fft_last_passes_lanes(f2* cbuf, const f2* tw, int lane, float scale, float* regs_out)
+template <int N, bool INV, int OUT, typename LC = LaneConsts<N>>
+__device__ __forceinline__ float fft_last_passes_lanes(f2* cbuf, const f2* tw, int lane, float scale, float* regs_out, const LC* lc = nullptr)
 {
     typedef LaneExchange<N> LX;
     f2 s[16];
-    fft_second_pass_regs<N, INV>(cbuf, tw, lane, s);
+    fft_second_pass_regs<N, INV>(cbuf, tw, lane, s, lc);
     second_exchange_regs<N>(s);
     f2 e[4][4];
 #pragma unroll
     for (int g = 0; g < 4; g++)
 #pragma unroll
         for (int i = 0; i < 4; i++) e[g][i] = s[LX::register_of(g, i)];
-    return fft_last_pass_consume<N, INV, OUT>(e, cbuf, tw, lane, scale, regs_out);
+    return fft_last_pass_consume<N, INV, OUT>(e, cbuf, tw, lane, scale, regs_out, lc);
 }
 
 // What the consumer keeps of a finished 16-element last-pass item (item k: element i is bin k + (N/16)*i).
@@ -738,15 +748,17 @@ template <int N> struct LazyLag {
     const f2* t1;       // tw + OFF2 + lane
     float scale;
     int lane;
-    __device__ __forceinline__ void load(const float (&xin)[Geo<N>::P], f2* cbuf, const f2* tw, const float (&ftw)[18], int lane_, float scale_)
+    template <typename LC = LaneConsts<N>>
+    __device__ __forceinline__ void load(const float (&xin)[Geo<N>::P], f2* cbuf, const f2* tw, const float (&ftw)[18], int lane_, float scale_, const LC* lc = nullptr)
     {
-        fft_first_pass<N, true>(xin, cbuf, ftw, lane_);
+        fft_first_pass<N, true>(xin, cbuf, ftw, lane_, lc);
         lane = lane_;
         scale = scale_;
         t1 = tw + PL::OFF2 + lane;
+        if constexpr (LC::TRANSFORM) t1 = lc->tw2;
         if constexpr (lane_exchange_used<N, true, OUT_LAG>()) {
             f2 s[16];
-            fft_second_pass_regs<N, true>(cbuf, tw, lane, s);
+            fft_second_pass_regs<N, true>(cbuf, tw, lane, s, lc);
             second_exchange_regs<N>(s);
 #pragma unroll
             for (int g = 0; g < 4; g++)
@@ -930,19 +942,19 @@ __device__ __forceinline__ float fft_split(const float (&xin)[Geo<N>::P], f2* cb
 }
 
 // Whole transform of one wavefront: P real inputs per lane (first-pass order) -> OUT (see above).
-template <int N, bool INV, int OUT, bool CTW = false>
+template <int N, bool INV, int OUT, bool CTW = false, typename LC = LaneConsts<N>>
 __device__ __forceinline__ float fft_from_regs(const float (&xin)[Geo<N>::P], f2* cbuf, const f2* tw, const float (&ftw)[18],
                                                int lane, float scale = 0.0f, float* regs_out = nullptr, const TwRegs<N>* twr = nullptr,
-                                               TwGlobal tg = TwGlobal{nullptr, false, f2{0.0f, 0.0f}})
+                                               TwGlobal tg = TwGlobal{nullptr, false, f2{0.0f, 0.0f}}, const LC* lc = nullptr)
 {
     typedef Plan<N> PL;
     static_assert(!CTW || Geo<N>::SPLIT, "the compact twiddle image belongs to a split transform");
     if constexpr (Geo<N>::SPLIT) {
         return fft_split<N, INV, OUT, CTW>(xin, cbuf, tw, ftw, lane, scale, regs_out, twr, tg);
     } else {
-        fft_first_pass<N, INV>(xin, cbuf, ftw, lane);
+        fft_first_pass<N, INV>(xin, cbuf, ftw, lane, lc);
         if constexpr (lane_exchange_used<N, INV, OUT>()) {
-            return fft_last_passes_lanes<N, INV, OUT>(cbuf, tw, lane, scale, regs_out);
+            return fft_last_passes_lanes<N, INV, OUT>(cbuf, tw, lane, scale, regs_out, lc);
         } else {
             fft_pass<N, PL::R1, PL::L1, PL::OFF1, INV, RealExchange<N>::USE>(cbuf, tw, lane);
             return fft_last_pass_fused<N, INV, OUT>(cbuf, tw, lane, scale, regs_out);

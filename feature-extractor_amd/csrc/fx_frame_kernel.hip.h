@@ -1,5 +1,8 @@
-// Re-materialisation points of lane-derived values (see opaque()).  (Letting the compiler hoist at some of them took 5 % of the
-// instructions out at 1024 points and not a microsecond: round 3, profiles/r03_variants.txt (e).)
+// Re-materialisation points of lane-derived values (see opaque()).  (Round 3, while the LDS exchange bound the 1024-point kernel: letting the
+// compiler hoist at some of them took 5 % of the instructions out and not a microsecond, profiles/r03_variants.txt (e).  Since the second
+// exchange is in registers that kernel is bound by VALU issue and instructions are time: its batch form keeps a hand-picked record of such
+// values across the frame loop -- LaneConsts, fx_lane_consts.hip.h: 2669 -> 2540 VALU instructions per frame, 2.594 -> 2.543 ms per 524 288
+// frames, 128 VGPRs, no scratch; profiles/lane_consts_ab.txt.  The points stay opaque for everything that is not in the record.)
 // A kernel with registers to spare (HOIST: the spectral analyser alone at 1024 points, 77 of the 128 VGPRs four wavefronts per SIMD allow) is
 // transparent at the top of the frame loop (point 15) and at the start of the spectral section (point 0), so that the frame's addresses and the
 // sixteen window gains of a lane are formed once per wavefront instead of once per frame: that kernel is bound by VALU issue (round 4:
@@ -110,10 +113,11 @@ __device__ __forceinline__ void load_half(const void* src, int sample_format, fl
 // the first / second half (the carried-over tail is always fp32).  N >= 512.
 // BLOCKS: the second half is the first N/2 samples of the stream `bs` (a channel's pending samples followed by its new block,
 // fx_blocks.hip.h) instead of a hop at src_b.
-template <int N, int FMT_A, int FMT_B, bool BLOCKS = false>
+// LC: the wavefront's record of lane-derived constants (LaneConsts), where the kernel keeps one: the stores' lane part comes from it.
+template <int N, int FMT_A, int FMT_B, bool BLOCKS = false, typename LC = LaneConsts<N>>
 __device__ __forceinline__ double load_window(const void* src_a, const void* src_b, float gain_a, float gain_b,
                                               float* rbuf, float* tail_out, int lane, const BlockStream bs = BlockStream{}, const bool a_stream = false,
-                                              const BlockStream bs_a = BlockStream{})
+                                              const BlockStream bs_a = BlockStream{}, const LC* lc = nullptr)
 {
     double ssq = 0.0;           // this lane's share of getRMSLevel's sum (ref RealTimeAnalyser.h:207): float squares, double sum
     constexpr int HALF = N / 2, QH = HALF / 256;
@@ -133,14 +137,16 @@ __device__ __forceinline__ double load_window(const void* src_a, const void* src
     for (int q = 0; q < QH; q++) {
         const int i = 256 * q + 4 * lane;
         const f4 v = widen_four<FMT_A>(ra[q]) * gain_a;        // ref AudioDataCollector.h:88 (x * 1.0f is exact)
-        *reinterpret_cast<f4*>(&rbuf[rimg<N>(i)]) = v;
+        if constexpr (LC::IMAGES) *reinterpret_cast<f4*>(lc->load_at + rimg_step<N>(256 * q)) = v;
+        else *reinterpret_cast<f4*>(&rbuf[rimg<N>(i)]) = v;
         if (Geo<N>::SPLIT) ssq += (double) (v.x * v.x) + (double) (v.y * v.y) + (double) (v.z * v.z) + (double) (v.w * v.w);
     }
 #pragma unroll
     for (int q = 0; q < QH; q++) {
         const int i = 256 * q + 4 * lane;
         const f4 v = widen_four<FMT_B>(rb[q]) * gain_b;
-        *reinterpret_cast<f4*>(&rbuf[rimg<N>(HALF + i)]) = v;
+        if constexpr (LC::IMAGES) *reinterpret_cast<f4*>(lc->load_at + rimg_step<N>(HALF + 256 * q)) = v;
+        else *reinterpret_cast<f4*>(&rbuf[rimg<N>(HALF + i)]) = v;
         if (tail_out) *reinterpret_cast<f4*>(tail_out + i) = v;
         if (Geo<N>::SPLIT) ssq += (double) (v.x * v.x) + (double) (v.y * v.y) + (double) (v.z * v.z) + (double) (v.w * v.w);
     }
@@ -348,8 +354,11 @@ static_assert(FrameLds<4096>::bytes(1, 8, false) <= 160 * 1024 && FrameLds<4096>
 // to give a CU an eighth wavefront at this size.
 // BLOCKS (one-frame calls, hop mode): p.in holds every channel's new BLOCK (rows of p.blk_in_row_bytes) and the hop analysed is the first
 // N/2 samples of [the channel's pending samples | its block] -- fx_push_samples without the re-blocking pass (FrameParams::block_mode).
-template <int N, bool DIRECT = false, bool HOIST = false, bool WIDE = false, bool BLOCKS = false> struct FrameWave {
+// LCG: the groups of the wavefront's record of lane-derived constants (LaneConsts; the 1024-point batch kernel), 0 = no record: `lc` is
+// then never read and every section forms what it needs from the lane number, frame by frame.
+template <int N, bool DIRECT = false, bool HOIST = false, bool WIDE = false, bool BLOCKS = false, unsigned LCG = 0u> struct FrameWave {
     typedef Geo<N> G;
+    typedef LaneConsts<N, LCG> LCT;
     static constexpr int M = G::M, P = G::P, U = G::U, HALF = N / 2;
 
     const FrameParams& p;
@@ -366,6 +375,7 @@ template <int N, bool DIRECT = false, bool HOIST = false, bool WIDE = false, boo
     double nyquist, rnyq, frpb;   // frpb: ref SpectralCharacteristics.h:64,105
     float  scale;       // JUCE inverse-transform scale 1/N
     int    c, T, t;     // channel, frames in this call, this frame
+    const LCT* lc = nullptr;    // the wavefront's lane-derived constants (LCG != 0)
 
     // |re| of the raw spectrum around and inside the lane's bins, kept from the harmonic FFT to the harmonic tail
     struct HarmonicSpectrum { float hre[U]; float left2, left1, right1; double sum, max; };
@@ -429,7 +439,7 @@ FX_MARK("load");
             const void* src_a = sr.a; const void* src_b = sr.b;
             const float gain_a = sr.gain_a, gain_b = sr.gain_b;
             if constexpr (N >= 512) {
-                FX_FORMATS(sr.fmt_a, sr.fmt_b, (ssq = load_window<N, FA, FB, BLOCKS>(src_a, src_b, gain_a, gain_b, rbuf, tail_dst, lane, sr.bs, sr.a_stream, sr.bs_a)));
+                FX_FORMATS(sr.fmt_a, sr.fmt_b, (ssq = load_window<N, FA, FB, BLOCKS>(src_a, src_b, gain_a, gain_b, rbuf, tail_dst, lane, sr.bs, sr.a_stream, sr.bs_a, lc)));
             } else {
                 load_half<N, HALF>(src_a, sr.fmt_a, gain_a, gain_a != 1.0f, rbuf, 0, nullptr, lane);
                 load_half<N, HALF>(src_b, sr.fmt_b, gain_b, gain_b != 1.0f, rbuf, HALF, tail_dst, lane);
@@ -443,6 +453,12 @@ FX_MARK("load");
     // getRMSLevel (a2, ref RealTimeAnalyser.h:207-208).  logRMS itself -- (float) log10(rms * 9 + 1) with
     // rms = (float) sqrt(sum / N) -- is a ~130-instruction fp64 computation of one number per wave; it is left
     // to fx_finalise_kernel (one thread per frame), and the spectral section brackets it instead (gate_threshold).
+    // where in the real image the inputs of the lane's g-th first-pass item start
+    __device__ __forceinline__ const float* first_pass_from(int lane, int g) const
+    {
+        if constexpr (LCT::REV) { static_assert(G::GA == 1, "one first-pass item per lane"); return lc->rbase; }
+        else return rbuf + first_pass_rbase<N>(lane, g);
+    }
     __device__ __forceinline__ double sum_squares(int lane, float (&xr)[P]) const
     {
 FX_MARK("rms");
@@ -451,7 +467,7 @@ FX_MARK("rms");
 #pragma unroll
         for (int g = 0; g < G::GA; g++)
 #pragma unroll
-            for (int j = 0; j < G::RA; j++) xr[g * G::RA + j] = (rbuf + first_pass_rbase<N>(lane, g))[first_pass_rstep<N>(j)];
+            for (int j = 0; j < G::RA; j++) xr[g * G::RA + j] = first_pass_from(lane, g)[first_pass_rstep<N>(j)];
         wave_fence();
         double s = 0.0;
 #pragma unroll
@@ -571,6 +587,12 @@ FX_MARK("flatprod");
         return pr;
     }
 
+    // the lane's own run of U bins in the bins image a transform left in the wave's buffer
+    __device__ __forceinline__ const float* own_bins(int lane) const
+    {
+        if constexpr (LCT::IMAGES) return lc->left2 + LaneOffsets<N>::left_back(2);
+        else return reinterpret_cast<const float*>(cbuf) + bimg<N>(U * lane);
+    }
     __device__ __forceinline__ void spectral(int lane, const float (&xr)[P], double sum_sq) const
     {
         float spec_aux = 0.0f;
@@ -584,8 +606,9 @@ FX_MARK("spec_fft");
             // in the falling half -- exact dyadic arithmetic, identical to bartlett_gain<N>(index)
 #pragma unroll
             for (int g = 0; g < G::GA; g++) {
-                const float base = (float) rev4<G::IDIG>(lane + 64 * g) * (2.0f / N);
-                const float nbase = 1.0f - base;
+                float base = (float) rev4<G::IDIG>(lane + 64 * g) * (2.0f / N);
+                float nbase = 1.0f - base;
+                if constexpr (LCT::REV) { base = LCT::fresh(lc->base); nbase = 1.0f - base; }       // (the base, not the sixteen gains: 16 registers)
 #pragma unroll
                 for (int j = 0; j < G::RA; j++) {
                     const int r = (G::RA == 4) ? j : (G::RA == 8) ? ((j >> 1) + 4 * (j & 1)) : ((j >> 2) + 4 * (j & 3));
@@ -594,7 +617,7 @@ FX_MARK("spec_fft");
                     xw[g * G::RA + j] = xr[g * G::RA + j] * gain;
                 }
             }
-            spec_aux = fft_from_regs<N, false, OUT_RE_LOW_MAXABS, WIDE>(xw, cbuf, tw, p.first_tw, lane, 0.0f, nullptr, twr, tw_global());   // a4
+            spec_aux = fft_from_regs<N, false, OUT_RE_LOW_MAXABS, WIDE>(xw, cbuf, tw, p.first_tw, lane, 0.0f, nullptr, twr, tw_global(), lc);   // a4
         }
         FX_STOP(6, FX_KEEP(spec_aux); return);
 FX_MARK("spec_sums");
@@ -604,7 +627,7 @@ FX_MARK("spec_sums");
             // ref SpectralCharacteristics.h:153: getMagnitude over the first M floats of the interleaved
             // buffer = max |re|, |im| over bins [0, M/2)
             float maxabs = spec_aux;
-            lds_load_block<U>(reinterpret_cast<const float*>(cbuf) + bimg<N>(U * lane), re);
+            lds_load_block<U>(own_bins(lane), re);
             const float tg = gate_threshold(sum_sq, re);
             // fillIntermediateValues :62-97 over the lane's bins m = U*lane + j.  The sums over bins that the features
             // need are moments of the magnitudes: B0 = sum mag (magnitudeSum), B1 = sum m*mag, B2 = sum m^2*mag, because
@@ -748,14 +771,22 @@ FX_MARK("harm1");
         // ---------------- harmonic analyser, part 1: raw (un-windowed) spectrum ---------------------
         // ref RealTimeAnalyser.h:161
         lane = FX_OPQ(2, lane);
-        fft_from_regs<N, false, OUT_RE_LOW, WIDE>(xr, cbuf, tw, p.first_tw, lane, 0.0f, nullptr, twr, tw_global());
+        fft_from_regs<N, false, OUT_RE_LOW, WIDE>(xr, cbuf, tw, p.first_tw, lane, 0.0f, nullptr, twr, tw_global(), lc);
         {
             const int b0 = U * lane;
             const float* relin = reinterpret_cast<const float*>(cbuf);
-            lds_load_block<U>(relin + bimg<N>(b0), hre);
+            lds_load_block<U>(own_bins(lane), hre);
+            if constexpr (LCT::IMAGES) {
+                // (the neighbours sit one padding gap from the lane's run: LaneOffsets<N>::left_back / right_step)
+                const float* around = lc->left2;
+                h_left2  = b0 >= 2 ? fabsf(around[0]) : 0.0f;
+                h_left1  = b0 >= 1 ? fabsf(around[1]) : 0.0f;
+                h_right1 = b0 + U < M ? fabsf(around[LaneOffsets<N>::left_back(2) + LaneOffsets<N>::right_step()]) : 0.0f;
+            } else {
             h_left2  = b0 >= 2 ? fabsf(relin[bimg<N>(b0 - 2)]) : 0.0f;
             h_left1  = b0 >= 1 ? fabsf(relin[bimg<N>(b0 - 1)]) : 0.0f;
             h_right1 = b0 + U < M ? fabsf(relin[bimg<N>(b0 + U)]) : 0.0f;
+            }
 #pragma unroll
             for (int j = 0; j < U; j++) {                                      // ref HarmonicCharacteristics.h:61-69
                 const double v = (double) hre[j];
@@ -798,7 +829,7 @@ FX_MARK("lpf");
         float x[P];
 #pragma unroll
         for (int i = 0; i < P; i += 4) {
-            const f4 v = *reinterpret_cast<const f4*>(&rbuf[rimg<N>(P * lane + i)]);
+            const f4 v = *reinterpret_cast<const f4*>(LCT::IMAGES ? lc->warm + LaneOffsets<N>::warmup_back() + i : &rbuf[rimg<N>(P * lane + i)]);
             x[i] = v.x; x[i + 1] = v.y; x[i + 2] = v.z; x[i + 3] = v.w;
         }
         float yin = 0.0f;                             // y[P*lane - 1] used as this chunk's input
@@ -808,7 +839,7 @@ FX_MARK("lpf");
             for (int q = 0; q < KW / 4; q++) {
                 const int n0 = first - KW + 4 * q;    // multiple of 4: the whole group is in range or not
                 if (n0 >= 0) {
-                    const f4 v = *reinterpret_cast<const f4*>(&rbuf[rimg<N>(n0)]);
+                    const f4 v = *reinterpret_cast<const f4*>(LCT::IMAGES ? lc->warm + 4 * q : &rbuf[rimg<N>(n0)]);
                     const float w[4] = {v.x, v.y, v.z, v.w};
                     float aw[4];
                     scaled_pairs<4>(a, w, aw);
@@ -854,8 +885,9 @@ FX_MARK("lpf");
         // A lane's P samples lie in one half of the window; the gains w0 + i*wstep are exact dyadic
         // numbers (so the fma rounds nothing) and equal bartlett_gain<N>(P*lane + i).
         lane = FX_OPQ(3, lane);
-        const float w0 = bartlett_gain<N>(P * lane);
-        const float wstep = lane < 32 ? (2.0f / N) : -(2.0f / N);
+        float w0 = bartlett_gain<N>(P * lane);
+        float wstep = lane < 32 ? (2.0f / N) : -(2.0f / N);
+        if constexpr (LCT::IMAGES) { w0 = LCT::fresh(lc->w0); wstep = lc->wstep; }
 #pragma unroll
         for (int i = 0; i < P; i += 4) {
             f4 v;
@@ -863,7 +895,7 @@ FX_MARK("lpf");
             v.y = y[i + 1] * __builtin_fmaf(wstep, (float) (i + 1), w0);
             v.z = y[i + 2] * __builtin_fmaf(wstep, (float) (i + 2), w0);
             v.w = y[i + 3] * __builtin_fmaf(wstep, (float) (i + 3), w0);
-            *reinterpret_cast<f4*>(&rbuf[rimg<N>(P * lane + i)]) = v;
+            *reinterpret_cast<f4*>(LCT::IMAGES ? lc->warm + LaneOffsets<N>::warmup_back() + i : &rbuf[rimg<N>(P * lane + i)]) = v;
         }
         wave_fence();
     }
@@ -926,12 +958,12 @@ FX_MARK("pitch_fft");
 #pragma unroll
         for (int g = 0; g < G::GA; g++)
 #pragma unroll
-            for (int j = 0; j < G::RA; j++) xf[g * G::RA + j] = (rbuf + first_pass_rbase<N>(lane, g))[first_pass_rstep<N>(j)];
+            for (int j = 0; j < G::RA; j++) xf[g * G::RA + j] = first_pass_from(lane, g)[first_pass_rstep<N>(j)];
         wave_fence();
         // a11 getComplexConjugateMultiplication, ref PitchAnalyser.h:83-108: re*re, imag := 0, delivered in the order the
         // inverse transform's first pass wants it
         float xp[P];
-        fft_from_regs<N, false, OUT_POWER, WIDE>(xf, cbuf, tw, p.first_tw, lane, 0.0f, xp, twr, tw_global());  // ref RealTimeAnalyser.h:160
+        fft_from_regs<N, false, OUT_POWER, WIDE>(xf, cbuf, tw, p.first_tw, lane, 0.0f, xp, twr, tw_global(), lc);  // ref RealTimeAnalyser.h:160
         FX_STOP(3, for (int j = 0; j < P; j++) FX_KEEP(xp[j]); return 1.0);
 FX_MARK("power");
         lane = FX_OPQ(7, lane);
@@ -950,7 +982,7 @@ FX_MARK("ifft");
         float lag;
         if constexpr (N == 1024) {
             LazyLag<N> lz;                                                 // a12 inverse, ref :110-121, its last pass on demand
-            lz.load(xf, cbuf, tw, p.first_tw, lane, scale);
+            lz.load(xf, cbuf, tw, p.first_tw, lane, scale, lc);
             vreg[0] = lz.head(0);
             vreg[1] = lz.head(1);
             FX_STOP(4, FX_KEEP(vreg[0]); FX_KEEP(vreg[1]); return 1.0);
@@ -1096,6 +1128,13 @@ FX_MARK("harm2");
     }
 };
 
+// Which groups of LaneConsts a form of the frame kernel keeps: the 1024-point batch forms with both analysers.  (The spectral-only form has
+// its own HOIST, the one-frame forms have no frame loop to hoist out of, and the other sizes no registers to spare.)
+template <int N, bool SPEC, bool HARM, bool DIRECT, bool BLOCKS> constexpr unsigned lane_consts_groups()
+{
+    return (N == 1024 && SPEC && HARM && !DIRECT && !BLOCKS) ? LANE_CONSTS_GROUPS : 0u;
+}
+
 // SPEC / HARM: which of the reference's two analysers run (RealTimeSpectralAnalyser,
 // RealTimeHarmonicAnalyser -- both by default, as AnalyserTrackController constructs them)
 // DIRECT: calls of one frame per channel (FrameWave): p.T == 1, p.waves_per_ch == 1, a workgroup is p.ch_per_wg channels, no flux
@@ -1192,6 +1231,11 @@ __device__ __forceinline__ void frame_kernel_body(const FrameParams& p_arg)
 
     TwRegs<N> twr;
     if constexpr (TwRegs<N>::USE) twr.load(tw, lane0);
+    // the batch forms of the 1024-point kernel keep the values a lane derives from its number alone in registers for the wavefront's
+    // whole life (LaneConsts): formed here, from lane0 and the wave's buffer only -- the channel, the chunk and the frames are not in it
+    constexpr unsigned LCG = lane_consts_groups<N, SPEC, HARM, DIRECT, BLOCKS>();
+    LaneConsts<N, LCG> lcs;
+    if constexpr (LCG != 0u) lcs.form(lane0, cbuf, tw);
 
     const double nyquist = p.nyquist;
     const double rnyq = 1.0 / nyquist;
@@ -1214,12 +1258,12 @@ __device__ __forceinline__ void frame_kernel_body(const FrameParams& p_arg)
     };
     for (int t = live ? (CLAIM ? next_frame(0) : t_begin + slot) : t_end; t < t_end; t = next_frame(t)) {
         constexpr bool HOIST = SPEC && !HARM && N == 1024;       // (see FX_OPQ)
-        const int lane = FX_OPQ(15, lane0);
+        const int lane = LaneConsts<N, LCG>::TOP ? lane0 : FX_OPQ(15, lane0);
         // uniform per-frame results go to LDS as soon as they exist instead of occupying ~28 VGPRs
         // in every lane for the whole frame
         FramePart* fpl = p.part + ((size_t) c * T + t);
         if (lane == 0) fpl->flags = 0;            // the harmonic tail sets it; the other fields are read only where written
-        const FrameWave<N, DIRECT, HOIST, WIDE, BLOCKS> w{p, tw, &twr, prev, turn, cbuf, rbuf, fpl, nyquist, rnyq, frpb, scale, c, T, t};
+        const FrameWave<N, DIRECT, HOIST, WIDE, BLOCKS, LCG> w{p, tw, &twr, prev, turn, cbuf, rbuf, fpl, nyquist, rnyq, frpb, scale, c, T, t, &lcs};
 
         const double ssq_lane = w.load_frame(lane);
         float xr[P];
@@ -1246,7 +1290,7 @@ __device__ __forceinline__ void frame_kernel_body(const FrameParams& p_arg)
         }
         FX_STOP(6, continue); FX_STOP(7, continue); FX_STOP(8, continue); FX_STOP(9, continue); FX_STOP(10, continue);
         if constexpr (HARM) {
-            typename FrameWave<N, DIRECT, HOIST, WIDE, BLOCKS>::HarmonicSpectrum hs;
+            typename FrameWave<N, DIRECT, HOIST, WIDE, BLOCKS, LCG>::HarmonicSpectrum hs;
             if constexpr (G::SPLIT) w.template load_raw<true>(lane, xr);
             w.harmonic_spectrum(lane, xr, hs);
             FX_STOP(11, FX_KEEP(hs.sum); FX_KEEP(hs.max); FX_KEEP(hs.left2); FX_KEEP(hs.left1); FX_KEEP(hs.right1); for (int j = 0; j < G::U; j++) FX_KEEP(hs.hre[j]); continue);
