@@ -753,6 +753,12 @@ FX_MARK("spec_pass2");
             double max_e = (double) maxabs;                                    // :153
             if (max_mag > max_e) max_e = max_mag;                              // :161-162
             if (lane == 0) {
+                // :153 calls JUCE's getMagnitude, which this project restates as a scalar loop (oracle/fx_oracle.c buf_magnitude,
+                // tools/refdiff/juce_standin.h): minimum and maximum start at the buffer's first float -- bin 0's real part, this
+                // lane's -- and are only compared from there on, so a NaN there stays (every compare with it is false, :161-162
+                // included) and the slope is left at 0 (:165-167), while a NaN anywhere else is passed over, as fmaxf does.  The
+                // authority is that restatement, not a reference header: a JUCE build with SIMD min / max may treat NaN otherwise.
+                if (re[0] != re[0]) max_e = (double) re[0];
                 fpl->mag_sum = mag_sum; fpl->lhr = lhr; fpl->flux = flux; fpl->flat_sum = flat_sum; fpl->prod = prod;
                 fpl->max_e = max_e; fpl->b1 = b1; fpl->b2 = b2; fpl->cnt = (float) cnt;
             }

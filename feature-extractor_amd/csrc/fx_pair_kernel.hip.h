@@ -655,7 +655,8 @@ FX_MARK("p_spec_x2");
                 double* s = slot(0, 0);
                 s[0] = bcast63(inc.mant); s[1] = (double) __builtin_amdgcn_readlane(inc.exp, 63); s[2] = risky_lanes ? 1.0 : 0.0; s[3] = pr_end;
                 s[4] = flux; s[5] = vsum; s[6] = direct;
-                const double max_e = max_mag > (double) maxabs ? max_mag : (double) maxabs;        // :153, :161-162
+                double max_e = max_mag > (double) maxabs ? max_mag : (double) maxabs;              // :153, :161-162
+                if (re[0] != re[0]) max_e = (double) re[0];        // bin 0's real part NaN: the restated getMagnitude's NaN (FrameWave::spectral)
                 fpl->mag_sum = mag_sum; fpl->lhr = lhr; fpl->flat_sum = flat_sum; fpl->max_e = max_e; fpl->b1 = b1; fpl->b2 = b2;
                 fpl->cnt = (float) cnt;
             }

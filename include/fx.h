@@ -18,7 +18,11 @@
  *   - all work is enqueued on the context's HIP stream; fx_sync() waits for it.
  *   - feature vectors use the AudioFeatures slot order (RealTimeAnalyser.h:19-30).
  *   - numeric behaviour (NaN, inf, values > 1) is the reference's; nothing is
- *     clamped or "fixed".
+ *     clamped or "fixed".  The reference defines no answer for the harmonic energy
+ *     ratio, the odd/even ratio and the inharmonicity of a frame whose raw f0 is
+ *     not > 0 (it indexes bins out of bounds, HarmonicCharacteristics.h:161-166,205):
+ *     those three slots are deterministic there, nothing more.  Every other slot,
+ *     and every slot of a FX_SPECTRAL_ONLY context, is the reference's for every input.
  *   - there is NO CPU fallback: if no gfx950 device is usable every call fails
  *     with FX_ERR_NO_DEVICE.
  */

@@ -586,6 +586,10 @@ static double frequency_ratio(double f1, double f2)
 /* :200-210 */
 static double max_bin_in_neighbourhood(int centre, int range, const float* normed, int num_bins)
 {
+    /* The oracle's own guard: with f0 <= 0 (lag -1: every cnd NaN or inf) getBinForFrequency is negative and the reference reads
+     * binMagnitudes[centre] out of bounds (:161-166, :205) -- HER, OER and inharmonicity have no reference value in such a frame.  A probe
+     * below bin 0 adds nothing here, as in the kernels (fx_frame_kernel.hip.h, `bin >= 0 && bin < M`); for f0 > 0 no centre is negative. */
+    if (centre < 0) return 0.0;
     const int start = centre - range >= 0 ? centre - range : 0;
     const int end   = centre + range < num_bins ? centre + range : num_bins;
     double mx = normed[centre];

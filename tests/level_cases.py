@@ -26,7 +26,8 @@ BAND = (-9.0, -9.5, -10.0, -10.5, -11.0, -11.5, -12.0, -12.5, -13.0)          # 
 BELOW = (-15.0, -20.0, -30.0, -36.0)                                           # (-36: the samples are partly subnormal)
 SUBNORMAL = (-39.0, -42.0, -45.0)                                              # all subnormal; at -45 partly zero
 LOUD = (1.0, 3.0, 5.0)
-# A loud level is kept only where the oracle's output is finite with f0 > 0.  Every (base, e) dropped here is dropped for one reason: the
+# Loud levels, overflow and non-finite samples are held by tests/overflow_cases.py; here a loud level is kept only where the oracle's output
+# is finite with f0 > 0.  Every (base, e) dropped here is dropped for one reason: the
 # serial flatness product (SpectralCharacteristics.h:89-94) overflows to inf, so the raw flatness slot is inf and its smoothed value
 # inf or NaN.  (f0 > 0 holds at all three loud levels at every size: the lag is never -1 and the reference does not index out of bounds;
 # that overflow is what tests/signals.py's `levels` covers.)  tests/test_levels_cpu.py holds that exactly these are not finite.

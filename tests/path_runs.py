@@ -18,15 +18,17 @@ def _calls(an, hops, per, kinds=None):
 def _ring(gpu_fx, an, hops, per, kinds=None, depth=2):
     st = gpu_fx.HopStream(an, per, slots=3)
     got = []
-    for t in range(0, hops.shape[1], per):
-        if st.in_flight() == depth:
+    try:                                            # (the ring is closed before its analyser, also when an assertion fails)
+        for t in range(0, hops.shape[1], per):
+            if st.in_flight() == depth:
+                got.append(st.collect())
+            st.push(hops[:, t:t + per])
+            if kinds is not None:
+                assert [l["kind"] for l in an.last_launches()] == list(kinds), (t, an.last_launches())
+        while st.in_flight():
             got.append(st.collect())
-        st.push(hops[:, t:t + per])
-        if kinds is not None:
-            assert [l["kind"] for l in an.last_launches()] == list(kinds), (t, an.last_launches())
-    while st.in_flight():
-        got.append(st.collect())
-    st.close()
+    finally:
+        st.close()
     return tuple(np.concatenate([g[k] for g in got], axis=1) for k in (0, 1))
 
 

@@ -135,9 +135,10 @@ def assert_features_close(got, want, rtol=1e-5, names=None, what=""):
 from oracle.ulp import SLOTS, ULP_BUDGET, ULP_INFINITE, ulp_budget, ulp_distance  # noqa: E402,F401
 
 
-def assert_features_within(got, want, budget, names=SLOTS, what=""):
+def assert_features_within(got, want, budget, names=SLOTS, what="", defined=None):
     """every slot within its ulp budget (a 12-vector, ulp_budget()); onset (slot 0) bit-exact; NaN == NaN, inf == inf.
-    Returns the largest distance seen per slot."""
+    defined: a boolean array like got, False at the slot-frames that are not compared (tests/overflow_cases.py: where the reference
+    defines no answer); the onset column is always compared.  Returns the largest distance seen per slot."""
     got = np.asarray(got, np.float32)
     want = np.asarray(want, np.float32)
     assert got.shape == want.shape, (got.shape, want.shape)
@@ -147,6 +148,10 @@ def assert_features_within(got, want, budget, names=SLOTS, what=""):
     w = want.reshape(-1, 12)
     assert np.array_equal(g[:, 0], w[:, 0], equal_nan=True), "%s onset column differs at rows %s" % (what, np.nonzero(g[:, 0] != w[:, 0])[0][:8])
     d = ulp_distance(g, w)
+    if defined is not None:
+        defined = np.asarray(defined, bool)
+        assert defined.shape == got.shape and defined.reshape(-1, 12)[:, 0].all(), "the mask is not the vectors' shape, or covers the onset column"
+        d = np.where(defined.reshape(-1, 12), d, 0)
     bad = np.argwhere(d > budget[None, :])
     if bad.size:
         r, f = bad[0]

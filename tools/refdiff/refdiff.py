@@ -43,8 +43,9 @@ def build(mode):
 
 
 def run(hops, window_size, order=0, onset_type=1, onset_window=5, onset_sensitivity=0.7, gain=1.0,
-        sample_rate=48000.0, mode="cr", workdir=None):
-    """hops [C][T][N/2] float32 -> (raw [C][T][12], smoothed [C][T][12]) from the reference's headers."""
+        sample_rate=48000.0, mode="cr", workdir=None, analysers=3):
+    """hops [C][T][N/2] float32 -> (raw [C][T][12], smoothed [C][T][12]) from the reference's headers.
+    analysers: 1 the spectral analyser alone, 2 the harmonic analyser alone, 3 both (the driver's own default: nothing is passed on)."""
     import tempfile
     hops = np.ascontiguousarray(hops, np.float32)
     C, T, half = hops.shape
@@ -55,7 +56,7 @@ def run(hops, window_size, order=0, onset_type=1, onset_window=5, onset_sensitiv
         with open(fin, "wb") as f:
             f.write(struct.pack("<6i2fd", window_size, C, T, order, onset_type, onset_window, onset_sensitivity, gain, sample_rate))
             f.write(hops.tobytes())
-        subprocess.check_call([exe, fin, fout])
+        subprocess.check_call([exe, fin, fout] + ([] if analysers == 3 else [str(int(analysers))]))
         out = np.fromfile(fout, np.float32)
     n = C * T * 12
     return out[:n].reshape(C, T, 12), out[n:2 * n].reshape(C, T, 12)

@@ -4,7 +4,9 @@
 // Build container only; see tools/refdiff/README.md.  Nothing of the reference is copied: the headers are
 // #included by path at compile time.
 //
-//   refdiff_driver <in.bin> <out.bin>
+//   refdiff_driver <in.bin> <out.bin> [analysers]
+//   analysers: 1 the spectral analyser alone, 2 the harmonic analyser alone, 3 (the default) both, as the application constructs them;
+//              the slots of an analyser that is not constructed keep raw 0 and getValue 0/0
 //   in : int32 N, C, T, order, onset_type, onset_window; float32 onset_sensitivity, gain; float64 sample_rate;
 //        float32 hops[C][T][N/2]
 //   out: float32 raw[C][T][12], smoothed[C][T][12], lag[C][T]
@@ -24,6 +26,8 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <memory>
 
 struct Header { int32_t N, C, T, order, onset_type, onset_window; float onset_sensitivity, gain; double sample_rate; };
 
@@ -35,7 +39,9 @@ static void feed (AudioDataCollector& c, const float* hop, int n)
 
 int main (int argc, char** argv)
 {
-    if (argc != 3) return 2;
+    if (argc != 3 && argc != 4) return 2;
+    const int analysers = argc == 4 ? atoi (argv[3]) : 3;
+    if (analysers < 1 || analysers > 3) return 2;
     FILE* f = fopen (argv[1], "rb");
     if (! f) return 2;
     Header h;
@@ -57,19 +63,24 @@ int main (int argc, char** argv)
         AudioFeatures shared, harmOwn;
         AudioFeatures& specFeatures = shared;
         AudioFeatures& harmFeatures = h.order == 2 ? harmOwn : shared;
-        RealTimeSpectralAnalyser spectral (specCollector, specFeatures, h.N, h.sample_rate);
-        RealTimeHarmonicAnalyser harmonic (harmCollector, harmFeatures, h.N, h.sample_rate);
-        spectral.setOnsetDetectionType ((OnsetDetector::eOnsetDetectionType) h.onset_type);
-        spectral.setOnsetDetectionSensitivity (h.onset_sensitivity);
-        if (h.onset_window > 0) spectral.setOnsetWindowLength (h.onset_window);
+        std::unique_ptr<RealTimeSpectralAnalyser> spectral;
+        std::unique_ptr<RealTimeHarmonicAnalyser> harmonic;
+        if (analysers & 1) spectral.reset (new RealTimeSpectralAnalyser (specCollector, specFeatures, h.N, h.sample_rate));
+        if (analysers & 2) harmonic.reset (new RealTimeHarmonicAnalyser (harmCollector, harmFeatures, h.N, h.sample_rate));
+        if (spectral)
+        {
+            spectral->setOnsetDetectionType ((OnsetDetector::eOnsetDetectionType) h.onset_type);
+            spectral->setOnsetDetectionSensitivity (h.onset_sensitivity);
+            if (h.onset_window > 0) spectral->setOnsetWindowLength (h.onset_window);
+        }
 
         for (int t = 0; t < h.T; t++)
         {
             const float* hop = hops.data() + ((size_t) c * h.T + t) * half;
             feed (specCollector, hop, half);
             feed (harmCollector, hop, half);
-            if (h.order == 1) { harmonic.step(); spectral.step(); }
-            else              { spectral.step(); harmonic.step(); }
+            if (h.order == 1) { if (harmonic) harmonic->step(); if (spectral) spectral->step(); }
+            else              { if (spectral) spectral->step(); if (harmonic) harmonic->step(); }
             float* r = raw.data() + ((size_t) c * h.T + t) * 12;
             float* s = sm.data() + ((size_t) c * h.T + t) * 12;
             for (int i = 0; i < 12; i++)
@@ -80,7 +91,7 @@ int main (int argc, char** argv)
                 r[i] = a.smoothedFeatures[(size_t) i].history.back();
                 s[i] = a.getValue ((AudioFeatures::eAudioFeature) i);
             }
-            lag[(size_t) c * h.T + t] = harmonic.getPitchAnalyser().getNormalisedLagPosition().getX() * (float) (2 * h.N);
+            lag[(size_t) c * h.T + t] = ! harmonic ? 0.0f : harmonic->getPitchAnalyser().getNormalisedLagPosition().getX() * (float) (2 * h.N);
         }
     }
     f = fopen (argv[2], "wb");
