@@ -211,6 +211,42 @@ class BatchAnalyser:
         capi.check(self._lib.fx_get_channel_frames(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         return out
 
+    # ---- moving tracks between contexts (include/fx.h, fx_export_channels / fx_import_channels) ----
+    def track_state_bytes(self):
+        """Bytes of one track's record (a multiple of 16)."""
+        return int(self._lib.fx_track_state_bytes(self._h))
+
+    def export_tracks(self, channels, device=False):
+        """The listed tracks' whole state, one record each: uint8 [n][track_state_bytes()], numpy or (device=True) a CUDA torch tensor.
+        Duplicates allowed; nothing in the context changes.  Synchronises the context's stream: the records are valid on return."""
+        a, ptr = self._track_list(channels)
+        size = self.track_state_bytes()
+        if device:
+            import torch
+            out = torch.empty((int(a.size), size), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            if a.size:
+                self._ordered(out.device, self._lib.fx_export_channels, self._h, ptr, int(a.size), ctypes.c_void_p(out.data_ptr()), out.numel(), capi.MEM_DEVICE)
+        else:
+            out = np.empty((int(a.size), size), np.uint8)
+            capi.check(self._lib.fx_export_channels(self._h, ptr, int(a.size), out.ctypes.data_as(ctypes.c_void_p), out.size, capi.MEM_HOST))
+        return out
+
+    def import_tracks(self, channels, state):
+        """Records of export_tracks (of this or any compatible context: same window size, order, analysers, kernel family and pending
+        samples) into the listed slots, record i into channels[i]; no slot twice.  `state`: uint8, numpy (any shape with the records back
+        to back) or a CUDA torch tensor.  The tracks go on exactly as they would have where they were."""
+        a, ptr = self._track_list(channels)
+        if hasattr(state, "data_ptr"):
+            if str(state.dtype) != "torch.uint8" or not state.is_cuda or not state.is_contiguous():
+                raise ValueError("track records on the device are a contiguous CUDA uint8 tensor")
+            self._ordered(state.device, self._lib.fx_import_channels, self._h, ptr, int(a.size), ctypes.c_void_p(state.data_ptr()), state.numel(), capi.MEM_DEVICE)
+            return
+        s = np.asarray(state)
+        if s.dtype != np.uint8:
+            raise ValueError("track records are uint8, not %s" % s.dtype)
+        s = np.ascontiguousarray(s)
+        capi.check(self._lib.fx_import_channels(self._h, ptr, int(a.size), s.ctypes.data_as(ctypes.c_void_p), s.size, capi.MEM_HOST))
+
     # ---- launch-shape knobs (within a kernel family they never change a result bit; waves_per_frame selects the family) ----
     def get_tuning(self):
         t = capi.Tuning()

@@ -84,13 +84,15 @@ def _prototypes():
     P = ctypes.POINTER
     vpp, ip, fp, dp, llp, tp, strings = P(vp), P(i), P(f), P(d), P(ll), P(Tuning), P(cp)
     ull = ctypes.c_ulonglong
-    st = i                  # fx_status and int: ctypes' default restype
+    st = i                  # fx_status and int: ctypes' default restype (fx_track_state_bytes' size_t is at most 2432 + 6 * 4096: read as int)
     return [
         ("fx_create", [vpp, i, i, i, d, u], st), ("fx_destroy", [vp], st), ("fx_reset_state", [vp], st),
         ("fx_set_sample_rate", [vp, d], st), ("fx_set_onset_sensitivity", [vp, f], st), ("fx_set_onset_window", [vp, i], st),
         ("fx_set_onset_type", [vp, i], st), ("fx_set_gain", [vp, f], st),
         ("fx_set_channel_gains", [vp, fp], st), ("fx_set_channel_onset", [vp, fp, ip, ip], st), ("fx_get_channel_settings", [vp, fp, fp, ip, ip], st),
         ("fx_reset_channels", [vp, ip, i], st), ("fx_clear_pending_channels", [vp, ip, i], st), ("fx_get_channel_frames", [vp, llp], st),
+        ("fx_track_state_bytes", [vp], st), ("fx_export_channels", [vp, ip, i, vp, ctypes.c_size_t, i], st),
+        ("fx_import_channels", [vp, ip, i, vp, ctypes.c_size_t, i], st),
         ("fx_push_hops", [vp, vp, i, i, i, vp, vp], st), ("fx_push_samples", [vp, vp, i, i, i, vp, vp, ip], st),
         ("fx_set_channel_map", [vp, ip], st), ("fx_push_interleaved", [vp, vp, i, i, i, i, vp, vp, ip], st),
         ("fx_pending_samples", [vp], st), ("fx_clear_pending", [vp], st), ("fx_process_frames", [vp, vp, i, i, i, vp, vp], st),

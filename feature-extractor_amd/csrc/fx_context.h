@@ -1,6 +1,6 @@
 // fx_context.h -- the context behind the C ABI (include/fx.h), shared by the shim's host units (fx_capi.cpp, fx_plan.cpp, fx_stream.cpp,
 // fx_comm.cpp) and the units that attach through its hooks (fx_taps.hip, fx_interleave.hip, fx_events.hip, fx_tracks.hip,
-// fx_osc_table.hip, fx_osc_bundle.hip).  Internal.
+// fx_osc_table.hip, fx_osc_bundle.hip, fx_track_state.hip).  Internal.
 #ifndef FX_CONTEXT_H
 #define FX_CONTEXT_H
 
@@ -60,6 +60,7 @@ struct fx_taps;
 struct fx_interleave;   // fx_interleave.hip
 struct fx_events;       // fx_events.hip
 struct fx_tracks;       // fx_tracks.hip
+struct fx_track_state;  // fx_track_state.hip
 // The OSC address table in force (fx_osc_table.hip makes and frees it; fx_osc_bundle.hip reads it): one device allocation, [C][128]
 // bytes of rows, then int len[C]; the messages' lengths on the host.
 struct fx_osc_table {
@@ -179,6 +180,11 @@ struct fx_context {
     // set.  fx_set_osc_addresses installs the hook fx_destroy calls.  A setting: no reset touches it.
     fx_osc_table* osc_table = nullptr;
     void (*osc_table_release)(fx_context*) = nullptr;
+
+    // moving tracks between contexts (fx_track_state.hip): the entry list's staging, its device copy and the records' scratch; null
+    // until the first fx_export_channels / fx_import_channels, which installs the hook fx_destroy calls.
+    fx_track_state* track_state = nullptr;
+    void (*track_state_release)(fx_context*) = nullptr;
 };
 
 // The per-track rows (fx_capi.cpp), for the units that change them.  fx_channel_rows: what every track runs with now -- the table's rows,

@@ -256,6 +256,83 @@ struct ResetParams {
 };
 hipError_t launch_reset_channels_kernel(const ResetParams& p, hipStream_t stream);
 
+// fx_export_channels / fx_import_channels (fx_track_state.hip): a track's whole state as one record of 16-byte pieces --
+//   [header: 5][latest vector: 3][ring, 48 rows of 3 in TRACK order][flux row][tail row][pending row], the three rows N/8 pieces each
+// -- 2432 + 6 N bytes.  The header is all a destination needs to refuse or to place the record; nothing in a record depends on the
+// source context's frame index, ping-pong indices, channel count or slot.
+constexpr unsigned TRACK_MAGIC = 0x54527846u;   // "FxRT" as the bytes lie
+constexpr unsigned TRACK_LAYOUT_VERSION = 1;
+struct TrackHeader {
+    unsigned  magic, version;
+    int       N;
+    unsigned  flags;            // the create flags that shape state: FX_ORDER_MASK | FX_SPECTRAL_ONLY | FX_HARMONIC_ONLY
+    int       family;           // wavefronts per frame in force (uses_pairs, fx_plan.h): 1 or 2
+    int       pending;          // samples pending per channel (one per context) ...
+    int       carry_format;     // ... and their format; FX_SAMPLE_F32 where nothing is pending
+    int       onset_window;
+    long long frames;           // the track's own frame count: frames_seen - first_frame
+    long long onset_frames;     // frames_seen - onset_reset_frame
+    float     gain, sensitivity, onset_multiplier;
+    int       onset_type;
+    unsigned  record_bytes;     // 2432 + 6 N
+    unsigned  zero[3];
+};
+static_assert(sizeof(TrackHeader) == 80, "five 16-byte pieces");
+constexpr int TRACK_HEADER_PIECES = 5, TRACK_LATEST_PIECES = FX_NUM_FEATURES / 4, TRACK_ROW_PIECES = FX_NUM_FEATURES / 4;
+constexpr int TRACK_RING_PIECES = HLEN * TRACK_ROW_PIECES;
+constexpr int TRACK_FIXED_PIECES = TRACK_HEADER_PIECES + TRACK_LATEST_PIECES + TRACK_RING_PIECES;      // 152
+inline size_t track_record_pieces(int N) { return (size_t) TRACK_FIXED_PIECES + 3 * (size_t) (N / 8); }
+// One list entry as the kernels read it (wave-uniform): the record's header as the host wrote it (export) or read it (import), and the slot.
+struct TrackEntry {
+    TrackHeader header;
+    int         channel;
+    int         pad_[3];
+};
+static_assert(sizeof(TrackEntry) == 96, "entries are 16-byte pieces");
+// Where piece q of a record lives in the context's tables.  Ring: record row k holds the track's frame frames - HLEN + k, whose global
+// index is frames_seen - HLEN + k, so it is ring row (hist_base + k) mod HLEN with hist_base = frames_seen mod HLEN -- the same
+// rotation for every track of a context, and pieces map to pieces (a row is three).  `at`: the piece within the channel's row(s) of
+// that table; ring_row: the RECORD's row k (its frame exists iff frames - HLEN + k >= 0).
+enum { TRACK_IN_HEADER = 0, TRACK_IN_LATEST, TRACK_IN_RING, TRACK_IN_PREV, TRACK_IN_TAIL, TRACK_IN_CARRY };
+struct TrackPiece { int where, at, ring_row; };
+__host__ __device__ inline TrackPiece track_piece(int q, int row_pieces, int hist_base)
+{
+    if (q < TRACK_HEADER_PIECES) return {TRACK_IN_HEADER, q, 0};
+    q -= TRACK_HEADER_PIECES;
+    if (q < TRACK_LATEST_PIECES) return {TRACK_IN_LATEST, q, 0};
+    q -= TRACK_LATEST_PIECES;
+    if (q < TRACK_RING_PIECES) {
+        const int k = q / TRACK_ROW_PIECES;
+        int row = hist_base + k;
+        if (row >= HLEN) row -= HLEN;
+        return {TRACK_IN_RING, row * TRACK_ROW_PIECES + (q - k * TRACK_ROW_PIECES), k};
+    }
+    q -= TRACK_RING_PIECES;
+    const int which = q / row_pieces;
+    return {TRACK_IN_PREV + which, q - which * row_pieces, 0};
+}
+// the bytes of word w of piece `at` of a pending row that lie below carry_bytes, as a mask (the rest of a record's pending row is zeros)
+__host__ __device__ inline unsigned track_carry_mask(int at, int w, int carry_bytes)
+{
+    const int left = carry_bytes - (at * 16 + w * 4);
+    return left >= 4 ? 0xffffffffu : (left <= 0 ? 0u : (1u << (8 * left)) - 1u);
+}
+struct TrackStateParams {
+    const TrackEntry* entries;  // [n], device memory; every channel in [0, C) (checked by the host, and again by the kernels)
+    int        n, C;
+    int        row_pieces;      // N / 8
+    int        hist_base;       // frames_seen mod HLEN
+    int        carry_bytes;     // pending samples x their size
+    float*     prev;            // [C][N/2]
+    float*     tail;            // [C][N/2]: the tail the next call reads
+    unsigned char* carry;       // [C][N/2 * 4 bytes]: the pending rows the next call reads
+    float*     hist;            // [C][HLEN][12]
+    float*     latest;          // [C][12]
+    unsigned char* records;     // [n][track_record_pieces x 16], 16-byte aligned
+};
+hipError_t launch_pack_tracks_kernel(const TrackStateParams& p, hipStream_t stream);      // tables -> records (writes every byte of them)
+hipError_t launch_unpack_tracks_kernel(const TrackStateParams& p, hipStream_t stream);    // records -> tables (the header is the host's)
+
 // Re-order the reference's N-entry twiddle table (canonical[i] = (re, im) of e^{-2*pi*i/N} as floats)
 // into the order the FFT passes read it; `out` has room for window_size complex entries.
 void build_pass_twiddles(int window_size, const float* canonical, float* out);
@@ -317,6 +394,7 @@ hipError_t launch_hop_kernel(int window_size, const FrameParams& p, const Epilog
 //   4  fx_push_samples never feeds a block to the one-frame kernels directly (FrameParams::block_mode): every call re-blocks first, as
 //      calls that complete several hops do
 //   5  a call of two hops per channel runs the batch kernels' two-frame form instead of two one-frame launches
+//   6  fx_export_channels / fx_import_channels move a HOST buffer's records through the device scratch two at a time (default: 32 MB a chunk)
 // None changes a result bit (bit 0 makes the call fail, as it must).
 #define FX_HOOK_NO_HANDOVER      1u
 #define FX_HOOK_NO_QUARTER_TURN  2u
@@ -324,6 +402,7 @@ hipError_t launch_hop_kernel(int window_size, const FrameParams& p, const Epilog
 #define FX_HOOK_TAIL_ALWAYS_FUSED 8u
 #define FX_HOOK_NO_BLOCK_FEED    16u
 #define FX_HOOK_NO_TWO_LAUNCHES  32u
+#define FX_HOOK_SMALL_TRACK_CHUNKS 64u
 extern "C" fx_status fx_set_tuning_internal(fx_context* ctx, unsigned test_hooks);
 
 // Launch record, NOT part of the public ABI (tests only): the launches the context's last call made -- fx_push_hops, fx_process_frames,

@@ -168,6 +168,43 @@ fx_status fx_clear_pending_channels(fx_context* ctx, const int* channels, int nu
  * No device use. */
 fx_status fx_get_channel_frames(fx_context* ctx, long long* frames);
 
+/* ---- moving tracks between contexts: export and import a track's whole state ----
+ * The reference's tracks are heap objects (AnalyserTrackController.h) that a host moves by moving a pointer; here a track is a row of
+ * the context's tables, and a RECORD of fx_track_state_bytes() bytes is the way back out: rebalancing shards, draining a GPU, a
+ * context with another num_channels, a restart that keeps every track's analysis state.  A record holds all of it -- flux state,
+ * overlap tail, pending samples, the 48 newest frames' raw values (every ValueHistory and both onset histories), the latest vector,
+ * gain, onset sensitivity / window / type, the track's frame count and the frames since its last onset-window reset -- so a track
+ * imported into any slot of any compatible context goes on, bit for bit, as it would have where it was: raw and smoothed values,
+ * fx_get_channel_frames, fx_get_taps frame_index and fx_onset_event::frame included.  The sample rate is the context's and does not
+ * travel; OSC addresses, sender routes and the channel map belong to the slot and do not travel either.
+ *
+ * A record is canonical: its bytes depend on the track's state alone, not on the source context's frame index, num_channels or the
+ * slot -- export, import anywhere compatible, export again gives the same bytes.  Every part starts on a 16-byte boundary:
+ *   header (80 bytes): uint32 magic, layout version; int32 window_size; uint32 create flags that shape state (order, analyser bits);
+ *     int32 kernel family in force (1, or 2 for the FX_LOW_LATENCY pairs), pending count, pending format, onset window; int64 frames,
+ *     onset_frames; float gain, sensitivity, onset multiplier; int32 onset type; uint32 record bytes; three zero words
+ *   latest vector [12] | ring [48][12]: row k = the raw values of the track's frame frames - 48 + k, zeros before its first frame |
+ *   flux row [N/2] | tail row [N/2] | pending row (N/2 * 4 bytes, zeros beyond the pending samples)
+ *
+ * channels / num_channels follow fx_reset_channels: host memory, num_channels == 0 is a no-op, every entry is checked before
+ * anything is touched and fx_last_error names the bad one.  Record i belongs to channels[i]; records lie back to back.  Duplicates are
+ * allowed on export and refused on import.  The buffer is FX_MEM_HOST or FX_MEM_DEVICE (16-byte aligned), at least num_channels *
+ * fx_track_state_bytes() bytes, and valid on return either way: both calls synchronise the context's stream, as the per-track setters
+ * do, so with a fx_stream_* ring they come after the batches submitted and before every later one, the captured step included.
+ * A device buffer is read and written on the context's stream only (the records' headers too): what the caller queued on
+ * fx_get_stream() to fill it, or made that stream wait for, comes first.  A host buffer's records pass through at most 32 MB of
+ * device scratch, a chunk at a time.
+ * Export changes nothing in the context.
+ *
+ * Import: the context must match each record in window_size, those flags, the kernel family, the pending count and -- where samples
+ * are pending -- their format; otherwise, or for a bad magic or version, FX_ERR_INVALID_ARGUMENT names the record and the field.  All
+ * of this is decided before any change (for a host buffer before any device use).  A valid import creates the per-track table if
+ * there is none, as the first per-track setter does.  Failures are fx_reset_channels': tracks not listed are untouched in every case;
+ * after a failed upload or launch the listed ones may be part old, part new. */
+size_t    fx_track_state_bytes(fx_context* ctx);   /* bytes of one track's record; a multiple of 16; 0 for a null context */
+fx_status fx_export_channels(fx_context* ctx, const int* channels, int num_channels, void* out, size_t out_bytes, int mem_kind);
+fx_status fx_import_channels(fx_context* ctx, const int* channels, int num_channels, const void* in, size_t in_bytes, int mem_kind);
+
 /* Replaces RealTimeAudioDataOverlapper::getNextBuffer (RealTimeAudioAnalysis.h:
  * 205-228) + both run() loops (RealTimeAnalyser.h:141-177, :201-234) for
  * `num_hops` consecutive hops of window_size/2 samples per channel.

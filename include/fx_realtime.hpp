@@ -148,6 +148,20 @@ public:
     // frame index starts at 0 again; settings stay, the other tracks are untouched.
     void resetTrack (int track)                                { const int t = at (track); resetTracks (&t, 1); }
     void resetTracks (const int* tracks, int count)            { check (fx_reset_channels (ctx, tracks, count)); }
+    // A track that leaves for another analyser or arrives from one (fx_export_channels / fx_import_channels): the reference moves an
+    // AnalyserTrackController by its pointer; here its whole state travels as one record of trackStateBytes() per track, and the track
+    // goes on in its new slot exactly as it would have in the old one.  Host memory; record i belongs to tracks[i].
+    std::size_t trackStateBytes() const                        { return fx_track_state_bytes (ctx); }
+    std::vector<unsigned char> exportTracks (const int* tracks, int count)
+    {
+        std::vector<unsigned char> records ((std::size_t) (count > 0 ? count : 0) * trackStateBytes());
+        check (fx_export_channels (ctx, tracks, count, records.data(), records.size(), FX_MEM_HOST));
+        return records;
+    }
+    void importTracks (const int* tracks, int count, const std::vector<unsigned char>& records)
+    {
+        check (fx_import_channels (ctx, tracks, count, records.data(), records.size(), FX_MEM_HOST));
+    }
     std::vector<long long> trackFrames() const                 // frames each track has analysed since it was created or last reset
     {
         std::vector<long long> f ((std::size_t) channels);
@@ -578,6 +592,8 @@ private:
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <exception>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -918,6 +934,22 @@ public:
         callOnWorker ([list] (RealTimeBatchAnalyser& a) { a.resetTracks (list.data(), (int) list.size()); });
     }
 
+    // A track that leaves for another analyser or arrives from one while the engine runs (RealTimeBatchAnalyser::exportTracks /
+    // importTracks): the worker makes the call between two blocks, so the record is the track's state at a block boundary; the caller
+    // waits for the result (an Error is thrown here, on the caller's thread).  The audio thread is not involved.  The lists are copied.
+    std::vector<unsigned char> exportTracks (const int* tracks, int count)
+    {
+        const std::vector<int> list = checkedTracks (tracks, count);
+        std::vector<unsigned char> records;
+        waitOnWorker ([&list, &records] (RealTimeBatchAnalyser& a) { records = a.exportTracks (list.data(), (int) list.size()); });
+        return records;
+    }
+    void importTracks (const int* tracks, int count, const std::vector<unsigned char>& records)
+    {
+        const std::vector<int> list = checkedTracks (tracks, count);
+        waitOnWorker ([&list, &records] (RealTimeBatchAnalyser& a) { a.importTracks (list.data(), (int) list.size(), records); });
+    }
+
     // wait until everything pushed so far has been analysed and published (not for the audio thread)
     void drain()
     {
@@ -982,6 +1014,38 @@ private:
         ready.notify_one();                                                         // notify(), ref AudioDataCollector.h:68-69
     }
 
+    std::vector<int> checkedTracks (const int* tracks, int count) const
+    {
+        if (count < 0 || (count > 0 && tracks == nullptr)) throw Error (FX_ERR_INVALID_ARGUMENT, "bad track list");
+        for (int i = 0; i < count; ++i)
+            if (tracks[i] < 0 || tracks[i] >= analyser.getNumChannels()) throw Error (FX_ERR_INVALID_ARGUMENT, "no such track");
+        return std::vector<int> (tracks, tracks + count);
+    }
+    // callOnWorker for a call whose result the caller needs: returns when the worker has made it, and throws what it threw (whatever
+    // it threw) on the caller's thread.  The command is queued under the lock the worker leaves its loop under, so an engine that
+    // stops meanwhile either still makes the call or refuses it here; on the worker thread itself (a framesAnalysed / onsetDetected
+    // callback) the call is made at once -- that thread is between two blocks already and must not wait for itself.
+    void waitOnWorker (const std::function<void (RealTimeBatchAnalyser&)>& f)
+    {
+        if (std::this_thread::get_id() == worker.get_id()) { f (analyser); return; }
+        struct Reply { std::mutex m; std::condition_variable cv; bool done = false; std::exception_ptr thrown; };
+        auto reply = std::make_shared<Reply>();
+        {
+            std::lock_guard<std::mutex> g (wake);
+            if (! running.load()) throw Error (FX_ERR_INVALID_ARGUMENT, "the engine is not running");
+            commands.push_back ([reply, &f] (RealTimeBatchAnalyser& a)
+            {
+                std::exception_ptr thrown;
+                try { f (a); } catch (...) { thrown = std::current_exception(); }
+                { std::lock_guard<std::mutex> r (reply->m); reply->done = true; reply->thrown = thrown; }
+                reply->cv.notify_all();
+            });
+        }
+        ready.notify_one();
+        std::unique_lock<std::mutex> g (reply->m);
+        reply->cv.wait (g, [&reply] { return reply->done; });
+        if (reply->thrown) std::rethrow_exception (reply->thrown);
+    }
     void fail (const char* what)
     {
         std::lock_guard<std::mutex> g (statLock);
