@@ -109,10 +109,12 @@ __global__ void __launch_bounds__(NT) log_attack_time_kernel(const float* env, i
     __shared__ int s_idx[NT];
     float m = -__builtin_huge_valf();
     bool any = false;
-    for (int k = threadIdx.x; k < n; k += NT) { const float v = env[k]; if (!any || v > m) { m = v; any = true; } }   // findMinMax(...).getEnd(), :615
-    s_max[threadIdx.x] = any ? m : -__builtin_huge_valf();
+    // findMinMax(...).getEnd(), :615: the maximum starts from env[0] and moves on `>` only, so a NaN anywhere but at 0 is skipped -- here too, or one
+    // early in a thread's stride would hide the maxima behind it (as in auto_correlation_kernel below); a NaN at env[0] is thread 0's business
+    for (int k = threadIdx.x; k < n; k += NT) { const float v = env[k]; if (v == v && (!any || v > m)) { m = v; any = true; } }
+    s_max[threadIdx.x] = any ? m : -__builtin_huge_valf();                 // (-inf never moves the maximum)
     __syncthreads();
-    if (threadIdx.x == 0) { float mm = s_max[0]; for (int k = 1; k < NT; k++) if (s_max[k] > mm) mm = s_max[k]; s_max[0] = mm; }
+    if (threadIdx.x == 0) { float mm = env[0]; for (int k = 0; k < NT; k++) if (s_max[k] > mm) mm = s_max[k]; s_max[0] = mm; }      // a NaN at 0 stays: it equals no entry, i = n
     __syncthreads();
     const float max_energy = s_max[0];
     int first = n;                                                         // first index holding the maximum, :616-618
