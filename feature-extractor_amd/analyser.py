@@ -274,7 +274,7 @@ class BatchAnalyser:
     def last_launches(self):
         """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
         (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events, osc_table,
-        osc_bundle)."""
+        osc_bundle, display)."""
         cap = capi.LAUNCH_RECORD_CAP
         buf = (ctypes.c_int * (cap * len(capi.LAUNCH_FIELDS)))()
         n = self._lib.fx_last_launches_internal(self._h, buf, cap)
@@ -328,6 +328,41 @@ class BatchAnalyser:
         out = np.empty(max(int(max_events), 1), capi.ONSET_EVENT_DTYPE)      # (never a null pointer: max_events == 0 is still a drain)
         capi.check(self._lib.fx_get_onset_events(self._h, out.ctypes.data_as(ctypes.c_void_p), int(max_events), ctypes.byref(n), ctypes.byref(dropped)))
         return out[:n.value].copy(), dropped.value
+
+    # ---- audio display levels: every track's scrolling waveform, made on the GPU (include/fx.h, fx_enable_display) ----
+    def enable_display(self, samples_per_block=256, length=1024):
+        """Enable the audio display (AnalyserTrack.h:27-29: setSamplesPerBlock (256), setBufferSize (1024)) or resize it: every track
+        becomes a new component with a ring of `length` (lo, hi) levels, one published per samples_per_block samples; length 0
+        disables it."""
+        capi.check(self._lib.fx_enable_display(self._h, int(samples_per_block), int(length)))
+        self._display_length = int(length)
+
+    def set_display_samples_per_block(self, n):
+        """setSamplesPerBlock: in force from the next sample on; the running block keeps its count."""
+        capi.check(self._lib.fx_set_display_samples_per_block(self._h, int(n)))
+
+    def clear_display(self, channels):
+        """clear() on the listed tracks: levels, running value and count become zero, the ring position stays."""
+        a, ptr = self._track_list(channels)
+        capi.check(self._lib.fx_clear_display_channels(self._h, ptr, int(a.size)))
+
+    def display(self, channels=None, device=False):
+        """The listed tracks' levels (None: all tracks) in drawing order, oldest first: float32 [n][length][2] of (lo, hi), numpy or
+        (device=True) a CUDA torch tensor, after the analysis calls made so far."""
+        if channels is None:
+            n, ptr = self.num_channels, None
+        else:
+            a, ptr = self._track_list(channels)
+            n = int(a.size)
+        length = getattr(self, "_display_length", 0)
+        if device:
+            import torch
+            out = torch.empty((n, length, 2), dtype=torch.float32, device=torch.device("cuda", self.device))
+            self._ordered(out.device, self._lib.fx_get_display, self._h, ptr, n, ctypes.c_void_p(out.data_ptr() if out.numel() else 0), capi.MEM_DEVICE)
+        else:
+            out = np.empty((n, length, 2), np.float32)
+            capi.check(self._lib.fx_get_display(self._h, ptr, n, out.ctypes.data_as(ctypes.c_void_p), capi.MEM_HOST))
+        return out
 
     def last_kernel_ms(self):
         a, b = ctypes.c_float(), ctypes.c_float()

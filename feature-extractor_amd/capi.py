@@ -24,7 +24,8 @@ MAX_UNITS = 24
 LAUNCH_FIELDS = ["kind", "window", "analysers", "T", "direct_state", "block_mode", "num_chunks", "ch_per_wg", "waves_per_ch", "hop_pairs",
                  "ep_T", "out_stride", "ep_form", "reblock"]
 LAUNCH_KINDS = {1: "frame", 2: "frame_tail", 3: "hop", 4: "hop_pair", 5: "pair", 6: "epilogue", 7: "reblock", 8: "osc", 9: "taps",
-                10: "deinterleave", 11: "onset_events", 12: "osc_table", 13: "osc_bundle"}
+                10: "deinterleave", 11: "onset_events", 12: "osc_table", 13: "osc_bundle", 14: "display"}
+MAX_DISPLAY_LENGTH, MAX_DISPLAY_SAMPLES_PER_BLOCK = 4096, 65536
 MAX_TAP_CHANNELS = 64
 OSC_ADDRESS_MAX = 124               # FX_OSC_ADDRESS_MAX
 OSC_SENDER_MAX_TARGETS = 64         # FX_OSC_SENDER_MAX_TARGETS
@@ -100,6 +101,8 @@ def _prototypes():
         ("fx_sync", [vp], st), ("fx_get_stream", [vp, vpp], st), ("fx_last_kernel_ms", [vp, fp, fp], st),
         ("fx_request_taps", [vp, ip, i], st), ("fx_get_taps", [vp, i, fp, fp, fp, fp, fp, fp, llp], st),
         ("fx_enable_onset_events", [vp, i], st), ("fx_get_onset_events", [vp, vp, i, ip, llp], st),
+        ("fx_enable_display", [vp, i, i], st), ("fx_set_display_samples_per_block", [vp, i], st),
+        ("fx_clear_display_channels", [vp, ip, i], st), ("fx_get_display", [vp, ip, i, vp, i], st),
         ("fx_stream_create", [vp, i, i, i, vpp], st), ("fx_stream_destroy", [vp], st), ("fx_stream_acquire", [vp, vpp], st),
         ("fx_stream_submit", [vp], st), ("fx_stream_push", [vp, vp, i], st), ("fx_stream_collect", [vp, vp, vp], st),
         ("fx_stream_submit_samples", [vp, i], st), ("fx_stream_push_samples", [vp, vp, i, i], st),

@@ -365,6 +365,7 @@ fx_status fx_destroy(fx_context* c)
     if (c->tracks_release) c->tracks_release(c);
     if (c->osc_table_release) c->osc_table_release(c);
     if (c->track_state_release) c->track_state_release(c);
+    if (c->display_release) c->display_release(c);
     void* bufs[] = {c->d_tw, c->d_prev, c->d_tail[0], c->d_tail[1], c->d_hist, c->d_latest,
                     c->d_raw, c->d_part, c->d_in, c->d_out_raw, c->d_queue, c->d_carry[0], c->d_carry[1], c->d_hops, c->d_osc, c->d_chan};
     for (void* b : bufs) if (b) (void) hipFree(b);
@@ -385,6 +386,7 @@ fx_status fx_reset_state(fx_context* c)
     if (c->h_err) *c->h_err = 0;
     if (c->taps_release) c->taps_release(c);
     if (c->events_reset) { const fx_status st = c->events_reset(c); if (st != FX_OK) return st; }     // the list emptied, still enabled
+    if (c->display_reset) { const fx_status st = c->display_reset(c, nullptr, c->C, false); if (st != FX_OK) return st; }   // every track a new component
     return zero_state(c);
 }
 

@@ -1,6 +1,6 @@
 // fx_context.h -- the context behind the C ABI (include/fx.h), shared by the shim's host units (fx_capi.cpp, fx_plan.cpp, fx_stream.cpp,
 // fx_comm.cpp) and the units that attach through its hooks (fx_taps.hip, fx_interleave.hip, fx_events.hip, fx_tracks.hip,
-// fx_osc_table.hip, fx_osc_bundle.hip, fx_track_state.hip).  Internal.
+// fx_osc_table.hip, fx_osc_bundle.hip, fx_track_state.hip, fx_display.hip).  Internal.
 #ifndef FX_CONTEXT_H
 #define FX_CONTEXT_H
 
@@ -61,6 +61,7 @@ struct fx_interleave;   // fx_interleave.hip
 struct fx_events;       // fx_events.hip
 struct fx_tracks;       // fx_tracks.hip
 struct fx_track_state;  // fx_track_state.hip
+struct fx_display;      // fx_display.hip
 // The OSC address table in force (fx_osc_table.hip makes and frees it; fx_osc_bundle.hip reads it): one device allocation, [C][128]
 // bytes of rows, then int len[C]; the messages' lengths on the host.
 struct fx_osc_table {
@@ -68,7 +69,7 @@ struct fx_osc_table {
     std::vector<int> message_bytes;     // [C]
     int              longest = 0;       // the smallest legal stride
 };
-// Where an analysis call reads its FIRST frame, as the kernels read it: `in` (device) holds rows of in_row_bytes per channel; hop_mode 1:
+// Where an analysis call reads its frames (the taps take the FIRST, the audio display every hop), as the kernels read them: `in` (device) holds rows of in_row_bytes per channel; hop_mode 1:
 // hops of N/2 samples, the window is [the channel's tail | hop 0 x gain]; 0: whole frames, frame 0 as given.  carry != null: the hop is
 // the first N/2 samples of [pending | block] (fx_blocks.hip.h, BlockStream), the pending row of the channel at carry + c * carry_row_bytes.
 struct fx_tap_source {
@@ -185,6 +186,15 @@ struct fx_context {
     // until the first fx_export_channels / fx_import_channels, which installs the hook fx_destroy calls.
     fx_track_state* track_state = nullptr;
     void (*track_state_release)(fx_context*) = nullptr;
+
+    // audio display levels (fx_display.hip): null until fx_enable_display, which installs the hooks (and removes them again when it
+    // disables the display).  display_launch: once the analysis launches of a call of T frames per channel are enqueued, `src` where
+    // they read its samples.  display_reset: the listed tracks (null: all C) become new components (fx_reset_state, fx_reset_channels),
+    // or are cleared with their ring position kept (keep_next).
+    fx_display* display = nullptr;
+    fx_status (*display_launch)(fx_context*, const fx_tap_source& src, int T) = nullptr;
+    fx_status (*display_reset)(fx_context*, const int* channels, int n, bool keep_next) = nullptr;
+    void      (*display_release)(fx_context*) = nullptr;
 };
 
 // The per-track rows (fx_capi.cpp), for the units that change them.  fx_channel_rows: what every track runs with now -- the table's rows,

@@ -419,6 +419,9 @@ constexpr int FX_LAUNCH_OSC_TABLE = 12;
 // fx_get_osc_bundles / fx_get_osc_bundles_addressed (fx_osc_bundle.hip): one launch of fx_osc_bundle_kernel; it starts a new record too.
 // T = the tracks per bundle.
 constexpr int FX_LAUNCH_OSC_BUNDLE = 13;
+// The audio display's step (fx_display.hip), the last entry of an analysis call on a context with the display enabled: ONE launch of
+// fx_display_kernel per call, T = the frames per channel the call analysed.
+constexpr int FX_LAUNCH_DISPLAY = 14;
 struct fx_launch_record {
     int kind;               // FX_LAUNCH_*
     int window, analysers;  // window size, analysers mask (bit 0 spectral, bit 1 harmonic)

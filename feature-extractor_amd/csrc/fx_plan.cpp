@@ -365,12 +365,10 @@ fx_status fx_run(fx_context* c, const void* in, int T, int sample_format, int in
     if (blocks && (T < 1 || T > 4096 || !hop_mode || in_kind != FX_MEM_DEVICE)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "a block feed is 1 .. 4096 hops per channel from device memory");
     Plan plan;
     if ((st = plan_call(c, d_in, T, sample_format, hop_mode, d_or, d_os, blocks, nullptr, c->d_part, c->d_raw, ROUTE_AUTO, &plan)) != FX_OK) return st;
+    const fx_tap_source src = {d_in, sample_format, hop_mode, blocks ? blocks->in_row_bytes : (long long) (T * per_frame * esz),
+                               blocks ? blocks->carry_in : nullptr, blocks ? blocks->carry_bytes : 0, blocks ? blocks->carry_row_bytes : 0};
     // armed taps (fx_request_taps): their launch reads this call's first frame before any launch of the call changes the context's state
-    if (taps && c->taps_armed && c->taps_launch) {
-        const fx_tap_source src = {d_in, sample_format, hop_mode, blocks ? blocks->in_row_bytes : (long long) (T * per_frame * esz),
-                                   blocks ? blocks->carry_in : nullptr, blocks ? blocks->carry_bytes : 0, blocks ? blocks->carry_row_bytes : 0};
-        if ((st = c->taps_launch(c, src)) != FX_OK) return st;
-    }
+    if (taps && c->taps_armed && c->taps_launch && (st = c->taps_launch(c, src)) != FX_OK) return st;
 
     // timed: e0 before the first launch, e1 after the last launch that analyses frames, e2 after the last launch (frame-kernel time is
     // only split out of calls of one part)
@@ -400,6 +398,9 @@ fx_status fx_run(fx_context* c, const void* in, int T, int sample_format, int in
     c->ev_valid = last_valid;
     // every frame's raw vector is on its way to d_or: the list's one launch (a failure leaves the stream to fx_reset_state)
     if (list_events && (st = c->events_launch(c, d_or, T, c->frames_seen - T)) != FX_OK) return st;
+    // the audio display (fx_enable_display) reads the call's samples where the launches above read them: its one launch (a block
+    // feed's launches wrote the OTHER carry buffer; the pending rows they read stand until the next call)
+    if (events && c->display_launch && (st = c->display_launch(c, src, T)) != FX_OK) return st;
 
     if (out_kind == FX_MEM_HOST) {
         if (out_raw) HIP_TRY(hipMemcpyAsync(out_raw, c->d_out_raw, raw_bytes, hipMemcpyDeviceToHost, c->stream));

@@ -176,7 +176,9 @@ fx_status fx_reset_channels(fx_context* c, const int* channels, int num_channels
         r.onset_reset_frame = c->frames_seen;
     }
     if ((st = fx_upload_channel_rows(c, rows, sensitivity)) != FX_OK) return st;
-    return clear_rows(c, channels, num_channels, fxk::FX_CLEAR_PREV | fxk::FX_CLEAR_TAIL | fxk::FX_CLEAR_CARRY | fxk::FX_CLEAR_LATEST);
+    if ((st = clear_rows(c, channels, num_channels, fxk::FX_CLEAR_PREV | fxk::FX_CLEAR_TAIL | fxk::FX_CLEAR_CARRY | fxk::FX_CLEAR_LATEST)) != FX_OK) return st;
+    // the audio display's own launch (fx_display.hip): the listed tracks' components are new ones too
+    return c->display_reset ? c->display_reset(c, channels, num_channels, false) : FX_OK;
 }
 
 fx_status fx_clear_pending_channels(fx_context* c, const int* channels, int num_channels)

@@ -371,6 +371,49 @@ fx_status fx_enable_onset_events(fx_context* ctx, int capacity);
  * cap < 0, out == NULL with cap > 0, a context on which the list is not enabled. */
 fx_status fx_get_onset_events(fx_context* ctx, fx_onset_event* out, int cap, int* count, long long* dropped);
 
+/* ---- audio display levels: every track's scrolling waveform, made on the GPU ----
+ * AnalyserTrackController.h:74-78 binds setBufferToDrawUpdatedCallback on the harmonic collector; AudioDataCollector::getAnalysisBuffer
+ * (AudioDataCollector.h:88-91) calls it with every gained hop it hands out, and AnalyserTrack::updateBufferToPush (AnalyserTrack.h:148-157)
+ * pushes that hop into an AudioVisualiserComponent set up with setSamplesPerBlock (256) and setBufferSize (1024) (AnalyserTrack.h:27-29).
+ * Per track the component keeps a ring levels[L] of (lo, hi) pairs, a running pair `value`, and the ints `sub` and `next`, all zero in
+ * a new component, and runs for every sample x of every hop, in order:
+ *     if (--sub <= 0) { next %= L; levels[next++] = value; sub = samplesPerBlock; value = (x, x); }
+ *     else { lo' = lo < x ? lo : x;  t = x < hi ? hi : x;  hi' = lo' < t ? t : lo';  value = (lo', hi'); }
+ * Here a context on which the display is enabled keeps that state per track in device memory, bit for bit:
+ *   - a block is published one sample late, when the first sample of the next block arrives; the first entry published by a new or
+ *     cleared component is (0, 0); equal values take the newer sample (so the sign of a zero is the latest one's); a NaN sample makes
+ *     both ends NaN, and the next sample replaces both.
+ *   - the display receives exactly the hops a call analyses, as the analysers read them: fx_push_hops, fx_push_samples and
+ *     fx_push_interleaved show each analysed hop's N/2 samples, widened as the load stage widens them and times the gain in force
+ *     for that track (the float the `window` tap shows in its second half); fx_process_frames shows the second half of each frame
+ *     as given, without gain.  Pending samples are not shown until their hop completes.  The fx_stream_* ring does not feed the
+ *     display, as it does not serve taps or events.
+ *   - it is made by one extra launch on the context's stream per analysis call; the results an enabled context returns are the bits
+ *     it returns with the display disabled, and a context that never enabled it makes exactly the launches it made before.
+ *   - fx_reset_state makes every track a new component, fx_reset_channels the listed tracks (sub and next are per track, so tracks
+ *     may stand at different phases); fx_clear_pending* does not touch the display.  The display belongs to the slot:
+ *     fx_export_channels / fx_import_channels records do not carry it. */
+/* buffer_size in [1, 4096]: enable the display with rings of buffer_size levels, or resize it; every track becomes a new component
+ * publishing every samples_per_block (in [1, 65536]) samples.  buffer_size 0: disable it and free its memory.  Memory:
+ * num_channels x buffer_size x 8 bytes, and two 16-byte state records per track (a call reads one and writes the other).  A failed
+ * allocation is FX_ERR_OUT_OF_MEMORY and leaves the old display in force.  Synchronises the context's stream.  A null context or a
+ * value out of range is FX_ERR_INVALID_ARGUMENT, before any device use. */
+fx_status fx_enable_display(fx_context* ctx, int samples_per_block, int buffer_size);
+/* setSamplesPerBlock (AnalyserTrackController.h:154-158): only the int is replaced -- the running block keeps its `sub` -- and the
+ * new value takes effect with the next sample in stream order.  FX_ERR_INVALID_ARGUMENT, before any device use: a null context, a
+ * value outside [1, 65536], a context without a display. */
+fx_status fx_set_display_samples_per_block(fx_context* ctx, int samples_per_block);
+/* clear() on the listed tracks (clearAudioDisplayData, AnalyserTrackController.h:105,114): levels, value and sub become zero, next
+ * stays.  channels / num_channels follow fx_reset_channels.  FX_ERR_INVALID_ARGUMENT, before any device use: a null context, a bad
+ * list (fx_last_error names the entry), a context without a display. */
+fx_status fx_clear_display_channels(fx_context* ctx, const int* channels, int num_channels);
+/* The listed tracks' rings in drawing order, oldest first -- levels[(next + k) % L] for k = 0 .. L-1, as the component draws them
+ * -- to levels [num_channels][L][2] floats, after the analysis calls made so far.  channels == NULL with num_channels == the
+ * context's channel count means all tracks.  FX_MEM_HOST returns when the bytes are there; FX_MEM_DEVICE (4-byte aligned) is
+ * asynchronous on the context's stream.  FX_ERR_INVALID_ARGUMENT, before any device use: a null context or buffer, an unknown
+ * memory kind, a bad list (fx_last_error names the entry), a context without a display. */
+fx_status fx_get_display(fx_context* ctx, const int* channels, int num_channels, float* levels, int mem_kind);
+
 /* ---- streaming ingest: replaces AudioDataCollector's ring + busy-wait reader ----
  * (AudioDataCollector.h:24,36-94: audio thread writes a 4096-sample ring, the analysis thread spins
  * until a hop is available.)  Here the producer owns a ring of `slots` PINNED host batches, each

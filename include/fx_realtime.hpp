@@ -258,6 +258,26 @@ public:
         return events;
     }
 
+    // The scrolling audio display of every track (fx_enable_display / fx_get_display): the AudioVisualiserComponent the reference
+    // feeds with every gained hop (AnalyserTrackController.h:74-78, AnalyserTrack.h:27-29,148-157), kept on the GPU.  Once enabled,
+    // every analysis call folds its hops into the tracks' (lo, hi) levels; getDisplayLevels returns the listed tracks' rings (an
+    // empty list: all tracks) in drawing order, oldest first, [tracks][bufferSize][2].
+    void enableDisplay (int samplesPerBlock = 256, int bufferSize = 1024)
+    {
+        check (fx_enable_display (ctx, samplesPerBlock, bufferSize));
+        displayLength = bufferSize;
+    }
+    void setSamplesPerBlock (int samplesPerBlock)               { check (fx_set_display_samples_per_block (ctx, samplesPerBlock)); }   // ref AnalyserTrackController.h:154-158
+    void clearDisplay (const std::vector<int>& tracks)          { check (fx_clear_display_channels (ctx, tracks.data(), (int) tracks.size())); }   // ref :105,114
+    std::vector<float> getDisplayLevels (const std::vector<int>& tracks = {})
+    {
+        const int n = tracks.empty() ? channels : (int) tracks.size();
+        std::vector<float> levels ((std::size_t) n * (std::size_t) displayLength * 2 + 1);      // (never a null pointer)
+        check (fx_get_display (ctx, tracks.empty() ? nullptr : tracks.data(), n, levels.data(), FX_MEM_HOST));
+        levels.resize (levels.size() - 1);
+        return levels;
+    }
+
     // hops [channels][numHops][window/2] host floats -> raw / smoothed [channels][numHops][12]
     void pushHops (const float* hops, int numHops, float* raw, float* smoothed)
     {
@@ -314,6 +334,7 @@ private:
     int channels, window;
     std::vector<int> channelMap;             // [track]: what fx_set_channel_map was last given (the identity by default)
     int highestSource = channels - 1;
+    int displayLength = 0;                   // levels per track of the audio display (0: not enabled)
     std::vector<float> latest;
 };
 
