@@ -274,7 +274,7 @@ class BatchAnalyser:
     def last_launches(self):
         """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
         (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events, osc_table,
-        osc_bundle, display)."""
+        osc_bundle, display, sources)."""
         cap = capi.LAUNCH_RECORD_CAP
         buf = (ctypes.c_int * (cap * len(capi.LAUNCH_FIELDS)))()
         n = self._lib.fx_last_launches_internal(self._h, buf, cap)
@@ -518,6 +518,130 @@ class BatchAnalyser:
         n, K = interleaved_dims(tuple(keep.shape), count * (3 if fmt == capi.SAMPLE_S24 else 1), fmt, num_source_channels)
         frames = (self.pending_samples() + n) // (self.window_size // 2)
         return self._analyse("fx_push_interleaved", d, (n, K), frames, want_raw, want_smoothed, block=True)
+
+    # ---- file sources: tracks play device-resident clips (include/fx.h, fx_create_clips .. fx_push_sources; AudioFilePlayer.h:41-67) ----
+    def create_clips(self, samples, lengths=None, sample_format=None, borrow=False):
+        """A bank of clips in device memory -> the first clip's id (the clips get consecutive ids).  `samples`: the clips back to back
+        as ONE numpy array (host) or torch CUDA tensor (from a 4-byte boundary) with `lengths` in samples, or a list of numpy arrays,
+        one clip each.  Formats as push_samples.  borrow=True (device tensors only): the bank refers to the tensor's memory, which
+        the analyser keeps alive until destroy_clips and the caller must not change."""
+        if isinstance(samples, (list, tuple)):
+            if lengths is not None:
+                raise ValueError("a list of clips carries its own lengths")
+            if not samples:
+                raise ValueError("a bank holds at least one clip")
+            tagged = all(isinstance(p, PackedS24) for p in samples)
+            per = 3 if tagged or sample_format == "s24" else 1
+            parts = [np.ascontiguousarray(p).ravel() for p in samples]
+            lengths = [p.size // per for p in parts]
+            samples = np.concatenate(parts)
+            if tagged:
+                samples = samples.view(PackedS24)
+        if lengths is None:
+            raise ValueError("give the clips' lengths (in samples)")
+        ptr, fmt, mem, count, keep, device = _describe_input(samples, sample_format, self.device, 4)
+        ls = np.ascontiguousarray(np.asarray(lengths).ravel().astype(np.int64))
+        if int(ls.sum()) != count:
+            raise ValueError("the clips' lengths add up to %d samples, the bank holds %d" % (int(ls.sum()), count))
+        if borrow and mem != capi.MEM_DEVICE:
+            raise ValueError("only a device tensor can be borrowed")
+        first = ctypes.c_int(-1)
+        args = (self._h, ptr, ls.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(ls.size), fmt, mem, capi.CLIP_BORROW if borrow else 0, ctypes.byref(first))
+        if mem == capi.MEM_DEVICE:
+            self._ordered(device, self._lib.fx_create_clips, *args)
+            if not borrow:
+                self.sync()                      # the copy has read the tensor: the caller may drop it
+        else:
+            capi.check(self._lib.fx_create_clips(*args))
+        if borrow:
+            if not hasattr(self, "_borrowed"):
+                self._borrowed = {}
+            self._borrowed[first.value] = keep
+        return first.value
+
+    def destroy_clips(self, first_id):
+        """Frees the bank whose first clip is `first_id`; refused while a track has one of its clips loaded."""
+        capi.check(self._lib.fx_destroy_clips(self._h, int(first_id)))
+        getattr(self, "_borrowed", {}).pop(int(first_id), None)
+
+    def _per_entry(self, values, size, names=None):
+        """one int32 per list entry from a scalar or a sequence (names: strings that stand for values)"""
+        vals = list(values) if isinstance(values, (list, tuple, np.ndarray)) else [values]
+        vals = [names[x] if names and isinstance(x, str) and x in names else x for x in vals]
+        if not all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in vals):
+            raise ValueError("expected integers%s, not %r" % (" or one of %s" % ", ".join(sorted(names)) if names else "", values))
+        v = np.asarray(vals, dtype=np.int32).ravel()
+        if v.size == 1 and size != 1:
+            v = np.full(size, v[0], np.int32)
+        if v.size != size:
+            raise ValueError("one value per listed track (%d), not %d" % (size, v.size))
+        v = np.ascontiguousarray(v)
+        return v, v.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+    def load_clips(self, channels, clip_ids, loop=None):
+        """loadFileIntoTransport for the listed tracks: track channels[i] gets clip clip_ids[i] (-1 or None: no file; one id for all is
+        fine), looping unless loop (one flag or one per entry) says otherwise.  The tracks stop at position 0 and their pending samples
+        become zeros."""
+        a, ptr = self._track_list(channels)
+        ids = list(clip_ids) if isinstance(clip_ids, (list, tuple, np.ndarray)) else [clip_ids]
+        v, vp = self._per_entry([-1 if x is None else x for x in ids], int(a.size))
+        l, lp = None, None
+        if loop is not None:
+            flags = list(loop) if isinstance(loop, (list, tuple, np.ndarray)) else [loop]
+            l, lp = self._per_entry([int(bool(x)) for x in flags], int(a.size))
+        capi.check(self._lib.fx_set_channel_clips(self._h, ptr, int(a.size), vp, lp))
+
+    def set_sources(self, channels, sources):
+        """The listed tracks listen to the live block ("input", capi.SOURCE_INPUT) or to their clip ("file", capi.SOURCE_FILE); their
+        pending samples become zeros either way, and a track that goes to the input stops its player."""
+        a, ptr = self._track_list(channels)
+        v, vp = self._per_entry(sources, int(a.size), {"input": capi.SOURCE_INPUT, "file": capi.SOURCE_FILE})
+        capi.check(self._lib.fx_set_channel_sources(self._h, ptr, int(a.size), vp))
+
+    def transport(self, channels, command):
+        """"play", "pause", "stop" or "restart" (capi.PLAY ...) for the listed tracks, as the reference's buttons: play, pause and stop
+        zero the tracks' pending samples, restart keeps them and keeps the state."""
+        a, ptr = self._track_list(channels)
+        if isinstance(command, str):
+            if command not in capi.TRANSPORT_COMMANDS:
+                raise ValueError("a transport command is one of %s" % ", ".join(sorted(capi.TRANSPORT_COMMANDS)))
+            command = capi.TRANSPORT_COMMANDS[command]
+        capi.check(self._lib.fx_transport(self._h, ptr, int(a.size), int(command)))
+
+    def transport_state(self):
+        """The table: dict of source, state (int32 [C]; capi.SOURCE_*, capi.TRANSPORT_*), position, laps (int64 [C])."""
+        C = self.num_channels
+        out = {"source": np.empty(C, np.int32), "state": np.empty(C, np.int32), "position": np.empty(C, np.int64), "laps": np.empty(C, np.int64)}
+        ip, llp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)
+        capi.check(self._lib.fx_get_transport(self._h, out["source"].ctypes.data_as(ip), out["state"].ctypes.data_as(ip),
+                                              out["position"].ctypes.data_as(llp), out["laps"].ctypes.data_as(llp)))
+        return out
+
+    def push_sources(self, live=None, num_samples=None, want_raw=True, want_smoothed=True, sample_format=None, device=False):
+        """One tick: every track gets n samples -- row c of `live` ([C][n] as push_samples takes it) where the track's source is the
+        input, its clip's next n samples where it plays a file, silence otherwise -- and they are analysed as push_samples analyses
+        them -> (raw, smoothed).  live=None (allowed while no track listens to the input) needs num_samples and sample_format (the
+        clips' format, "f32" by default); device=True then returns torch tensors."""
+        if live is not None:
+            d = _describe_input(live, sample_format, self.device, 4)
+            n, rest = divmod(d[3], self.num_channels)
+            if rest:
+                raise ValueError("input size is not a multiple of the channel count")
+            if num_samples is not None and int(num_samples) != n:
+                raise ValueError("the live block holds %d samples per track, not %d" % (n, int(num_samples)))
+        else:
+            if num_samples is None:
+                raise ValueError("a tick without a live block needs num_samples")
+            name = "f32" if sample_format is None else sample_format
+            if name not in _FORMAT_NAMES:
+                raise ValueError("sample_format must be one of %s" % ", ".join(sorted(_FORMAT_NAMES)))
+            n, where = int(num_samples), None
+            if device:
+                import torch
+                where = torch.device("cuda", self.device)
+            d = (None, _FORMAT_NAMES[name], capi.MEM_DEVICE if device else capi.MEM_HOST, 0, None, where)
+        frames = (self.pending_samples() + n) // (self.window_size // 2) if n > 0 else 0
+        return self._analyse("fx_push_sources", d, (n,), frames, want_raw, want_smoothed, block=True)
 
     def get_features(self, out=None):
         """Latest AudioFeatures::getValue of every slot, [C][12]: a host array, or -- with `out`, a contiguous

@@ -1,6 +1,6 @@
 // fx_context.h -- the context behind the C ABI (include/fx.h), shared by the shim's host units (fx_capi.cpp, fx_plan.cpp, fx_stream.cpp,
 // fx_comm.cpp) and the units that attach through its hooks (fx_taps.hip, fx_interleave.hip, fx_events.hip, fx_tracks.hip,
-// fx_osc_table.hip, fx_osc_bundle.hip, fx_track_state.hip, fx_display.hip).  Internal.
+// fx_osc_table.hip, fx_osc_bundle.hip, fx_track_state.hip, fx_display.hip, fx_clips.hip).  Internal.
 #ifndef FX_CONTEXT_H
 #define FX_CONTEXT_H
 
@@ -62,6 +62,7 @@ struct fx_events;       // fx_events.hip
 struct fx_tracks;       // fx_tracks.hip
 struct fx_track_state;  // fx_track_state.hip
 struct fx_display;      // fx_display.hip
+struct fx_clips;        // fx_clips.hip
 // The OSC address table in force (fx_osc_table.hip makes and frees it; fx_osc_bundle.hip reads it): one device allocation, [C][128]
 // bytes of rows, then int len[C]; the messages' lengths on the host.
 struct fx_osc_table {
@@ -195,6 +196,11 @@ struct fx_context {
     fx_status (*display_launch)(fx_context*, const fx_tap_source& src, int T) = nullptr;
     fx_status (*display_reset)(fx_context*, const int* channels, int n, bool keep_next) = nullptr;
     void      (*display_release)(fx_context*) = nullptr;
+
+    // file sources (fx_clips.hip): the clip banks, the per-track transport tables and the staging of fx_push_sources; null until the
+    // first call of that unit, which installs the hook fx_destroy calls.  The player's state, not the analysers': no reset touches it.
+    fx_clips* clips = nullptr;
+    void (*clips_release)(fx_context*) = nullptr;
 };
 
 // The per-track rows (fx_capi.cpp), for the units that change them.  fx_channel_rows: what every track runs with now -- the table's rows,

@@ -422,6 +422,9 @@ constexpr int FX_LAUNCH_OSC_BUNDLE = 13;
 // The audio display's step (fx_display.hip), the last entry of an analysis call on a context with the display enabled: ONE launch of
 // fx_display_kernel per call, T = the frames per channel the call analysed.
 constexpr int FX_LAUNCH_DISPLAY = 14;
+// fx_push_sources (fx_clips.hip): one launch of fx_clip_gather_kernel, the FIRST entry of the call's record; T = the samples per track
+// the call forms.  The entries after it are those of fx_push_samples on the planar block it made.
+constexpr int FX_LAUNCH_SOURCES = 15;
 struct fx_launch_record {
     int kind;               // FX_LAUNCH_*
     int window, analysers;  // window size, analysers mask (bit 0 spectral, bit 1 harmonic)

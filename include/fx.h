@@ -129,7 +129,8 @@ fx_status fx_set_gain(fx_context* ctx, float gain);
  * A bad entry fails the whole call with FX_ERR_INVALID_ARGUMENT (fx_last_error names the track) and changes nothing; a failed
  * upload reports FX_ERR_HIP and leaves the old settings in force.  They synchronise the context's stream.
  * Not per track: the NUMBER of pending samples (tracks would hold different numbers of them -- ragged blocks), the sample rate, the
- * window size and the analysers' order; those stay one per context. */
+ * window size and the analysers' order; those stay one per context.  (Files of different lengths share a context all the same:
+ * every track gets n samples per tick, and a clip that has ended renders silence -- file sources, fx_push_sources below.) */
 /* AudioDataCollector::setGain per track (AnalyserTrackController.h:126-130).  gain [num_channels]; any float, as fx_set_gain. */
 fx_status fx_set_channel_gains(fx_context* ctx, const float* gain);
 /* setOnsetDetectionSensitivity / setOnsetWindowLength / setOnsetDetectionType per track (AnalyserTrackController.h:132-134).
@@ -267,6 +268,86 @@ int fx_pending_samples(fx_context* ctx);
 /* AudioDataCollector::clearBuffer (AudioDataCollector.h:122; the transport buttons, AnalyserTrackController.h:135-137,167-171):
  * the pending samples become zeros; their count, like the ring's indices, stays. */
 fx_status fx_clear_pending(fx_context* ctx);
+
+/* ---- file sources: tracks play device-resident clips, transport on the GPU ----
+ * In the reference every track listens either to the audio device or to its own AudioFilePlayer, a looping file behind play / pause /
+ * stop / restart buttons (AudioFilePlayer.h:41-67, AnalyserTrackController.h:92-138, AudioFileTransportComponent.h:133-179).  Here a
+ * file is a CLIP in device memory, a track's player is a row of a per-track table in device memory, and one call per tick,
+ * fx_push_sources, gives every track its next n samples -- from the caller's live block or from the track's clip -- and analyses
+ * them as fx_push_samples would.  So thousands of tracks play thousands of files of different lengths in one context, and no file
+ * sample crosses the host link after its bank was made.
+ *
+ * CLIPS.  A clip is L >= 1 samples of one FX_SAMPLE_* format in device memory, at the context's sample rate.  Clips are made in
+ * banks, one allocation and one copy per bank: `samples` holds num_clips (>= 1) clips back to back, lengths[k] samples each, in
+ * FX_MEM_HOST or FX_MEM_DEVICE memory (device memory from a 4-byte boundary); the clips get the ids *first_id, *first_id + 1, ...
+ * With FX_CLIP_BORROW (FX_MEM_DEVICE only) the bank is not copied: it refers to the caller's memory, which must stay valid and
+ * unchanged until fx_destroy_clips.  Otherwise the copy is made on the context's stream: a host buffer may be reused on return, a
+ * device buffer once the stream has reached the copy (fx_sync).  fx_destroy_clips takes the first id of a bank; it is refused
+ * (FX_ERR_INVALID_ARGUMENT, nothing changes) while any track has one of the bank's clips loaded.  fx_destroy releases every bank.
+ *
+ * THE TABLE, one row per track, made by the first call of this section (a context on which none was made runs exactly the launches
+ * it ran before):
+ *   source    FX_SOURCE_INPUT (default) or FX_SOURCE_FILE
+ *   state     FX_TRANSPORT_NO_FILE, _PLAYING, _PAUSED, _STOPPED (the reference's enum, in its order) and our own _FINISHED
+ *   loop      1: the reference's setLooping(true) (AudioFilePlayer.h:53); 0: one-shot
+ *   clip      the loaded clip's address and length L;  position (int64, samples);  laps (int64, completed passes of a looping clip)
+ *
+ * A TICK.  fx_push_sources forms num_samples samples for every track c:
+ *   source INPUT:                row c of live_block, [num_channels][num_samples] as fx_push_samples takes it (FX_MEM_DEVICE: 4-byte
+ *                                aligned).  live_block == NULL is allowed only while no track's source is INPUT.
+ *   FILE, PLAYING, looping:      out[i] = clip[(position + i) mod L];  then laps += (position + n) div L, position = (position + n) mod L
+ *   FILE, PLAYING, one-shot:     out[i] = clip[position + i] while position + i < L, zero samples after;  then position =
+ *                                min(position + n, L), and the state becomes FINISHED if the old position + n >= L
+ *   FILE in any other state:     n zero samples (all bytes zero in every format), as a stopped AudioTransportSource renders silence
+ * and hands that planar block to the path of fx_push_samples: every result, the pending samples and the launch sequence after the
+ * first launch (the gather) are those of fx_push_samples on the same block, bit for bit -- taps, onset events and the display
+ * included.  The gain is the collector's: the load stage applies it to file audio as to live audio (AudioDataCollector.h:88).
+ * fx_push_samples' rules and refusals hold unchanged, and all refusals come before any launch: a refused call changes nothing.
+ * Every FILE track's loaded clip must have the call's sample_format, whatever its state (FX_ERR_INVALID_ARGUMENT names the track).
+ * mem_kind covers live_block and the results.  Clip bytes and the table are read on the context's stream only.
+ * fx_push_samples and fx_push_interleaved do not consult the table and advance no position.
+ *
+ * COMMANDS take a list of tracks under fx_reset_channels' rules: host memory, duplicates allowed (for the two setters the last
+ * entry of a track wins), num_channels == 0 is a no-op, every entry -- track, clip id, source, command -- is checked before
+ * anything changes and before any device use (FX_ERR_INVALID_ARGUMENT, fx_last_error names the entry); they synchronise the
+ * context's stream and take effect in stream order.
+ *   fx_set_channel_clips    the file-dropped callback (AnalyserTrackController.h:109-124): track channels[i] loads clip clip_ids[i]
+ *                           (-1: no file), loop[i] != 0 looping (loop == NULL: all looping).  The state becomes STOPPED (NO_FILE for
+ *                           -1), position and laps 0, and the tracks' pending samples become zeros.  The source is not changed.
+ *   fx_set_channel_sources  (:92-107) types[i] is FX_SOURCE_INPUT or FX_SOURCE_FILE.  Going to INPUT stops the player (STOPPED if it
+ *                           has a clip, position 0); going to FILE keeps the player's state.  Either way the tracks' pending samples
+ *                           become zeros, even when the type does not change (toggleCollectInput, AudioDataCollector.h:119).
+ *   fx_transport            FX_PLAY     STOPPED or PAUSED -> PLAYING; FINISHED -> position 0, PLAYING; PLAYING stays.  A listed
+ *                                       track without a clip refuses the whole call.
+ *                           FX_PAUSE    PLAYING -> PAUSED; other states unchanged
+ *                           FX_STOP     any state with a clip -> STOPPED, position 0
+ *                           FX_RESTART  position 0; FINISHED -> STOPPED, otherwise the state is kept
+ *                           PLAY, PAUSE and STOP zero the tracks' pending samples (clearAnalysisBuffers, :135-137); RESTART does not
+ *                           (:138).  RESTART keeping the state is the engine's behaviour (AudioFilePlayer.h:65), not the GUI's label
+ *                           (AudioFileTransportComponent.h:165 shows "playing" after a restart while paused).  FINISHED is known on
+ *                           the device only: one launch over the list applies the command there.
+ *   fx_get_transport        the whole table, [num_channels] each in host memory; any pointer may be NULL.  Synchronises.
+ * None of these calls touches the display (pair them with fx_clear_display_channels where the reference's GUI does).
+ * fx_reset_state and fx_reset_channels leave the table alone: it is the player's state, not the analysers'.  Records of
+ * fx_export_channels do not carry it: like the display it belongs to the slot.
+ *
+ * Deliberate differences from the reference.  JUCE's AudioTransportSource is not part of the reference tree: its fade on stop, its
+ * read-ahead buffer and its sample-rate correction are not reproduced (clips are at the context's rate).  Each track hears its own
+ * player only: in the reference every player renders into the sound card's shared output buffers, so tracks playing at once hear
+ * each other -- a property of the one device, not carried over.  One-shot playback and FINISHED are ours. */
+enum { FX_SOURCE_INPUT = 0, FX_SOURCE_FILE = 1 };
+enum { FX_TRANSPORT_NO_FILE = 0, FX_TRANSPORT_PLAYING = 1, FX_TRANSPORT_PAUSED = 2, FX_TRANSPORT_STOPPED = 3, FX_TRANSPORT_FINISHED = 4 };
+enum { FX_PLAY = 0, FX_PAUSE = 1, FX_STOP = 2, FX_RESTART = 3 };
+enum { FX_CLIP_BORROW = 1 };
+fx_status fx_create_clips(fx_context* ctx, const void* samples, const long long* lengths, int num_clips, int sample_format,
+                          int mem_kind, unsigned flags, int* first_id);
+fx_status fx_destroy_clips(fx_context* ctx, int first_id);
+fx_status fx_set_channel_clips(fx_context* ctx, const int* channels, int num_channels, const int* clip_ids, const int* loop);
+fx_status fx_set_channel_sources(fx_context* ctx, const int* channels, int num_channels, const int* types);
+fx_status fx_transport(fx_context* ctx, const int* channels, int num_channels, int command);
+fx_status fx_get_transport(fx_context* ctx, int* source, int* state, long long* position, long long* laps);
+fx_status fx_push_sources(fx_context* ctx, const void* live_block, int num_samples, int sample_format, int mem_kind,
+                          float* out_raw, float* out_smoothed, int* frames_out);
 
 /* Same analysis on already assembled windows (the `audioWindow` each run()
  * loop sees, RealTimeAnalyser.h:147,206): frames [num_channels][num_frames]

@@ -406,6 +406,22 @@ public:
         if (frames > 0) reportOnsets();
         return frames;
     }
+    // one tick of a context whose tracks listen to the device or to their AudioFilePlayer (below; fx_push_sources): `liveBlock` is the
+    // block pushBlock takes -- read by the tracks whose source is the input, and may be null while there is none -- and every track
+    // that plays a file gets its clip's next numberOfSamples samples on the GPU
+    int pushSources (const void* liveBlock, int numberOfSamples, int sampleFormat = FX_SAMPLE_F32)
+    {
+        const std::size_t most = (std::size_t) ((fx_pending_samples (analyser.handle()) + numberOfSamples) / hop);
+        rawValues.resize ((std::size_t) channels * most * FX_NUM_FEATURES);
+        smoothedValues.resize (rawValues.size());
+        int frames = 0;
+        check (fx_push_sources (analyser.handle(), liveBlock, numberOfSamples, sampleFormat, FX_MEM_HOST,
+                                most ? rawValues.data() : nullptr, most ? smoothedValues.data() : nullptr, &frames));
+        lastFrames = frames;
+        if (frames > 0 && framesAnalysed) framesAnalysed (frames);
+        if (frames > 0) reportOnsets();
+        return frames;
+    }
     void setNotifyAnalysisThreadCallback (std::function<void (int)> f)  { framesAnalysed = f; }    // ref :107 (argument: frames per channel)
     // The tracks' onsetDetectedCallback (RealTimeAnalyser.h:256, AnalyserTrackController.h:80-84) as one callback: after each block
     // that completed frames it is called once per (track, frame) whose onset slot is 1, in (frame, track) order.  Setting it enables
@@ -437,6 +453,78 @@ private:
     std::function<void (int)> framesAnalysed;
     std::function<void (int, long long)> onsetDetected;
     std::function<std::vector<fx_onset_event>()> drainOnsets;
+};
+
+// AudioFilePlayer, ref Source/AudioFilePlayer.h:41-67 with the file half of AnalyserTrackController.h:92-138, for a SET of tracks of a
+// RealTimeBatchAnalyser: the tracks' players are rows of the context's transport table (fx.h, file sources), their files clips in
+// device memory.  One object per track is the reference's shape; one object for a group that is started and stopped together costs
+// one launch per command instead of one per track.  The audio itself moves in AudioDataCollector::pushSources, once per tick for the
+// whole context.  As in the reference the transport buttons clear the tracks' collectors (play, pause, stop; not restart), and
+// restart keeps the state (AudioFilePlayer.h:65).  Differences from the reference are those fx.h lists: no fade, no resampling,
+// each track hears its own player only; one-shot playback (setLooping (false)) ends in FX_TRANSPORT_FINISHED.
+class AudioFilePlayer
+{
+public:
+    AudioFilePlayer (RealTimeBatchAnalyser& analyserToPlayInto, std::vector<int> tracksToPlay)
+        : analyser (analyserToPlayInto), tracks (std::move (tracksToPlay)), clipOf (tracks.size(), -1) {}
+
+    // Files for any player of the context: `lengths.size()` clips back to back in host memory -> the first clip's id (fx_create_clips).
+    int createClips (const void* samples, const std::vector<long long>& lengths, int sampleFormat = FX_SAMPLE_F32)
+    {
+        int first = -1;
+        check (fx_create_clips (analyser.handle(), samples, lengths.data(), (int) lengths.size(), sampleFormat, FX_MEM_HOST, 0, &first));
+        return first;
+    }
+    void destroyClips (int firstId) { check (fx_destroy_clips (analyser.handle(), firstId)); }
+
+    // ref AudioFilePlayer.h:41-57 (and the file-dropped callback, AnalyserTrackController.h:109-124): every track of the set loads
+    // clipIds[i] (one id: all load the same clip; -1: no file), looping as the reference's reader source does unless told otherwise.
+    // The tracks stop at position 0 and their collectors are cleared.
+    void loadFileIntoTransport (const std::vector<int>& clipIds, bool looping = true)
+    {
+        if (clipIds.size() != tracks.size() && clipIds.size() != 1) throw Error (FX_ERR_INVALID_ARGUMENT, "one clip per track of the player, or one for all");
+        std::vector<int> ids (tracks.size()), loop (tracks.size(), looping ? 1 : 0);
+        for (std::size_t i = 0; i < tracks.size(); ++i) ids[i] = clipIds[clipIds.size() == 1 ? 0 : i];
+        check (fx_set_channel_clips (analyser.handle(), tracks.data(), (int) tracks.size(), ids.data(), loop.data()));
+        clipOf = ids;
+    }
+    void loadFileIntoTransport (int clipId, bool looping = true) { loadFileIntoTransport (std::vector<int> (1, clipId), looping); }
+    bool hasFile() const                                                                            // ref :67: every track of the set has one
+    {
+        for (int id : clipOf) if (id < 0) return false;
+        return ! clipOf.empty();
+    }
+    // AnalyserTrackController.h:92-107: the tracks listen to their player (true) or to the audio device (false, which stops the player)
+    void setFileSource (bool listenToFile)
+    {
+        const std::vector<int> types (tracks.size(), listenToFile ? FX_SOURCE_FILE : FX_SOURCE_INPUT);
+        check (fx_set_channel_sources (analyser.handle(), tracks.data(), (int) tracks.size(), types.data()));
+    }
+    void play()    { command (FX_PLAY); }                       // ref :59-63; refused (fx::Error) while a track of the set has no file
+    void pause()   { command (FX_PAUSE); }
+    void stop()    { command (FX_STOP); }
+    void restart() { command (FX_RESTART); }                    // ref :65: position 0, the state kept
+
+    struct Transport { std::vector<int> source, state; std::vector<long long> position, laps; };   // one entry per track of the set
+    Transport getTransport() const
+    {
+        const std::size_t all = (std::size_t) analyser.getNumChannels();
+        std::vector<int> source (all), state (all);
+        std::vector<long long> position (all), laps (all);
+        check (fx_get_transport (analyser.handle(), source.data(), state.data(), position.data(), laps.data()));
+        Transport t;
+        for (int c : tracks) {
+            t.source.push_back (source[(std::size_t) c]); t.state.push_back (state[(std::size_t) c]);
+            t.position.push_back (position[(std::size_t) c]); t.laps.push_back (laps[(std::size_t) c]);
+        }
+        return t;
+    }
+    const std::vector<int>& getTracks() const { return tracks; }
+
+private:
+    void command (int which) { check (fx_transport (analyser.handle(), tracks.data(), (int) tracks.size(), which)); }
+    RealTimeBatchAnalyser& analyser;
+    std::vector<int> tracks, clipOf;
 };
 
 // The stand-in for AudioDataCollector's ring (ref Source/AudioDataCollector.h:24,36-94: the audio thread writes a ring, the analysis thread
