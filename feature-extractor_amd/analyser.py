@@ -274,7 +274,7 @@ class BatchAnalyser:
     def last_launches(self):
         """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
         (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events, osc_table,
-        osc_bundle, display, sources)."""
+        osc_bundle, display, sources, resample)."""
         cap = capi.LAUNCH_RECORD_CAP
         buf = (ctypes.c_int * (cap * len(capi.LAUNCH_FIELDS)))()
         n = self._lib.fx_last_launches_internal(self._h, buf, cap)
@@ -520,11 +520,12 @@ class BatchAnalyser:
         return self._analyse("fx_push_interleaved", d, (n, K), frames, want_raw, want_smoothed, block=True)
 
     # ---- file sources: tracks play device-resident clips (include/fx.h, fx_create_clips .. fx_push_sources; AudioFilePlayer.h:41-67) ----
-    def create_clips(self, samples, lengths=None, sample_format=None, borrow=False):
+    def create_clips(self, samples, lengths=None, sample_format=None, borrow=False, sample_rates=None):
         """A bank of clips in device memory -> the first clip's id (the clips get consecutive ids).  `samples`: the clips back to back
         as ONE numpy array (host) or torch CUDA tensor (from a 4-byte boundary) with `lengths` in samples, or a list of numpy arrays,
         one clip each.  Formats as push_samples.  borrow=True (device tensors only): the bank refers to the tensor's memory, which
-        the analyser keeps alive until destroy_clips and the caller must not change."""
+        the analyser keeps alive until destroy_clips and the caller must not change.  sample_rates: the clips' own rate in Hz, one
+        for all or one per clip (set_clip_rates); None or 0: the context's."""
         if isinstance(samples, (list, tuple)):
             if lengths is not None:
                 raise ValueError("a list of clips carries its own lengths")
@@ -545,6 +546,7 @@ class BatchAnalyser:
             raise ValueError("the clips' lengths add up to %d samples, the bank holds %d" % (int(ls.sum()), count))
         if borrow and mem != capi.MEM_DEVICE:
             raise ValueError("only a device tensor can be borrowed")
+        rates = None if sample_rates is None else self._clip_rates(sample_rates, int(ls.size))
         first = ctypes.c_int(-1)
         args = (self._h, ptr, ls.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(ls.size), fmt, mem, capi.CLIP_BORROW if borrow else 0, ctypes.byref(first))
         if mem == capi.MEM_DEVICE:
@@ -557,7 +559,28 @@ class BatchAnalyser:
             if not hasattr(self, "_borrowed"):
                 self._borrowed = {}
             self._borrowed[first.value] = keep
+        if rates is not None:
+            self.set_clip_rates(range(first.value, first.value + int(ls.size)), rates)
         return first.value
+
+    @staticmethod
+    def _clip_rates(rates, size):
+        """one float64 per clip from a scalar or a sequence"""
+        v = np.asarray(rates, dtype=np.float64).ravel()
+        if v.size == 1 and size != 1:
+            v = np.full(size, v[0], np.float64)
+        if v.size != size:
+            raise ValueError("one sample rate per clip (%d), not %d" % (size, v.size))
+        return np.ascontiguousarray(v)
+
+    def set_clip_rates(self, clip_ids, rates):
+        """fx_set_clip_rates: clip clip_ids[i] is a file of rates[i] Hz (one rate for all is fine; 0: the context's rate).  A track that
+        loads a clip whose rate is not the context's plays it through the resampler of include/fx.h, at the right pitch.  Refused
+        while a listed clip is loaded on a track."""
+        ids = np.ascontiguousarray(np.asarray(list(clip_ids), dtype=np.int32).ravel())
+        v = self._clip_rates(rates, int(ids.size))
+        capi.check(self._lib.fx_set_clip_rates(self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(ids.size),
+                                               v.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
 
     def destroy_clips(self, first_id):
         """Frees the bank whose first clip is `first_id`; refused while a track has one of its clips loaded."""
@@ -621,7 +644,8 @@ class BatchAnalyser:
         """One tick: every track gets n samples -- row c of `live` ([C][n] as push_samples takes it) where the track's source is the
         input, its clip's next n samples where it plays a file, silence otherwise -- and they are analysed as push_samples analyses
         them -> (raw, smoothed).  live=None (allowed while no track listens to the input) needs num_samples and sample_format (the
-        clips' format, "f32" by default); device=True then returns torch tensors."""
+        clips' format, "f32" by default -- which is also what a tick must be in while a clip with a rate of its own is loaded: the
+        resampler renders fp32); device=True then returns torch tensors."""
         if live is not None:
             d = _describe_input(live, sample_format, self.device, 4)
             n, rest = divmod(d[3], self.num_channels)

@@ -24,7 +24,7 @@ MAX_UNITS = 24
 LAUNCH_FIELDS = ["kind", "window", "analysers", "T", "direct_state", "block_mode", "num_chunks", "ch_per_wg", "waves_per_ch", "hop_pairs",
                  "ep_T", "out_stride", "ep_form", "reblock"]
 LAUNCH_KINDS = {1: "frame", 2: "frame_tail", 3: "hop", 4: "hop_pair", 5: "pair", 6: "epilogue", 7: "reblock", 8: "osc", 9: "taps",
-                10: "deinterleave", 11: "onset_events", 12: "osc_table", 13: "osc_bundle", 14: "display", 15: "sources"}
+                10: "deinterleave", 11: "onset_events", 12: "osc_table", 13: "osc_bundle", 14: "display", 15: "sources", 16: "resample"}
 # file sources (include/fx.h): FX_SOURCE_*, FX_TRANSPORT_*, the fx_transport commands FX_PLAY .. FX_RESTART, FX_CLIP_BORROW
 SOURCE_INPUT, SOURCE_FILE = 0, 1
 TRANSPORT_NO_FILE, TRANSPORT_PLAYING, TRANSPORT_PAUSED, TRANSPORT_STOPPED, TRANSPORT_FINISHED = range(5)
@@ -104,6 +104,7 @@ def _prototypes():
         ("fx_set_channel_map", [vp, ip], st), ("fx_push_interleaved", [vp, vp, i, i, i, i, vp, vp, ip], st),
         ("fx_pending_samples", [vp], st), ("fx_clear_pending", [vp], st),
         ("fx_create_clips", [vp, vp, llp, i, i, i, u, ip], st), ("fx_destroy_clips", [vp, i], st), ("fx_set_channel_clips", [vp, ip, i, ip, ip], st),
+        ("fx_set_clip_rates", [vp, ip, i, dp], st), ("fx_get_resampler_table", [fp, i, ip, ip], st),
         ("fx_set_channel_sources", [vp, ip, i, ip], st), ("fx_transport", [vp, ip, i, i], st), ("fx_get_transport", [vp, ip, ip, llp, llp], st),
         ("fx_push_sources", [vp, vp, i, i, i, vp, vp, ip], st), ("fx_process_frames", [vp, vp, i, i, i, vp, vp], st),
         ("fx_get_smoothed", [vp, vp, i], st), ("fx_host_alloc", [vpp, ctypes.c_size_t], st), ("fx_host_free", [vp], st),
@@ -208,6 +209,17 @@ def plan_units(window_size, flags, waves_per_channel, num_frames, tuning=None):
 
 def _fp(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+RESAMPLER_ZERO_CROSSINGS, RESAMPLER_PHASES = 16, 512
+
+
+def resampler_table():
+    """fx_get_resampler_table: (the table float32 [Z * P + 2], Z, P) of the resampler rated clips play through (host arithmetic)"""
+    out = np.empty(RESAMPLER_ZERO_CROSSINGS * RESAMPLER_PHASES + 2, np.float32)
+    z, p = ctypes.c_int(0), ctypes.c_int(0)
+    check(load_library().fx_get_resampler_table(_fp(out), out.size, ctypes.byref(z), ctypes.byref(p)))
+    return out, z.value, p.value
 
 
 def pack_osc12(features12):

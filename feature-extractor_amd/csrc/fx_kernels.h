@@ -425,6 +425,9 @@ constexpr int FX_LAUNCH_DISPLAY = 14;
 // fx_push_sources (fx_clips.hip): one launch of fx_clip_gather_kernel, the FIRST entry of the call's record; T = the samples per track
 // the call forms.  The entries after it are those of fx_push_samples on the planar block it made.
 constexpr int FX_LAUNCH_SOURCES = 15;
+// fx_push_sources while a FILE track has a rated clip loaded: one launch of fx_clip_resample_kernel, the SECOND entry of the call's
+// record, after the gather; T = the samples per track.  A context without such a track records no entry of this kind.
+constexpr int FX_LAUNCH_RESAMPLE = 16;
 struct fx_launch_record {
     int kind;               // FX_LAUNCH_*
     int window, analysers;  // window size, analysers mask (bit 0 spectral, bit 1 harmonic)

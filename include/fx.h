@@ -277,7 +277,8 @@ fx_status fx_clear_pending(fx_context* ctx);
  * them as fx_push_samples would.  So thousands of tracks play thousands of files of different lengths in one context, and no file
  * sample crosses the host link after its bank was made.
  *
- * CLIPS.  A clip is L >= 1 samples of one FX_SAMPLE_* format in device memory, at the context's sample rate.  Clips are made in
+ * CLIPS.  A clip is L >= 1 samples of one FX_SAMPLE_* format in device memory, at the context's sample rate unless
+ * fx_set_clip_rates says otherwise (CLIPS AT THEIR OWN RATE, below).  Clips are made in
  * banks, one allocation and one copy per bank: `samples` holds num_clips (>= 1) clips back to back, lengths[k] samples each, in
  * FX_MEM_HOST or FX_MEM_DEVICE memory (device memory from a 4-byte boundary); the clips get the ids *first_id, *first_id + 1, ...
  * With FX_CLIP_BORROW (FX_MEM_DEVICE only) the bank is not copied: it refers to the caller's memory, which must stay valid and
@@ -331,8 +332,44 @@ fx_status fx_clear_pending(fx_context* ctx);
  * fx_reset_state and fx_reset_channels leave the table alone: it is the player's state, not the analysers'.  Records of
  * fx_export_channels do not carry it: like the display it belongs to the slot.
  *
- * Deliberate differences from the reference.  JUCE's AudioTransportSource is not part of the reference tree: its fade on stop, its
- * read-ahead buffer and its sample-rate correction are not reproduced (clips are at the context's rate).  Each track hears its own
+ * CLIPS AT THEIR OWN RATE.  The reference hands the reader's rate to its transport source "for sample rate correction"
+ * (AudioFilePlayer.h:55-58): a 44.1 kHz file keeps its pitch on a 48 kHz device.  fx_set_clip_rates gives clip clip_ids[i] the rate
+ * sample_rates[i] in Hz; 0, every clip's default, means the context's rate.  The lists follow fx_reset_channels' rules (host memory,
+ * num_clips == 0 is a no-op, of a duplicate id the last entry wins); every entry is checked before anything changes and before
+ * any device use (an unknown id; a rate that is NaN, infinite or negative); and the call is refused, naming the track, while a
+ * listed clip is loaded on any track: the rate is the file's and is set before loading.
+ *   At fx_set_channel_clips a track is RATED if its clip's rate is neither 0 nor the context's sample rate.  The host forms
+ * r = clip rate / context rate and rho = min(1, 1/r) in fp64 and J = ceil(Z / rho); they go into the track's row, so the device never
+ * divides.  r outside [1/8, 8] refuses the load, naming the entry.  The host remembers the context's rate at the load of every clip
+ * with a rate of its own: after a later fx_set_sample_rate, fx_push_sources is refused (FX_ERR_INVALID_ARGUMENT names the track,
+ * nothing changes) while a FILE track holds such a clip, until the clip is loaded again.
+ *   A rated clip may be in any FX_SAMPLE_* format: the resampler widens it as the load stage would and renders fp32.  So while any
+ * FILE track has a rated clip loaded, whatever its state, a tick must be FX_SAMPLE_F32 (refused otherwise, naming the track); the
+ * unrated FILE clips keep their rule.  The launch record then holds the resampler's launch after the gather's; a context without a
+ * rated clip on a FILE track runs exactly the launches it ran before.
+ *   The resampler is ours (JUCE's is not in the reference tree) and this is its specification.  THE TABLE is one side of a
+ * Kaiser-windowed sinc with Z = 16 zero crossings, P = 512 phases and beta = 9:
+ *   T[i] = fl32(sinc(i/P) * I0(beta * sqrt(1 - (i/(P*Z))^2)) / I0(beta)) for 0 <= i < Z*P, computed on the host in fp64;
+ *   T[Z*P] = T[Z*P + 1] = +0: Z*P + 2 entries.  fx_get_resampler_table copies them to out[capacity] (host only: no device, no
+ *   context; refused if capacity < Z*P + 2) and reports Z and P.  The kernel reads a device copy of the same table.
+ * A rated track's row carries k (int64), the outputs rendered since its position was last set to 0: a load, FX_STOP, FX_RESTART,
+ * a switch to INPUT and FX_PLAY from FINISHED set k to 0, FX_PAUSE keeps it.  A tick of n samples renders, while the track is
+ * PLAYING (zeros otherwise, as for any FILE track), output k' = k + i for 0 <= i < n, every operation IEEE in the stated type, none
+ * contracted:
+ *   x = fl64(k') * r;  i0 = floor(x);  f = x - i0;  acc = +0 (fp32);  for j = -(J-1) .. J, ascending:
+ *     a = |fl64(j) - f| * rho; a tap with a >= Z is not added;  q = a * P;  i = floor(q);  t = fl32(q - i);
+ *     c = T[i] + t * (T[i+1] - T[i]) (fp32);  m = i0 + j;  looping: s = widen(clip[m mod L]), the mathematical modulo; one-shot: a tap
+ *     with m outside [0, L) is not added;  acc = acc + c * s (fp32)
+ *   out = acc * fl32(rho), and for a one-shot out = +0 where x >= L.
+ * After the tick k = k + n and, with x' = fl64(k) * r: looping: position = floor(x') mod L, laps = floor(x') div L; one-shot: position
+ * = min(floor(x'), L) and the state is FINISHED iff x' >= L.  fx_get_transport reports these.  The gain stays the load stage's.
+ * x depends on the absolute k' alone, so any cut of a stream into ticks gives the same samples bit for bit.  The phase resolution
+ * falls as k grows: ulp(x) is 2^-20 source samples after 2^32 outputs.  The tests reach no k beyond what their ticks add up to: the
+ * conversion of a 64-bit k to fp64 is untested on the device beyond that.
+ *
+ * Deliberate differences from the reference.  JUCE's AudioTransportSource is not part of the reference tree: its fade on stop and
+ * its read-ahead buffer are not reproduced, and its sample-rate correction (JUCE's ResamplingAudioSource, absent as well) is
+ * replaced by the windowed-sinc resampler specified above, so a rated clip's samples are ours, not JUCE's.  Each track hears its own
  * player only: in the reference every player renders into the sound card's shared output buffers, so tracks playing at once hear
  * each other -- a property of the one device, not carried over.  One-shot playback and FINISHED are ours. */
 enum { FX_SOURCE_INPUT = 0, FX_SOURCE_FILE = 1 };
@@ -343,6 +380,8 @@ fx_status fx_create_clips(fx_context* ctx, const void* samples, const long long*
                           int mem_kind, unsigned flags, int* first_id);
 fx_status fx_destroy_clips(fx_context* ctx, int first_id);
 fx_status fx_set_channel_clips(fx_context* ctx, const int* channels, int num_channels, const int* clip_ids, const int* loop);
+fx_status fx_set_clip_rates(fx_context* ctx, const int* clip_ids, int num_clips, const double* sample_rates);
+fx_status fx_get_resampler_table(float* out, int capacity, int* zero_crossings, int* phases);
 fx_status fx_set_channel_sources(fx_context* ctx, const int* channels, int num_channels, const int* types);
 fx_status fx_transport(fx_context* ctx, const int* channels, int num_channels, int command);
 fx_status fx_get_transport(fx_context* ctx, int* source, int* state, long long* position, long long* laps);

@@ -460,7 +460,7 @@ private:
 // device memory.  One object per track is the reference's shape; one object for a group that is started and stopped together costs
 // one launch per command instead of one per track.  The audio itself moves in AudioDataCollector::pushSources, once per tick for the
 // whole context.  As in the reference the transport buttons clear the tracks' collectors (play, pause, stop; not restart), and
-// restart keeps the state (AudioFilePlayer.h:65).  Differences from the reference are those fx.h lists: no fade, no resampling,
+// restart keeps the state (AudioFilePlayer.h:65).  Differences from the reference are those fx.h lists: no fade, a resampler of our own,
 // each track hears its own player only; one-shot playback (setLooping (false)) ends in FX_TRANSPORT_FINISHED.
 class AudioFilePlayer
 {
@@ -469,11 +469,27 @@ public:
         : analyser (analyserToPlayInto), tracks (std::move (tracksToPlay)), clipOf (tracks.size(), -1) {}
 
     // Files for any player of the context: `lengths.size()` clips back to back in host memory -> the first clip's id (fx_create_clips).
-    int createClips (const void* samples, const std::vector<long long>& lengths, int sampleFormat = FX_SAMPLE_F32)
+    // `sampleRates`: the files' own rates in Hz, one per clip (the reader->sampleRate the reference hands to setSource "for sample
+    // rate correction", ref AudioFilePlayer.h:55-58); empty or 0: the context's rate.
+    int createClips (const void* samples, const std::vector<long long>& lengths, int sampleFormat = FX_SAMPLE_F32,
+                     const std::vector<double>& sampleRates = std::vector<double>())
     {
+        if (! sampleRates.empty() && sampleRates.size() != lengths.size()) throw Error (FX_ERR_INVALID_ARGUMENT, "one sample rate per clip");
         int first = -1;
         check (fx_create_clips (analyser.handle(), samples, lengths.data(), (int) lengths.size(), sampleFormat, FX_MEM_HOST, 0, &first));
+        if (! sampleRates.empty())
+        {
+            std::vector<int> ids (lengths.size());
+            for (std::size_t i = 0; i < ids.size(); ++i) ids[i] = first + (int) i;
+            setClipRates (ids, sampleRates);
+        }
         return first;
+    }
+    // fx_set_clip_rates: refused while a listed clip is loaded on a track -- the rate is the file's and is set before loading
+    void setClipRates (const std::vector<int>& clipIds, const std::vector<double>& sampleRates)
+    {
+        if (clipIds.size() != sampleRates.size()) throw Error (FX_ERR_INVALID_ARGUMENT, "one sample rate per clip");
+        check (fx_set_clip_rates (analyser.handle(), clipIds.data(), (int) clipIds.size(), sampleRates.data()));
     }
     void destroyClips (int firstId) { check (fx_destroy_clips (analyser.handle(), firstId)); }
 

@@ -12,6 +12,11 @@
                (64 calls back to back on the library's stream through the C ABI, outputs preallocated, one synchronisation per
                pass), passes of the two alternated, median pass.
   (c) tiny     the same with every track looping a 1-sample and a 5-sample clip: the gather's byte-by-byte path.
+  (d) rated    clips at their own sample rate (fx_set_clip_rates): a 480-sample fx_push_sources tick at 1024 and 8192 tracks,
+               2048-point windows, with every track looping a 48 000-sample clip that is (1) unrated fp32, (2) 44.1 kHz in s16 and
+               (3) 96 kHz in fp32, in a 48 kHz context -- timed as (b), passes of the three alternated, median pass.  The resample
+               kernel's own time comes from a kernel trace of the same part in a run of its own (kernel_times DIR);
+               profiles/clip_resample.txt holds a run's output.
 
 Prints plain lines; profiles/clip_sources.txt holds a run's output.
 """
@@ -45,11 +50,11 @@ def _samples(torch, count, fmt, seed):
     return x if fmt == "f32" else x.to(torch.float16)
 
 
-def _playing(torch, C, N, fmt, L, seed):
-    """a context whose C tracks each play (looping) their own clip of L samples from one borrowed bank"""
+def _playing(torch, C, N, fmt, L, seed, rate=None):
+    """a context whose C tracks each play (looping) their own clip of L samples, files of `rate` Hz, from one borrowed bank"""
     an = fx.BatchAnalyser(C, N)
     bank = _samples(torch, C * L, fmt, seed)
-    first = an.create_clips(bank, lengths=[L] * C, sample_format=fmt, borrow=True)
+    first = an.create_clips(bank, lengths=[L] * C, sample_format=fmt, borrow=True, sample_rates=rate)
     tracks = list(range(C))
     an.load_clips(tracks, [first + k for k in tracks])
     an.set_sources(tracks, "file")
@@ -157,9 +162,44 @@ def live(reps, lengths, label, calls=64):
             an.close(); twin.close()
 
 
+RATED_SETUPS = [("unrated fp32 loops", "f32", None), ("44.1k -> 48k, s16 clips", "s16", 44100.0), ("96k -> 48k, fp32 clips", "f32", 96000.0)]
+
+
+def rated(reps, calls=64):
+    """(d): the three set-ups' ticks, timed as live() times its two entry points"""
+    import torch
+    n, N, L = 480, 2048, 48000
+    F32, DEV = fx.capi.SAMPLE_F32, fx.capi.MEM_DEVICE
+    for C in (1024, 8192):
+        ans = [_playing(torch, C, N, fmt, L, 31 + i, rate) for i, (_, fmt, rate) in enumerate(RATED_SETUPS)]
+        sm = torch.empty((C, 1, 12), dtype=torch.float32, device="cuda")       # a 480-sample block completes <= 1 hop
+        torch.cuda.synchronize()
+
+        def one_pass(an):
+            an.sync()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                fx.capi.check(an._lib.fx_push_sources(an._h, None, n, F32, DEV, None, ctypes.c_void_p(sm.data_ptr()), None))
+            an.sync()
+            return (time.perf_counter() - t0) / calls * 1e6
+
+        for an in ans:
+            one_pass(an)                                                        # warm: buffers sized, kernels loaded
+        times = [[] for _ in ans]
+        for r in range(reps):
+            for i in ([0, 1, 2], [2, 0, 1], [1, 2, 0])[r % 3]:
+                times[i].append(one_pass(ans[i]))
+        med = [statistics.median(t) for t in times]
+        for (label, _, _), m in zip(RATED_SETUPS, med):
+            print("(d) %5d tracks each looping a %d-sample clip, %d-sample f32 ticks, %d-pt, %d calls back to back per pass, median of %d passes: "
+                  "%-24s %.1f us per fx_push_sources call, %.3f x the unrated tick" % (C, L, n, N, calls, reps, label + ":", m, m / med[0]), flush=True)
+        for an in ans:
+            an.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("part", choices=["kernels", "summary", "live", "tiny", "kernel_times"])
+    ap.add_argument("part", choices=["kernels", "summary", "live", "tiny", "rated", "kernel_times"])
     ap.add_argument("trace_dir", nargs="?")
     ap.add_argument("--reps", type=int, default=15)
     a = ap.parse_args()
@@ -169,6 +209,8 @@ def main():
         summary(a.trace_dir)
     elif a.part == "kernel_times":
         kernel_times(a.trace_dir)
+    elif a.part == "rated":
+        rated(a.reps)
     elif a.part == "live":
         live(a.reps, [48000], "b")
     else:
