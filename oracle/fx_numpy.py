@@ -201,6 +201,12 @@ def pitch(fre, nyquist):
     for i in range(1, 2 * n):
         s = f32(s + v[i])
         cnd[i] = f32(v[i] / s) if s != 0 else f32(0)
+    lag = lag_search(cnd, n)
+    return (nyquist * 2.0) / lag, lag, cnd
+
+
+def lag_search(cnd, n):
+    """ref PitchAnalyser.h:161-217 on cnd[0 .. n] (the walk may look at cnd[n]): the lag estimate, -1.0 if there is none."""
     gmin, gidx, lag = f32(100.0), -1.0, -1.0
     i = 2
     while i < n:
@@ -213,8 +219,7 @@ def pitch(fre, nyquist):
             lag = float(i) if cnd[i] <= cnd[right] else float(right)
             break
         i += 1
-    lag = gidx if lag == -1.0 else lag
-    return (nyquist * 2.0) / lag, lag, cnd
+    return gidx if lag == -1.0 else lag
 
 
 def harmonic(re, f0, nyquist):

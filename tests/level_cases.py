@@ -15,6 +15,7 @@ import zlib
 
 import numpy as np
 
+import lag_cases
 import signals
 
 T = 12
@@ -138,17 +139,11 @@ def windows(h):
 def lag_regime(oracle, window):
     """which part of the lag search (PitchAnalyser.h:161-190) decides this window, by the oracle's own cnd (fxo_estimate_pitch): the 64-sample
     block in which the walk from the first cnd < 0.01 stops falling -- where a kernel that takes the cnd block by block may stop -- or the
-    global-minimum fallback.  -> one of LAG_REGIMES; the lag the walk gives is checked against the oracle's"""
-    window = np.ascontiguousarray(window, np.float32)
-    N = window.shape[0]
-    pitch = oracle.forward_real(oracle.bartlett(oracle.lowpass(window)))
-    _, lag, cnd = oracle.estimate_pitch(pitch)
-    s = 2
-    while s < N and not cnd[s] < np.float32(0.01):
-        s += 1
-    if s == N:
+    global-minimum fallback.  -> one of LAG_REGIMES; the lag the walk gives is checked against the oracle's.  (The classification is
+    tests/lag_cases.py's, which holds a frame for every seam between the blocks; these regimes are the coarse view of it.)"""
+    lag, cnd = lag_cases.oracle_cnd(oracle, window)
+    kind, _, s, mine = lag_cases.classify_cnd(cnd, len(window))
+    if kind == "fallback":
         return "fallback"
-    while s + 1 < N and cnd[s + 1] < cnd[s]:
-        s += 1
-    assert lag == (s if cnd[s] <= cnd[s + 1] else s + 1), (lag, s)
+    assert lag == mine, (lag, s)
     return "blocks 0-1" if s + 1 < 128 else "blocks 2-3" if s + 1 < 256 else "past 255"

@@ -135,7 +135,13 @@ def test_lag_search_regimes_of_the_1024_point_case(oracle):
     The global-minimum fallback (no cnd below 0.01 in [2, N)) is not among them and no band-level channel of the low tones supplies it
     at 1024 points (every channel of low_tones at 8 to 24 channels and every signal of tests/signals.py was tried at full scale and at
     every band level): with a smooth autocorrelation cnd[s] is about 2 / s, below the threshold from s = 200 on, so only a 256-point
-    window can end there.  The 256-point case does, and the fallback's code (LagSearch::finish) is the same at every size."""
+    window can end there.  The 256-point case does, and the fallback's code (LagSearch::finish) is the same at every size.
+    (tests/golden/make_lag_cases.py looked again, over four families of synthetic frames and short decaying bursts: still no fallback at
+    512 points or more -- lag_cases.UNREACHED says so per size.)
+
+    These regimes are the coarse view.  The seams between them -- `first` and `stop` on lanes 62, 63, 0 and 1 of every 64-sample block
+    up to block 7, samples 126-129 and 254-257 on both sides, the walk to N-1 that is decided against cnd[N] -- are held by the frames
+    of tests/lag_cases.py (tests/test_lag_cases_cpu.py, tests/test_gpu_lag_cases.py); lag_regime shares its classification."""
     def regimes(N, chans):
         hops = lc.hops(N)
         return {(i, t): lc.lag_regime(oracle, w) for i in chans for t, w in enumerate(lc.windows(hops[i]))}
