@@ -274,7 +274,7 @@ class BatchAnalyser:
     def last_launches(self):
         """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
         (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events, osc_table,
-        osc_bundle, display, sources, resample)."""
+        osc_bundle, display, sources, resample, monitor)."""
         cap = capi.LAUNCH_RECORD_CAP
         buf = (ctypes.c_int * (cap * len(capi.LAUNCH_FIELDS)))()
         n = self._lib.fx_last_launches_internal(self._h, buf, cap)
@@ -666,6 +666,65 @@ class BatchAnalyser:
             d = (None, _FORMAT_NAMES[name], capi.MEM_DEVICE if device else capi.MEM_HOST, 0, None, where)
         frames = (self.pending_samples() + n) // (self.window_size // 2) if n > 0 else 0
         return self._analyse("fx_push_sources", d, (n,), frames, want_raw, want_smoothed, block=True)
+
+    # ---- monitor mix: every tick's tracks summed to a stereo output (include/fx.h, fx_enable_monitor .. fx_get_monitor) ----
+    def enable_monitor(self, enable=True):
+        """Make the monitor (every send off, gains 1 / 1, no tick yet) or free it; enabling an enabled monitor keeps its sends.  While
+        it is enabled every push_sources tick also mixes what the tracks play down to two output channels on the device."""
+        capi.check(self._lib.fx_enable_monitor(self._h, 1 if enable else 0))
+
+    def _gains(self, values, size, what):
+        """one finite float32 per list entry from a scalar or a sequence; None stays None (that gain is kept)"""
+        if values is None:
+            return None, None
+        v = np.asarray(values, dtype=np.float32).ravel()
+        if v.size == 1 and size != 1:
+            v = np.full(size, v[0], np.float32)
+        if v.size != size:
+            raise ValueError("one %s gain per listed track (%d), not %d" % (what, size, v.size))
+        bad = np.flatnonzero(~np.isfinite(v))
+        if bad.size:
+            raise ValueError("entry %d: the %s gain %r is not a finite number" % (int(bad[0]), what, float(v[bad[0]])))
+        v = np.ascontiguousarray(v)
+        return v, v.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+    def set_monitor(self, channels, on=True, left=None, right=None):
+        """The listed tracks' sends: on (one flag or one per entry), left / right gain (one value or one per entry; None keeps it).
+        Of a track listed twice the last entry wins.  In force from the next tick on."""
+        a, ptr = self._track_list(channels)
+        flags = list(on) if isinstance(on, (list, tuple, np.ndarray)) else [on]
+        o, op = self._per_entry([int(bool(x)) for x in flags], int(a.size))
+        l, lp = self._gains(left, int(a.size), "left")
+        r, rp = self._gains(right, int(a.size), "right")
+        capi.check(self._lib.fx_set_channel_monitor(self._h, ptr, int(a.size), op, lp, rp))
+
+    def monitor_sends(self):
+        """The send table: dict of on (int32 [C]), left, right (float32 [C])."""
+        C = self.num_channels
+        out = {"on": np.empty(C, np.int32), "left": np.empty(C, np.float32), "right": np.empty(C, np.float32)}
+        fp = ctypes.POINTER(ctypes.c_float)
+        capi.check(self._lib.fx_get_channel_monitor(self._h, out["on"].ctypes.data_as(ctypes.POINTER(ctypes.c_int)), out["left"].ctypes.data_as(fp),
+                                                    out["right"].ctypes.data_as(fp)))
+        return out
+
+    def get_monitor(self, device=False):
+        """The last tick's mix, float32 [2][n] (left, right; n == 0 before the first tick): numpy, or (device=True) a CUDA torch tensor
+        written asynchronously on the library's stream."""
+        n, probe = ctypes.c_int(0), ctypes.c_float(0.0)
+        # (no room at all: refused while a mix is held, and the refusal still reports the mix's length)
+        status = self._lib.fx_get_monitor(self._h, ctypes.byref(probe), 0, ctypes.byref(n), capi.MEM_HOST)
+        if status != capi.FX_OK and n.value == 0:
+            capi.check(status)
+        if device:
+            import torch
+            out = torch.empty((2, n.value), dtype=torch.float32, device=torch.device("cuda", self.device))
+            if n.value:
+                self._ordered(out.device, self._lib.fx_get_monitor, self._h, ctypes.c_void_p(out.data_ptr()), n.value, ctypes.byref(n), capi.MEM_DEVICE)
+        else:
+            out = np.empty((2, n.value), np.float32)
+            if n.value:
+                capi.check(self._lib.fx_get_monitor(self._h, out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n), capi.MEM_HOST))
+        return out
 
     def get_features(self, out=None):
         """Latest AudioFeatures::getValue of every slot, [C][12]: a host array, or -- with `out`, a contiguous

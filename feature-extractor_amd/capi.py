@@ -24,13 +24,14 @@ MAX_UNITS = 24
 LAUNCH_FIELDS = ["kind", "window", "analysers", "T", "direct_state", "block_mode", "num_chunks", "ch_per_wg", "waves_per_ch", "hop_pairs",
                  "ep_T", "out_stride", "ep_form", "reblock"]
 LAUNCH_KINDS = {1: "frame", 2: "frame_tail", 3: "hop", 4: "hop_pair", 5: "pair", 6: "epilogue", 7: "reblock", 8: "osc", 9: "taps",
-                10: "deinterleave", 11: "onset_events", 12: "osc_table", 13: "osc_bundle", 14: "display", 15: "sources", 16: "resample"}
+                10: "deinterleave", 11: "onset_events", 12: "osc_table", 13: "osc_bundle", 14: "display", 15: "sources", 16: "resample", 17: "monitor"}
 # file sources (include/fx.h): FX_SOURCE_*, FX_TRANSPORT_*, the fx_transport commands FX_PLAY .. FX_RESTART, FX_CLIP_BORROW
 SOURCE_INPUT, SOURCE_FILE = 0, 1
 TRANSPORT_NO_FILE, TRANSPORT_PLAYING, TRANSPORT_PAUSED, TRANSPORT_STOPPED, TRANSPORT_FINISHED = range(5)
 PLAY, PAUSE, STOP, RESTART = range(4)
 TRANSPORT_COMMANDS = {"play": PLAY, "pause": PAUSE, "stop": STOP, "restart": RESTART}
 CLIP_BORROW = 1
+MONITOR_GROUP = 64                  # FX_MONITOR_GROUP: the tracks whose sends are summed in a row before the groups are
 MAX_DISPLAY_LENGTH, MAX_DISPLAY_SAMPLES_PER_BLOCK = 4096, 65536
 MAX_TAP_CHANNELS = 64
 OSC_ADDRESS_MAX = 124               # FX_OSC_ADDRESS_MAX
@@ -106,7 +107,9 @@ def _prototypes():
         ("fx_create_clips", [vp, vp, llp, i, i, i, u, ip], st), ("fx_destroy_clips", [vp, i], st), ("fx_set_channel_clips", [vp, ip, i, ip, ip], st),
         ("fx_set_clip_rates", [vp, ip, i, dp], st), ("fx_get_resampler_table", [fp, i, ip, ip], st),
         ("fx_set_channel_sources", [vp, ip, i, ip], st), ("fx_transport", [vp, ip, i, i], st), ("fx_get_transport", [vp, ip, ip, llp, llp], st),
-        ("fx_push_sources", [vp, vp, i, i, i, vp, vp, ip], st), ("fx_process_frames", [vp, vp, i, i, i, vp, vp], st),
+        ("fx_push_sources", [vp, vp, i, i, i, vp, vp, ip], st),
+        ("fx_enable_monitor", [vp, i], st), ("fx_set_channel_monitor", [vp, ip, i, ip, fp, fp], st), ("fx_get_channel_monitor", [vp, ip, fp, fp], st),
+        ("fx_get_monitor", [vp, vp, i, ip, i], st), ("fx_process_frames", [vp, vp, i, i, i, vp, vp], st),
         ("fx_get_smoothed", [vp, vp, i], st), ("fx_host_alloc", [vpp, ctypes.c_size_t], st), ("fx_host_free", [vp], st),
         ("fx_sync", [vp], st), ("fx_get_stream", [vp, vpp], st), ("fx_last_kernel_ms", [vp, fp, fp], st),
         ("fx_request_taps", [vp, ip, i], st), ("fx_get_taps", [vp, i, fp, fp, fp, fp, fp, fp, llp], st),

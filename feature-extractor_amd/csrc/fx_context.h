@@ -1,6 +1,6 @@
 // fx_context.h -- the context behind the C ABI (include/fx.h), shared by the shim's host units (fx_capi.cpp, fx_plan.cpp, fx_stream.cpp,
 // fx_comm.cpp) and the units that attach through its hooks (fx_taps.hip, fx_interleave.hip, fx_events.hip, fx_tracks.hip,
-// fx_osc_table.hip, fx_osc_bundle.hip, fx_track_state.hip, fx_display.hip, fx_clips.hip).  Internal.
+// fx_osc_table.hip, fx_osc_bundle.hip, fx_track_state.hip, fx_display.hip, fx_clips.hip, fx_monitor.hip).  Internal.
 #ifndef FX_CONTEXT_H
 #define FX_CONTEXT_H
 
@@ -63,6 +63,7 @@ struct fx_tracks;       // fx_tracks.hip
 struct fx_track_state;  // fx_track_state.hip
 struct fx_display;      // fx_display.hip
 struct fx_clips;        // fx_clips.hip
+struct fx_monitor;      // fx_monitor.hip
 // The OSC address table in force (fx_osc_table.hip makes and frees it; fx_osc_bundle.hip reads it): one device allocation, [C][128]
 // bytes of rows, then int len[C]; the messages' lengths on the host.
 struct fx_osc_table {
@@ -201,6 +202,16 @@ struct fx_context {
     // first call of that unit, which installs the hook fx_destroy calls.  The player's state, not the analysers': no reset touches it.
     fx_clips* clips = nullptr;
     void (*clips_release)(fx_context*) = nullptr;
+
+    // the monitor mix (fx_monitor.hip): the send table, the partial sums and the last tick's mix; null until fx_enable_monitor, which
+    // installs the hooks (and removes them again when it disables the monitor).  fx_push_sources calls monitor_prepare before it
+    // launches anything (room for a tick of num_samples: a failure changes nothing) and monitor_launch once the tick's planar block
+    // is complete on the stream: `planar` [C][num_samples] starts a device buffer on a 16-byte boundary that holds 32 bytes
+    // more than the block (the kernel's 16-byte loads end past a row's end).  The slot's state, not the analysers': no reset touches it.
+    fx_monitor* monitor = nullptr;
+    fx_status (*monitor_prepare)(fx_context*, int num_samples) = nullptr;
+    fx_status (*monitor_launch)(fx_context*, const void* planar, int num_samples, int sample_format) = nullptr;
+    void      (*monitor_release)(fx_context*) = nullptr;
 };
 
 // The per-track rows (fx_capi.cpp), for the units that change them.  fx_channel_rows: what every track runs with now -- the table's rows,

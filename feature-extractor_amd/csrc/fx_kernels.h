@@ -428,6 +428,10 @@ constexpr int FX_LAUNCH_SOURCES = 15;
 // fx_push_sources while a FILE track has a rated clip loaded: one launch of fx_clip_resample_kernel, the SECOND entry of the call's
 // record, after the gather; T = the samples per track.  A context without such a track records no entry of this kind.
 constexpr int FX_LAUNCH_RESAMPLE = 16;
+// fx_push_sources on a context with the monitor enabled (fx_monitor.hip): the mix of the tick's planar block, after the gather and the
+// resampler and before the entries of fx_push_samples; ONE entry for its one or two launches (fx_monitor_mix_kernel, and
+// fx_monitor_sum_kernel where the context has more than one group of FX_MONITOR_GROUP tracks); T = the samples per track.
+constexpr int FX_LAUNCH_MONITOR = 17;
 struct fx_launch_record {
     int kind;               // FX_LAUNCH_*
     int window, analysers;  // window size, analysers mask (bit 0 spectral, bit 1 harmonic)

@@ -369,9 +369,10 @@ fx_status fx_clear_pending(fx_context* ctx);
  *
  * Deliberate differences from the reference.  JUCE's AudioTransportSource is not part of the reference tree: its fade on stop and
  * its read-ahead buffer are not reproduced, and its sample-rate correction (JUCE's ResamplingAudioSource, absent as well) is
- * replaced by the windowed-sinc resampler specified above, so a rated clip's samples are ours, not JUCE's.  Each track hears its own
- * player only: in the reference every player renders into the sound card's shared output buffers, so tracks playing at once hear
- * each other -- a property of the one device, not carried over.  One-shot playback and FINISHED are ours. */
+ * replaced by the windowed-sinc resampler specified above, so a rated clip's samples are ours, not JUCE's.  Each track's ANALYSERS
+ * hear its own player only: in the reference every player renders into the sound card's shared output buffers, so tracks playing
+ * at once hear each other -- a property of the one device, not carried over.  The shared output itself is the monitor mix (next
+ * section).  One-shot playback and FINISHED are ours. */
 enum { FX_SOURCE_INPUT = 0, FX_SOURCE_FILE = 1 };
 enum { FX_TRANSPORT_NO_FILE = 0, FX_TRANSPORT_PLAYING = 1, FX_TRANSPORT_PAUSED = 2, FX_TRANSPORT_STOPPED = 3, FX_TRANSPORT_FINISHED = 4 };
 enum { FX_PLAY = 0, FX_PAUSE = 1, FX_STOP = 2, FX_RESTART = 3 };
@@ -387,6 +388,58 @@ fx_status fx_transport(fx_context* ctx, const int* channels, int num_channels, i
 fx_status fx_get_transport(fx_context* ctx, int* source, int* state, long long* position, long long* laps);
 fx_status fx_push_sources(fx_context* ctx, const void* live_block, int num_samples, int sample_format, int mem_kind,
                           float* out_raw, float* out_smoothed, int* frames_out);
+
+/* ---- monitor mix: every tick's tracks summed to a stereo output on the GPU ----
+ * The reference's AudioFilePlayer is an AudioSourcePlayer on the device manager (AudioFilePlayer.h:30-34): a file is heard, every
+ * player renders into the sound card's output buffers and the speakers carry the sum of the tracks that play.  The MONITOR is that
+ * output, opt-in: while it is enabled every fx_push_sources tick also mixes the tick's planar block [C][n] down to two output
+ * channels [2][n] of fp32 in device memory, through a per-track SEND table (on / off, left gain, right gain), at the cost of one
+ * more launch record on the context's stream.  A context that never enables it makes exactly the launches it made before; an
+ * enabled context returns exactly the analysis bits it returned before.
+ *
+ *   fx_enable_monitor       enable != 0 makes the monitor: every track's send off with gains 1.0 / 1.0, no tick yet (num_samples 0).
+ *                           enable == 0 frees it.  Enabling an enabled monitor keeps the sends.  Synchronises the stream.  A failed
+ *                           allocation is FX_ERR_OUT_OF_MEMORY and changes nothing.
+ *   fx_set_channel_monitor  a list under fx_reset_channels' rules (host memory, duplicates allowed and the last entry of a track
+ *                           wins, num_channels == 0 is a no-op): on[i] != 0 puts track channels[i] on (on == NULL: every listed
+ *                           track on); left == NULL and / or right == NULL keep that gain.  Every entry is checked before anything
+ *                           changes and before any device use, fx_last_error names the entry: a gain that is NaN or infinite, a
+ *                           track out of range.  Refused without a monitor.  Takes effect in stream order, at the next tick.
+ *   fx_get_channel_monitor  the whole table, [num_channels] each in host memory; any pointer may be NULL.
+ *   fx_get_monitor          copies the last tick's mix: out[0 .. n) is left and out[capacity .. capacity + n) right, n that tick's
+ *                           num_samples, reported in *num_samples.  capacity < n is refused (the error names both numbers, and
+ *                           *num_samples still reports n: a host learns what room to bring).
+ *                           FX_MEM_HOST returns when the bytes are there; FX_MEM_DEVICE needs 4-byte alignment and is
+ *                           asynchronous on the context's stream.  Refused before any device use: a null context, a null out,
+ *                           an unknown memory kind, a context without a monitor.
+ *
+ * THE MIX.  x_c[i] is sample i of track c's row of the tick's planar block, after the gather and, if it ran, the resampler, widened
+ * exactly as the analysis kernels' load stage widens it: f32 as is, f16 the exact float, s16 v / 32768, s24 v / 8388608.  The
+ * collector's gain (fx_set_gain, fx_set_channel_gains) is the analysers' and is NOT applied: the reference's gain slider does not
+ * change what is heard either.  The track groups are g = 0 .. ceil(C / FX_MONITOR_GROUP) - 1, group g holds tracks 64 g .. 64 g + 63.
+ * For each output channel ch with gains gain_ch and each sample i:
+ *   P_g = +0;  for c ascending over group g's tracks whose send is on:  P_g = P_g + (gain_ch[c] * x_c[i])
+ *   out = +0;  for g ascending:                                         out = out + P_g
+ * Every operation is IEEE fp32, round to nearest, none contracted.  A track whose send is off contributes nothing: it is not added
+ * as 0 * x, so an inf or NaN in an off track never reaches the output.  A group with no track on adds +0, which changes no bit (the
+ * accumulators start at +0 and are never -0).  The fixed two-level order makes the result one defined bit pattern whatever the
+ * launch geometry: a flat sequential sum over 65 536 tracks would serialise the kernel, float atomics would make the bits depend
+ * on timing -- there are none.
+ *   What is mixed is whatever the tick gave each track: an INPUT track's live row (so "input monitoring" is turning an INPUT
+ * track's send on), a playing clip, zeros for a FILE track in any other state.  fx_push_samples, fx_push_interleaved, fx_push_hops,
+ * fx_process_frames and the fx_stream_* ring do not feed the monitor, and a tick of num_samples == 0 leaves the last mix alone.
+ * Like the players' table the sends belong to the slot: fx_reset_state and fx_reset_channels leave them, records of
+ * fx_export_channels do not carry them.
+ *   In a tick the mix follows the gather and the resampler and precedes everything fx_push_samples does; whatever can fail (the
+ * partial sums' and the output's memory among it) fails before the gather is launched: a refused tick changes nothing, the
+ * monitor included.  Not here: more than two outputs, a history beyond the last tick, fades, a master gain, tracks hearing each
+ * other's players. */
+#define FX_MONITOR_GROUP 64
+fx_status fx_enable_monitor(fx_context* ctx, int enable);
+fx_status fx_set_channel_monitor(fx_context* ctx, const int* channels, int num_channels, const int* on, const float* left,
+                                 const float* right);
+fx_status fx_get_channel_monitor(fx_context* ctx, int* on, float* left, float* right);
+fx_status fx_get_monitor(fx_context* ctx, float* out, int capacity, int* num_samples, int mem_kind);
 
 /* Same analysis on already assembled windows (the `audioWindow` each run()
  * loop sees, RealTimeAnalyser.h:147,206): frames [num_channels][num_frames]

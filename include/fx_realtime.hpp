@@ -537,7 +537,52 @@ public:
     }
     const std::vector<int>& getTracks() const { return tracks; }
 
+    // ref AudioFilePlayer.h:30-34: the player is an AudioSourcePlayer on the device manager, so the file is HEARD.  Here that is the
+    // context's monitor mix (fx.h, monitor mix): every pushSources tick also sums the tracks whose send is on to a stereo output in
+    // device memory.  The monitor is the context's, the sends are these tracks'; the collector's gain does not change what is heard.
+    void enableMonitor (bool enable = true) { check (fx_enable_monitor (analyser.handle(), enable ? 1 : 0)); }
+    // the set's sends on or off, and -- where given, one per track of the set or one for all -- their left / right gains
+    void setMonitor (bool on, const std::vector<float>& left = std::vector<float>(), const std::vector<float>& right = std::vector<float>())
+    {
+        const std::vector<int> flags (tracks.size(), on ? 1 : 0);
+        const std::vector<float> l = perTrack (left), r = perTrack (right);
+        check (fx_set_channel_monitor (analyser.handle(), tracks.data(), (int) tracks.size(), flags.data(),
+                                       left.empty() ? nullptr : l.data(), right.empty() ? nullptr : r.data()));
+    }
+    struct Sends { std::vector<int> on; std::vector<float> left, right; };                         // one entry per track of the set
+    Sends getMonitorSends() const
+    {
+        const std::size_t all = (std::size_t) analyser.getNumChannels();
+        std::vector<int> on (all);
+        std::vector<float> left (all), right (all);
+        check (fx_get_channel_monitor (analyser.handle(), on.data(), left.data(), right.data()));
+        Sends s;
+        for (int c : tracks) { s.on.push_back (on[(std::size_t) c]); s.left.push_back (left[(std::size_t) c]); s.right.push_back (right[(std::size_t) c]); }
+        return s;
+    }
+    // the last tick's mix of the whole context: `left` and `right` get that tick's samples (what an audio device's output callback
+    // copies into its two channels) -> their number, 0 before the first tick
+    int getMonitor (std::vector<float>& left, std::vector<float>& right) const
+    {
+        int n = 0;
+        float none = 0.0f;
+        const fx_status probe = fx_get_monitor (analyser.handle(), &none, 0, &n, FX_MEM_HOST);      // (no room: refused, the count reported)
+        if (probe != FX_OK && n == 0) check (probe);
+        std::vector<float> both (2 * (std::size_t) n);
+        if (n > 0) check (fx_get_monitor (analyser.handle(), both.data(), n, &n, FX_MEM_HOST));
+        left.assign (both.begin(), both.begin() + n);
+        right.assign (both.begin() + n, both.end());
+        return n;
+    }
+
 private:
+    std::vector<float> perTrack (const std::vector<float>& gains) const
+    {
+        if (! gains.empty() && gains.size() != tracks.size() && gains.size() != 1) throw Error (FX_ERR_INVALID_ARGUMENT, "one gain per track of the player, or one for all");
+        std::vector<float> v (tracks.size(), gains.size() == 1 ? gains[0] : 0.0f);
+        if (gains.size() == tracks.size()) v = gains;
+        return v;
+    }
     void command (int which) { check (fx_transport (analyser.handle(), tracks.data(), (int) tracks.size(), which)); }
     RealTimeBatchAnalyser& analyser;
     std::vector<int> tracks, clipOf;
