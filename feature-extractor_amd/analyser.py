@@ -274,7 +274,7 @@ class BatchAnalyser:
     def last_launches(self):
         """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
         (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events, osc_table,
-        osc_bundle, display, sources, resample, monitor)."""
+        osc_bundle, display, sources, resample, monitor, listen)."""
         cap = capi.LAUNCH_RECORD_CAP
         buf = (ctypes.c_int * (cap * len(capi.LAUNCH_FIELDS)))()
         n = self._lib.fx_last_launches_internal(self._h, buf, cap)
@@ -724,6 +724,24 @@ class BatchAnalyser:
             out = np.empty((2, n.value), np.float32)
             if n.value:
                 capi.check(self._lib.fx_get_monitor(self._h, out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n), capi.MEM_HOST))
+        return out
+
+    # ---- listening tracks: analysers hear the monitor output (include/fx.h, "Listening tracks") ----
+    def set_listen(self, channels, listen):
+        """What the listed tracks' analysers hear from the next tick on: "self" (capi.LISTEN_SELF, the track's own row), "left" or
+        "right" (capi.LISTEN_LEFT / LISTEN_RIGHT: that output of the monitor mix); one value or one per entry.  Of a track listed twice
+        the last entry wins.  The listed tracks' pending samples become zeros, also where nothing changes.  Needs the monitor."""
+        a, ptr = self._track_list(channels)
+        v, vp = self._per_entry(listen, int(a.size), capi.LISTENS)
+        bad = np.flatnonzero((v < capi.LISTEN_SELF) | (v > capi.LISTEN_RIGHT))
+        if bad.size:
+            raise ValueError("entry %d: unknown listen %d (one of %s)" % (int(bad[0]), int(v[bad[0]]), ", ".join(sorted(capi.LISTENS))))
+        capi.check(self._lib.fx_set_channel_listen(self._h, ptr, int(a.size), vp))
+
+    def listens(self):
+        """What every track hears: int32 [C] of capi.LISTEN_*."""
+        out = np.empty(self.num_channels, np.int32)
+        capi.check(self._lib.fx_get_channel_listen(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out
 
     def get_features(self, out=None):

@@ -24,7 +24,8 @@ MAX_UNITS = 24
 LAUNCH_FIELDS = ["kind", "window", "analysers", "T", "direct_state", "block_mode", "num_chunks", "ch_per_wg", "waves_per_ch", "hop_pairs",
                  "ep_T", "out_stride", "ep_form", "reblock"]
 LAUNCH_KINDS = {1: "frame", 2: "frame_tail", 3: "hop", 4: "hop_pair", 5: "pair", 6: "epilogue", 7: "reblock", 8: "osc", 9: "taps",
-                10: "deinterleave", 11: "onset_events", 12: "osc_table", 13: "osc_bundle", 14: "display", 15: "sources", 16: "resample", 17: "monitor"}
+                10: "deinterleave", 11: "onset_events", 12: "osc_table", 13: "osc_bundle", 14: "display", 15: "sources", 16: "resample", 17: "monitor",
+                18: "listen"}
 # file sources (include/fx.h): FX_SOURCE_*, FX_TRANSPORT_*, the fx_transport commands FX_PLAY .. FX_RESTART, FX_CLIP_BORROW
 SOURCE_INPUT, SOURCE_FILE = 0, 1
 TRANSPORT_NO_FILE, TRANSPORT_PLAYING, TRANSPORT_PAUSED, TRANSPORT_STOPPED, TRANSPORT_FINISHED = range(5)
@@ -32,6 +33,8 @@ PLAY, PAUSE, STOP, RESTART = range(4)
 TRANSPORT_COMMANDS = {"play": PLAY, "pause": PAUSE, "stop": STOP, "restart": RESTART}
 CLIP_BORROW = 1
 MONITOR_GROUP = 64                  # FX_MONITOR_GROUP: the tracks whose sends are summed in a row before the groups are
+LISTEN_SELF, LISTEN_LEFT, LISTEN_RIGHT = 0, 1, 2       # FX_LISTEN_*: what a track's analysers hear (fx_set_channel_listen)
+LISTENS = {"self": LISTEN_SELF, "left": LISTEN_LEFT, "right": LISTEN_RIGHT}
 MAX_DISPLAY_LENGTH, MAX_DISPLAY_SAMPLES_PER_BLOCK = 4096, 65536
 MAX_TAP_CHANNELS = 64
 OSC_ADDRESS_MAX = 124               # FX_OSC_ADDRESS_MAX
@@ -109,7 +112,8 @@ def _prototypes():
         ("fx_set_channel_sources", [vp, ip, i, ip], st), ("fx_transport", [vp, ip, i, i], st), ("fx_get_transport", [vp, ip, ip, llp, llp], st),
         ("fx_push_sources", [vp, vp, i, i, i, vp, vp, ip], st),
         ("fx_enable_monitor", [vp, i], st), ("fx_set_channel_monitor", [vp, ip, i, ip, fp, fp], st), ("fx_get_channel_monitor", [vp, ip, fp, fp], st),
-        ("fx_get_monitor", [vp, vp, i, ip, i], st), ("fx_process_frames", [vp, vp, i, i, i, vp, vp], st),
+        ("fx_get_monitor", [vp, vp, i, ip, i], st), ("fx_set_channel_listen", [vp, ip, i, ip], st), ("fx_get_channel_listen", [vp, ip], st),
+        ("fx_process_frames", [vp, vp, i, i, i, vp, vp], st),
         ("fx_get_smoothed", [vp, vp, i], st), ("fx_host_alloc", [vpp, ctypes.c_size_t], st), ("fx_host_free", [vp], st),
         ("fx_sync", [vp], st), ("fx_get_stream", [vp, vpp], st), ("fx_last_kernel_ms", [vp, fp, fp], st),
         ("fx_request_taps", [vp, ip, i], st), ("fx_get_taps", [vp, i, fp, fp, fp, fp, fp, fp, llp], st),

@@ -888,8 +888,9 @@ fx_status fx_push_sources(fx_context* c, const void* live_block, int num_samples
     }
     // (the last piece is stored whole; 32 bytes behind it for the monitor's loads: fx_context.h, monitor_launch)
     if ((st = fx_grow(&s->d_planar, &s->planar_cap, ((planar_bytes + 15) & ~(size_t) 15) + 32)) != FX_OK) return st;
-    // (the monitor's room before the gather moves the players on: a tick it cannot mix is refused with nothing changed)
-    if (c->monitor_prepare && (st = c->monitor_prepare(c, num_samples)) != FX_OK) return st;
+    // (the monitor's room, and its listeners' fp32, before the gather moves the players on: a tick it cannot mix is refused with
+    // nothing changed)
+    if (c->monitor_prepare && (st = c->monitor_prepare(c, num_samples, sample_format)) != FX_OK) return st;
     fxk::GatherParams p;
     p.rows = s->d_rows[s->cur];
     p.next = s->d_rows[s->cur ^ 1];
@@ -906,7 +907,8 @@ fx_status fx_push_sources(fx_context* c, const void* live_block, int num_samples
         if (fx_launch_record* r = note_launch(c, FX_LAUNCH_RESAMPLE, 0)) r->T = num_samples;
         HIP_TRY(fxk::launch_clip_resample_kernel(rp, c->stream));
     }
-    // what every track plays is complete: the monitor (fx_monitor.hip) hears it before the analysers do
+    // what every track plays is complete: the monitor (fx_monitor.hip) hears it before the analysers do, and the tracks that listen
+    // to its output get the mix in place of their own row
     if (c->monitor_launch && (st = c->monitor_launch(c, s->d_planar, num_samples, sample_format)) != FX_OK) return st;
     int frames = 0;
     st = fx_push_block(c, s->d_planar, num_samples, sample_format, FX_MEM_DEVICE, mem_kind, out_raw, out_smoothed, &frames, true);

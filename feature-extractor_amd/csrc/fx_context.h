@@ -208,9 +208,11 @@ struct fx_context {
     // launches anything (room for a tick of num_samples: a failure changes nothing) and monitor_launch once the tick's planar block
     // is complete on the stream: `planar` [C][num_samples] starts a device buffer on a 16-byte boundary that holds 32 bytes
     // more than the block (the kernel's 16-byte loads end past a row's end).  The slot's state, not the analysers': no reset touches it.
+    // monitor_prepare also refuses a tick that is not fp32 while a track listens to an output, and monitor_launch WRITES `planar`:
+    // the rows of the tracks that listen (fx_set_channel_listen) become the mix before the analysers read them.
     fx_monitor* monitor = nullptr;
-    fx_status (*monitor_prepare)(fx_context*, int num_samples) = nullptr;
-    fx_status (*monitor_launch)(fx_context*, const void* planar, int num_samples, int sample_format) = nullptr;
+    fx_status (*monitor_prepare)(fx_context*, int num_samples, int sample_format) = nullptr;
+    fx_status (*monitor_launch)(fx_context*, void* planar, int num_samples, int sample_format) = nullptr;
     void      (*monitor_release)(fx_context*) = nullptr;
 };
 

@@ -432,6 +432,9 @@ constexpr int FX_LAUNCH_RESAMPLE = 16;
 // resampler and before the entries of fx_push_samples; ONE entry for its one or two launches (fx_monitor_mix_kernel, and
 // fx_monitor_sum_kernel where the context has more than one group of FX_MONITOR_GROUP tracks); T = the samples per track.
 constexpr int FX_LAUNCH_MONITOR = 17;
+// fx_push_sources while a track listens to a monitor output (fx_set_channel_listen): one launch of fx_monitor_listen_kernel, the entry
+// directly after the monitor's; T = the samples per track.  A context in which no track listens records no entry of this kind.
+constexpr int FX_LAUNCH_LISTEN = 18;
 struct fx_launch_record {
     int kind;               // FX_LAUNCH_*
     int window, analysers;  // window size, analysers mask (bit 0 spectral, bit 1 harmonic)

@@ -11,6 +11,11 @@
 // group's partial rows P[g][ch][i]; fx_monitor_sum_kernel, a thread per (ch, i), adds the groups' rows in order.  A context of one
 // group writes its partial rows straight to the output and launches no second kernel.
 //
+// LISTENING TRACKS (include/fx.h, "Listening tracks"; ref AudioDataCollector.h:42,53: a file track's collectors copy one channel of the
+// device's OUTPUT buffer).  Once the mix is complete fx_monitor_listen_kernel copies an output row over the row of every track that
+// listens to it, a wavefront per (listener, tile of samples), so the analysers that follow read the mix.  The mix was formed from
+// every track's own row before, so nothing feeds back.  A context in which no track listens never launches it.
+//
 // Nothing in the shim's host units (build.py, HOST_SOURCES) refers to this unit: fx_enable_monitor installs the context's hooks.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -41,7 +46,7 @@ static_assert(FX_MONITOR_GROUP == 64, "a group's 64 sends are walked by one wave
 struct __attribute__((aligned(16))) MonitorSend {
     int   on;
     float left, right;
-    int   pad;
+    int   listen;       // FX_LISTEN_*: what the track's analysers hear.  The host's column is the truth; the kernels walk ListenEntry
 };
 static_assert(sizeof(MonitorSend) == 16, "a send is one 16-byte piece");
 
@@ -195,6 +200,74 @@ fx_monitor_sum_kernel(const float* __restrict__ part, float* __restrict__ out, i
     out[e] = acc;
 }
 
+} // namespace
+
+// (outside the unnamed namespace: tools/kernel_resources.py names the kernel in DESIGN.md's table of registers)
+// A track that listens, and the output row it hears (0 left, 1 right).  The device's list is COMPACT: a context of 65 536 tracks with two
+// listeners -- the reference's own case -- reads 16 bytes of it, not the 1 MB of its send table.
+struct ListenEntry { int track, output; };
+
+struct ListenParams {
+    const ListenEntry* list;    // [count]
+    const float*       mix;     // [2][stride]: the tick's mix, complete on the stream
+    float*             planar;  // the tick's planar fp32 block [C][n]
+    int                n, stride, tiles, count;
+};
+
+constexpr int LISTEN_THREADS = 64;      // one wavefront, lanes along the samples
+constexpr int LISTEN_QUADS = 2;         // 16-byte pieces a lane moves, both loads in flight before the first store
+constexpr int LISTEN_TILE = LISTEN_THREADS * 4 * LISTEN_QUADS;     // 512 samples: a 441- / 480- / 512-sample tick is one wavefront a listener
+
+typedef quad __attribute__((address_space(1)))* GlobalQuadOut;
+
+// Workgroup (one wavefront) w copies samples [tile * 512, +512) of output row list[w / tiles].output over row list[w / tiles].track of
+// the planar block, bit for bit (the words move as unsigned: a NaN keeps its payload).  Piece j of lane l is the four samples from
+// tile * 512 + j * 256 + 4 l on: a wavefront's loads and stores are 1 KB of consecutive addresses.  The source row starts on a 32-byte
+// boundary (stride is a multiple of 8), so a piece is one aligned 16-byte load, also where the row ends inside it: the padding up to
+// `stride` is allocated, read and not stored.  The destination row starts at track * n floats -- a dword boundary and no more when
+// n % 4 != 0 -- so a piece is stored as four dwords from a dword boundary (`quad`), and the n % 4 samples of the tail one dword at a
+// time: nothing is stored past the row's end, where the next track's row begins.  Every offset is 64-bit (65 536 tracks x 8193 samples
+// x 4 bytes pass 2^31).  The entry is the same in every lane: it arrives through the scalar cache.
+__global__ void __launch_bounds__(LISTEN_THREADS)
+fx_monitor_listen_kernel(const ListenParams p)
+{
+    const unsigned w = blockIdx.x / (unsigned) p.tiles, tile = blockIdx.x % (unsigned) p.tiles;
+    const ListenEntry e = p.list[w];
+    const unsigned* src = reinterpret_cast<const unsigned*>(p.mix) + (size_t) e.output * (size_t) p.stride;
+    unsigned* dst = reinterpret_cast<unsigned*>(p.planar) + (size_t) e.track * (size_t) p.n;
+    const long long i0 = (long long) tile * LISTEN_TILE + (long long) threadIdx.x * 4;
+    uint4 v[LISTEN_QUADS];
+#pragma unroll
+    for (int j = 0; j < LISTEN_QUADS; j++) {
+        const long long i = i0 + (long long) j * (LISTEN_THREADS * 4);
+        v[j] = i < p.n ? *reinterpret_cast<const uint4*>(src + i) : uint4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int j = 0; j < LISTEN_QUADS; j++) {
+        const long long i = i0 + (long long) j * (LISTEN_THREADS * 4);
+        if (i + 4 <= p.n) {
+            *(GlobalQuadOut) (dst + i) = quad{v[j].x, v[j].y, v[j].z, v[j].w};
+        } else if (i < p.n) {
+            const int left = (int) (p.n - i);       // 1 .. 3
+            dst[i] = v[j].x;
+            if (left > 1) dst[i + 1] = v[j].y;
+            if (left > 2) dst[i + 2] = v[j].z;
+        }
+    }
+}
+
+namespace {
+
+hipError_t launch_listen_kernel(ListenParams p, hipStream_t stream)
+{
+    if (p.n <= 0 || p.count <= 0) return hipSuccess;
+    p.tiles = (p.n + LISTEN_TILE - 1) / LISTEN_TILE;
+    const long long wgs = (long long) p.count * p.tiles;
+    if (wgs > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fx_monitor_listen_kernel, dim3((unsigned) wgs), dim3(LISTEN_THREADS), 0, stream, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_monitor_kernels(MixParams p, float* part, float* out, int sample_format, hipStream_t stream)
 {
     if (p.n <= 0 || p.C <= 0) return hipSuccess;
@@ -230,6 +303,11 @@ struct fx_monitor {
     float*                        d_out = nullptr;      // [2][stride]: the last tick's mix
     size_t                        part_cap = 0, out_cap = 0;    // bytes
     int                           n = 0, stride = 0;    // the last tick's samples and its rows' stride; n == 0: no tick yet
+    // the tracks whose listen (sends[t].listen) is not FX_LISTEN_SELF, ascending: on the host, and the same in device memory, [C]
+    // entries allocated with the monitor (a setter never reallocates under ticks in flight) and copied in stream order by the
+    // setter.  A tick's launch takes the host's count as an argument: list and count agree at every point of the stream.
+    fxk::ListenEntry*             d_listen = nullptr;
+    std::vector<fxk::ListenEntry> listeners;
 };
 
 namespace {
@@ -238,7 +316,7 @@ void monitor_release(fx_context* c)
 {
     fx_monitor* m = c->monitor;
     if (!m) return;
-    void* bufs[] = {m->d_sends, m->d_part, m->d_out};
+    void* bufs[] = {m->d_sends, m->d_part, m->d_out, m->d_listen};
     for (void* b : bufs) if (b) (void) hipFree(b);
     delete m;
     c->monitor = nullptr;
@@ -248,10 +326,13 @@ int stride_of(int num_samples) { return (int) (((long long) num_samples + 7) & ~
 
 // room for a tick of num_samples, before fx_push_sources launches anything.  A tick that needs more room than the last one replaces
 // the last mix anyway; if the larger buffer cannot be had, the old one is gone with it (fx_grow) and the monitor holds no tick.
-fx_status monitor_prepare(fx_context* c, int num_samples)
+fx_status monitor_prepare(fx_context* c, int num_samples, int sample_format)
 {
     fx_monitor* m = c->monitor;
     if (!m || num_samples <= 0) return FX_OK;
+    // the mix is fp32 and a listener's row becomes the mix (the rule of rated clips, fx_push_sources)
+    if (!m->listeners.empty() && sample_format != FX_SAMPLE_F32)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "track %d listens to the monitor's output, which is fp32: this call is in sample format %d", m->listeners[0].track, sample_format);
     const size_t row = (size_t) stride_of(num_samples) * sizeof(float);
     const int groups = (c->C + FX_MONITOR_GROUP - 1) / FX_MONITOR_GROUP;
     fx_status st = FX_OK;
@@ -264,7 +345,7 @@ fx_status monitor_prepare(fx_context* c, int num_samples)
 }
 
 // the tick's planar block is complete on the stream (fx_context.h states what `planar` must be)
-fx_status monitor_launch(fx_context* c, const void* planar, int num_samples, int sample_format)
+fx_status monitor_launch(fx_context* c, void* planar, int num_samples, int sample_format)
 {
     fx_monitor* m = c->monitor;
     if (!m || num_samples <= 0) return FX_OK;
@@ -280,6 +361,11 @@ fx_status monitor_launch(fx_context* c, const void* planar, int num_samples, int
     HIP_TRY(fxk::launch_monitor_kernels(p, m->d_part, m->d_out, sample_format, c->stream));
     m->n = num_samples;
     m->stride = p.stride;
+    if (m->listeners.empty()) return FX_OK;
+    // the mix is complete on the stream: the listeners' rows become it before the analysers read them (fp32: monitor_prepare)
+    const fxk::ListenParams lp{m->d_listen, m->d_out, static_cast<float*>(planar), num_samples, p.stride, 0, (int) m->listeners.size()};
+    if (fx_launch_record* r = note_launch(c, FX_LAUNCH_LISTEN, 0)) r->T = num_samples;
+    HIP_TRY(fxk::launch_listen_kernel(lp, c->stream));
     return FX_OK;
 }
 
@@ -291,6 +377,9 @@ fx_status fx_enable_monitor(fx_context* c, int enable)
 {
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
     if (!enable && !c->monitor) return FX_OK;
+    // (fx_destroy_clips' rule for loaded clips: what a track still uses is not freed under it)
+    if (!enable && !c->monitor->listeners.empty())
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "track %d listens to the monitor's output (fx_set_channel_listen)", c->monitor->listeners[0].track);
     { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess || n < 1) { (void) hipGetLastError(); return fx_fail(FX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)"); } }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));        // ticks in flight write the monitor that is about to go; copies in flight read it
@@ -305,21 +394,24 @@ fx_status fx_enable_monitor(fx_context* c, int enable)
     fx_monitor* m = new (std::nothrow) fx_monitor();
     if (!m) return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
     try {
-        m->sends.assign((size_t) c->C, fxk::MonitorSend{0, 1.0f, 1.0f, 0});
+        m->sends.assign((size_t) c->C, fxk::MonitorSend{0, 1.0f, 1.0f, FX_LISTEN_SELF});
     } catch (const std::bad_alloc&) {
         delete m;
         return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
     }
     const size_t bytes = m->sends.size() * sizeof(fxk::MonitorSend);
-    void* q = nullptr;
+    void *q = nullptr, *ql = nullptr;
     hipError_t e = hipMalloc(&q, bytes);
     if (e == hipSuccess) e = hipMemcpy(q, m->sends.data(), bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&ql, (size_t) c->C * sizeof(fxk::ListenEntry));
     if (e != hipSuccess) {
         if (q) (void) hipFree(q);
+        if (ql) (void) hipFree(ql);
         delete m;
         return fx_fail(e == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "allocating the send table failed: %s", hipGetErrorString(e));
     }
     m->d_sends = static_cast<fxk::MonitorSend*>(q);
+    m->d_listen = static_cast<fxk::ListenEntry*>(ql);
     c->monitor = m;
     c->monitor_prepare = monitor_prepare;
     c->monitor_launch = monitor_launch;
@@ -379,6 +471,59 @@ fx_status fx_get_channel_monitor(fx_context* c, int* on, float* left, float* rig
         if (left) left[t] = s.left;
         if (right) right[t] = s.right;
     }
+    return FX_OK;
+}
+
+fx_status fx_set_channel_listen(fx_context* c, const int* channels, int num_channels, const int* listen)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    if (num_channels < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative channel count %d", num_channels);
+    if (num_channels > 0 && !channels) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null channel list with %d entries", num_channels);
+    if (num_channels > 0 && !listen) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null listen list with %d entries", num_channels);
+    // the call's own values, then the range of its entries (fx_set_channel_monitor's order)
+    for (int i = 0; i < num_channels; i++)
+        if (listen[i] != FX_LISTEN_SELF && listen[i] != FX_LISTEN_LEFT && listen[i] != FX_LISTEN_RIGHT)
+            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: unknown listen %d", i, listen[i]);
+    for (int i = 0; i < num_channels; i++)
+        if (channels[i] < 0 || channels[i] >= c->C)
+            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: channel %d out of range [0,%d)", i, channels[i], c->C);
+    fx_monitor* m = c->monitor;
+    if (!m) return fx_fail(FX_ERR_INVALID_ARGUMENT, "the monitor is not enabled on this context (fx_enable_monitor)");
+    if (num_channels == 0) return FX_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    // the column as it will be (in list order: the last entry of a track wins) and its compact list, made beside the ones in force:
+    // a failed call changes nothing.  The copy reads the monitor's own list, which lives as long as the monitor.
+    std::vector<int> column;
+    std::vector<fxk::ListenEntry> next;
+    try {
+        column.resize((size_t) c->C);
+        for (int t = 0; t < c->C; t++) column[(size_t) t] = m->sends[(size_t) t].listen;
+        for (int i = 0; i < num_channels; i++) column[(size_t) channels[i]] = listen[i];
+        for (int t = 0; t < c->C; t++)
+            if (column[(size_t) t] != FX_LISTEN_SELF) next.push_back(fxk::ListenEntry{t, column[(size_t) t] - FX_LISTEN_LEFT});
+    } catch (const std::bad_alloc&) {
+        return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    }
+    m->listeners.swap(next);
+    if (!m->listeners.empty()) {
+        const hipError_t e = hipMemcpyAsync(m->d_listen, m->listeners.data(), m->listeners.size() * sizeof(fxk::ListenEntry), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) {
+            m->listeners.swap(next);
+            return fx_fail(FX_ERR_HIP, "copying the listeners failed: %s", hipGetErrorString(e));
+        }
+    }
+    for (int t = 0; t < c->C; t++) m->sends[(size_t) t].listen = column[(size_t) t];
+    // toggleCollectInput clears the collector whichever way it is switched (ref AudioDataCollector.h:119)
+    return fx_clear_pending_channels(c, channels, num_channels);
+}
+
+fx_status fx_get_channel_listen(fx_context* c, int* listen)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    if (!listen) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null output pointer");
+    const fx_monitor* m = c->monitor;
+    if (!m) return fx_fail(FX_ERR_INVALID_ARGUMENT, "the monitor is not enabled on this context (fx_enable_monitor)");
+    for (int t = 0; t < c->C; t++) listen[t] = m->sends[(size_t) t].listen;
     return FX_OK;
 }
 

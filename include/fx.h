@@ -369,10 +369,10 @@ fx_status fx_clear_pending(fx_context* ctx);
  *
  * Deliberate differences from the reference.  JUCE's AudioTransportSource is not part of the reference tree: its fade on stop and
  * its read-ahead buffer are not reproduced, and its sample-rate correction (JUCE's ResamplingAudioSource, absent as well) is
- * replaced by the windowed-sinc resampler specified above, so a rated clip's samples are ours, not JUCE's.  Each track's ANALYSERS
- * hear its own player only: in the reference every player renders into the sound card's shared output buffers, so tracks playing
- * at once hear each other -- a property of the one device, not carried over.  The shared output itself is the monitor mix (next
- * section).  One-shot playback and FINISHED are ours. */
+ * replaced by the windowed-sinc resampler specified above, so a rated clip's samples are ours, not JUCE's.  By default each track's
+ * ANALYSERS hear its own player; in the reference every player renders into the sound card's shared output buffers and a file
+ * track's collectors read one channel of those.  The shared output is the monitor mix (next section), and a track is told to hear
+ * it with fx_set_channel_listen ("Listening tracks" there).  One-shot playback and FINISHED are ours. */
 enum { FX_SOURCE_INPUT = 0, FX_SOURCE_FILE = 1 };
 enum { FX_TRANSPORT_NO_FILE = 0, FX_TRANSPORT_PLAYING = 1, FX_TRANSPORT_PAUSED = 2, FX_TRANSPORT_STOPPED = 3, FX_TRANSPORT_FINISHED = 4 };
 enum { FX_PLAY = 0, FX_PAUSE = 1, FX_STOP = 2, FX_RESTART = 3 };
@@ -432,14 +432,57 @@ fx_status fx_push_sources(fx_context* ctx, const void* live_block, int num_sampl
  * fx_export_channels do not carry them.
  *   In a tick the mix follows the gather and the resampler and precedes everything fx_push_samples does; whatever can fail (the
  * partial sums' and the output's memory among it) fails before the gather is launched: a refused tick changes nothing, the
- * monitor included.  Not here: more than two outputs, a history beyond the last tick, fades, a master gain, tracks hearing each
- * other's players. */
+ * monitor included.  Not here: more than two outputs, a history beyond the last tick, fades, a master gain.  Tracks hearing each
+ * other's players: "Listening tracks", below.
+ *
+ * LISTENING TRACKS.  Switching a track of the reference to "audio file" calls toggleCollectInput (false) on both of its collectors
+ * (AnalyserTrackController.h:92-107): from then on audioDeviceIOCallback copies outputChannelData[channelToCollect], not the input
+ * (AudioDataCollector.h:42,53), with the collector's gain applied on the way in as always (:88).  A file track's analysers never
+ * read their own player: they read one channel of the device's output buffer, the sum of every player.  Here a track is told to
+ * LISTEN to the left or the right monitor output, and its analysers, taps, display, onset events and pending samples see what
+ * those collectors would see; no sample leaves device memory on the way.
+ *
+ *   fx_set_channel_listen   a list under fx_set_channel_monitor's rules (host memory, duplicates allowed and the last entry of a
+ *                           track wins, num_channels == 0 is a no-op): track channels[i] hears listen[i], FX_LISTEN_SELF (its own
+ *                           row, the default), FX_LISTEN_LEFT or FX_LISTEN_RIGHT.  Every entry is checked before anything changes
+ *                           and before any device use, fx_last_error names the entry.  Refused: a null context, a negative count,
+ *                           a null list, a null `listen`, a value outside {0, 1, 2}, a track out of range, a context without a
+ *                           monitor.  Takes effect in stream order, at the next tick.  Zeroes the listed tracks' pending samples
+ *                           (fx_clear_pending_channels), also where the value does not change: toggleCollectInput clears the
+ *                           collector whichever way it is switched (AudioDataCollector.h:119).
+ *   fx_get_channel_listen   the whole column, [num_channels] in host memory.  Refused: a null context, a null `listen`, a context
+ *                           without a monitor.
+ *
+ *   1. Where a listen lives.  It is a column of the send table, FX_LISTEN_SELF when the monitor is made.  Like the sends it belongs
+ * to the slot: fx_reset_state, fx_reset_channels and fx_export_channels / fx_import_channels neither touch nor carry it.
+ *   2. fx_enable_monitor (ctx, 0) is refused with FX_ERR_INVALID_ARGUMENT, naming the first such track, while any track listens to
+ * an output, and changes nothing -- the rule fx_destroy_clips applies to loaded clips.  Disabling a monitor nobody listens to
+ * behaves as before.
+ *   3. The tick.  For every track c with listen != FX_LISTEN_SELF, row c of the tick's planar block becomes the mix:
+ * planar[c][i] = out[listen - 1][i] for 0 <= i < n, bit for bit -- a NaN or inf in the mix is heard as it is.  This happens after the
+ * mix and the groups' sum and before anything fx_push_samples would do.  The mix is formed from every track's OWN row first (live
+ * row, clip, resampler output or silence): a listening track's send still contributes its own source, nothing feeds back, and the
+ * mix of a tick is the same bits whether anybody listens or not.  No byte of a non-listening track's row changes.  Everything
+ * downstream equals fx_push_samples on that modified block: the load stage with the track's collector gain, taps, display, onset
+ * events, pending samples.
+ *   4. Sample format.  The mix is fp32: while any track listens an fx_push_sources tick must be FX_SAMPLE_F32; any other is refused
+ * before any launch, naming the first listening track, and changes nothing (the rule of rated clips).  A tick of num_samples == 0
+ * does nothing.
+ *   5. Launches.  A context in which no track listens makes exactly the launches it made before.  With a listener a tick makes one
+ * more, directly after the monitor's.
+ *   6. Ticks only.  fx_push_samples, fx_push_interleaved, fx_push_hops, fx_process_frames and the fx_stream_* ring do not consult the
+ * listens.
+ *   7. A documented difference: -0.  With one send on at gains (1, 0), a track listening FX_LISTEN_LEFT hears its own player, except
+ * that a -0 sample arrives as +0: the accumulators start at +0, and +0 + -0 is +0. */
 #define FX_MONITOR_GROUP 64
+enum { FX_LISTEN_SELF = 0, FX_LISTEN_LEFT = 1, FX_LISTEN_RIGHT = 2 };
 fx_status fx_enable_monitor(fx_context* ctx, int enable);
 fx_status fx_set_channel_monitor(fx_context* ctx, const int* channels, int num_channels, const int* on, const float* left,
                                  const float* right);
 fx_status fx_get_channel_monitor(fx_context* ctx, int* on, float* left, float* right);
 fx_status fx_get_monitor(fx_context* ctx, float* out, int capacity, int* num_samples, int mem_kind);
+fx_status fx_set_channel_listen(fx_context* ctx, const int* channels, int num_channels, const int* listen);
+fx_status fx_get_channel_listen(fx_context* ctx, int* listen);   /* [num_channels], host */
 
 /* Same analysis on already assembled windows (the `audioWindow` each run()
  * loop sees, RealTimeAnalyser.h:147,206): frames [num_channels][num_frames]

@@ -461,7 +461,8 @@ private:
 // one launch per command instead of one per track.  The audio itself moves in AudioDataCollector::pushSources, once per tick for the
 // whole context.  As in the reference the transport buttons clear the tracks' collectors (play, pause, stop; not restart), and
 // restart keeps the state (AudioFilePlayer.h:65).  Differences from the reference are those fx.h lists: no fade, a resampler of our own,
-// each track hears its own player only; one-shot playback (setLooping (false)) ends in FX_TRANSPORT_FINISHED.
+// a track hears its own player until it is told to listen to the monitor output (toggleCollectInput); one-shot playback
+// (setLooping (false)) ends in FX_TRANSPORT_FINISHED.
 class AudioFilePlayer
 {
 public:
@@ -573,6 +574,39 @@ public:
         left.assign (both.begin(), both.begin() + n);
         right.assign (both.begin() + n, both.end());
         return n;
+    }
+
+    // ref AudioDataCollector.h:42,53,119 (fx.h, listening tracks): the set's analysers hear their own rows (FX_LISTEN_SELF) or one
+    // output of the monitor mix (FX_LISTEN_LEFT / FX_LISTEN_RIGHT), from the next tick on; the collectors are cleared either way.
+    // Needs the monitor (enableMonitor).
+    void setListen (int output)
+    {
+        const std::vector<int> listen (tracks.size(), output);
+        check (fx_set_channel_listen (analyser.handle(), tracks.data(), (int) tracks.size(), listen.data()));
+    }
+    std::vector<int> getListens() const                                                             // one entry per track of the set
+    {
+        std::vector<int> all ((std::size_t) analyser.getNumChannels()), mine;
+        check (fx_get_channel_listen (analyser.handle(), all.data()));
+        for (int c : tracks) mine.push_back (all[(std::size_t) c]);
+        return mine;
+    }
+    // What the reference's source-type callback does (AnalyserTrackController.h:92-107).  true: the tracks collect the audio device's
+    // input -- their source is the input (which stops their players) and they hear their own rows.  false: their source is the file
+    // and, as the reference's collectors do from then on, they hear channel `outputChannel` (0 left, 1 right) of the device's output,
+    // the monitor mix.  A context without a monitor can only go to the input.
+    void toggleCollectInput (bool shouldCollectInput, int outputChannel = 0)
+    {
+        if (! shouldCollectInput && outputChannel != 0 && outputChannel != 1) throw Error (FX_ERR_INVALID_ARGUMENT, "the monitor has output channels 0 and 1");
+        if (! shouldCollectInput)
+        {
+            setListen (outputChannel == 0 ? FX_LISTEN_LEFT : FX_LISTEN_RIGHT);                       // (refused without a monitor, before the source changes)
+            setFileSource (true);
+            return;
+        }
+        setFileSource (false);
+        std::vector<int> all ((std::size_t) analyser.getNumChannels());
+        if (fx_get_channel_listen (analyser.handle(), all.data()) == FX_OK) setListen (FX_LISTEN_SELF);     // (no monitor: nobody listens)
     }
 
 private:

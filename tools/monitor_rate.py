@@ -44,14 +44,14 @@ def _library(path):
 class Playing:
     """a context of `lib` whose C tracks each loop their own clip of CLIP fp32 samples from one borrowed bank, through the C ABI alone"""
 
-    def __init__(self, torch, lib, C, seed, monitor=False):
+    def __init__(self, torch, lib, C, seed, monitor=False, window=WINDOW, clip=CLIP):
         self.lib, self.C, self.h = lib, C, ctypes.c_void_p()
-        self.check(lib.fx_create(ctypes.byref(self.h), 0, C, WINDOW, 48000.0, 0))
+        self.check(lib.fx_create(ctypes.byref(self.h), 0, C, window, 48000.0, 0))
         g = torch.Generator(device="cuda").manual_seed(seed)
-        self.bank = (torch.rand((C * CLIP,), generator=g, device="cuda") - 0.5) * 0.5
+        self.bank = (torch.rand((C * clip,), generator=g, device="cuda") - 0.5) * 0.5
         ints = lambda v: (ctypes.c_int * len(v))(*v)                                           # noqa: E731
         first = ctypes.c_int(-1)
-        lengths = (ctypes.c_longlong * C)(*([CLIP] * C))
+        lengths = (ctypes.c_longlong * C)(*([clip] * C))
         self.check(lib.fx_create_clips(self.h, ctypes.c_void_p(self.bank.data_ptr()), lengths, C, capi.SAMPLE_F32, capi.MEM_DEVICE, capi.CLIP_BORROW, ctypes.byref(first)))
         tracks = ints(list(range(C)))
         self.check(lib.fx_set_channel_clips(self.h, tracks, C, ints([first.value + k for k in range(C)]), None))
