@@ -736,9 +736,31 @@ FX_MARK("spec_pass2");
                 }
                 const double wm = b1 + 0.5 * mag_sum, s2b0 = (b2 + b1 + 0.25 * mag_sum) * mag_sum, ww = wm * wm;
                 const bool refine = accepted && (!(s2b0 - ww > 1e-9 * ww) || !(s2b0 < __builtin_huge_val()));
+                // the centroid on a tie between two floats (fx_wave.hip.h, centroid_near_tie): the reference's serial sums (:86, :95)
+                // redone in its order, the running values handed from lane to lane (rare, like harmonic_tail's)
+                int cstep = 0;
+                if (wave_ballot(accepted && centroid_near_tie(frpb * wm, mag_sum))) {
+                    double run_w = 0.0, run_m = 0.0;                           // (one sum at a time: the registers are full here)
+                    for (int l = 0; l < 64; l++) {
+                        double mine = run_m;
+#pragma unroll
+                        for (int j = 0; j < U; j++) { const double v = (double) re[j]; mine += v * v; }
+                        run_m = lane_get(mine, l);
+                    }
+                    for (int l = 0; l < 64; l++) {
+                        double mine = run_w;
+#pragma unroll
+                        for (int j = 0; j < U; j++) {
+                            const double v = (double) re[j];
+                            mine += ((double) (U * lane + j) * frpb + (frpb / 2.0)) * (v * v);
+                        }
+                        run_w = lane_get(mine, l);
+                    }
+                    cstep = __builtin_amdgcn_readfirstlane(centroid_step((float) (run_w / run_m), (float) ((frpb * wm) / mag_sum)));
+                }
                 double direct = 0.0;
                 if (refine) {
-                    const float centroid = (float) ((frpb * wm) / mag_sum);    // :95, :127
+                    const float centroid = centroid_stepped((float) ((frpb * wm) / mag_sum), cstep);    // :95, :127
                     const double cn = (double) centroid * rnyq;
 #pragma unroll
                     for (int j = 0; j < U; j++) {
@@ -748,7 +770,7 @@ FX_MARK("spec_pass2");
                     }
                 }
                 wave_sum4(lane, flux, vsum, flat_sum, direct);                 // one reduction for everything that is only recorded
-                if (lane == 0) { fpl->var = direct; fpl->refined = refine ? 1 : 0; fpl->vsum = vsum; }
+                if (lane == 0) { fpl->var = direct; fpl->refined = (refine ? SPREAD_REFINED : 0) | cstep; fpl->vsum = vsum; }
             }
             double max_e = (double) maxabs;                                    // :153
             if (max_mag > max_e) max_e = max_mag;                              // :161-162

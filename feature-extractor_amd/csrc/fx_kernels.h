@@ -37,7 +37,8 @@ struct FramePart {
     float  cnt;         // numMagnitudesUsedInFlatnessCalculation
     float  lag;         // ref PitchAnalyser.h:188-189
     int    flags;       // bit 0: harmonic analyser ran past the 0.005 gate  (ref HarmonicCharacteristics.h:88)
-    int    refined;     // `var` holds the reference's own sum (the moment form was not trustworthy for this frame, or the pair kernel summed it)
+    int    refined;     // bit 0: `var` holds the reference's own sum (the moment form was not trustworthy for this frame, or the pair kernel
+                        // summed it); bits 1, 2: the centroid is the float above / below the moments' (fx_wave.hip.h, CENTROID_UP / _DOWN)
 };
 static_assert(sizeof(FramePart) == 128, "one 128-byte line per frame");
 

@@ -619,7 +619,38 @@ FX_MARK("p_flat");
         // second pass over the lane's bins: sum (mag - mean)^2 for the slope (:182-188) and, if the moment form of the
         // spread is not trustworthy (see FrameWave::spectral), the reference's own sum
 FX_MARK("p_pass2");
-        const float centroid = (float) (wsum / mag_sum);                       // :127
+        // the centroid on a tie between two floats (fx_wave.hip.h, centroid_near_tie): the reference's serial sums (:86, :95) redone in
+        // its order, lane to lane, wave 0 then wave 1 (both waves hold the same totals and take the same branch; rare)
+        int cstep = 0;
+        if (accepted && centroid_near_tie(wsum, mag_sum)) {
+            auto serial_sums = [&](double& run_w, double& run_m) {
+                for (int l = 0; l < 64; l++) {
+                    double mine_w = run_w, mine_m = run_m;
+#pragma unroll
+                    for (int j = 0; j < U2; j++) {
+                        const double v = (double) re[j];
+                        const double mag = v * v;
+                        mine_m += mag;
+                        mine_w += ((double) (U2 * gl + j) * frpb + (frpb / 2.0)) * mag;
+                    }
+                    run_w = lane_get(mine_w, l);
+                    run_m = lane_get(mine_m, l);
+                }
+            };
+            double run_w = 0.0, run_m = 0.0;
+            if (w == 0) { serial_sums(run_w, run_m); if (lane == 0) { double* s = slot(0, 0); s[0] = run_w; s[1] = run_m; } }
+            pair_sync(lane);
+            if (w == 1) {
+                run_w = slot(0, 0)[0]; run_m = slot(0, 0)[1];
+                serial_sums(run_w, run_m);
+                if (lane == 0) { double* s = slot(1, 0); s[0] = run_w; s[1] = run_m; }
+            }
+            pair_sync(lane);
+            run_w = slot(1, 0)[0]; run_m = slot(1, 0)[1];
+            next_exchange();
+            cstep = __builtin_amdgcn_readfirstlane(centroid_step((float) (run_w / run_m), (float) (wsum / mag_sum)));
+        }
+        const float centroid = centroid_stepped((float) (wsum / mag_sum), cstep);     // :127
         const double cn = (double) centroid * rnyq;
         const double rm = 1.0 / (double) M;
         double var = ((b2 + b1 + 0.25 * mag_sum) * rm - (cn + cn) * (b1 + 0.5 * mag_sum)) * rm + (cn * cn) * mag_sum;
@@ -686,7 +717,7 @@ FX_MARK("p_spec_x2");
             if (lane == 0) {
                 fpl->flux = s[4] + flux; fpl->prod = prod; fpl->vsum = s[5] + vsum;
                 fpl->var = refine ? s[6] + direct : var;        // (this kernel forms the spread's sum itself, from its own centroid)
-                fpl->refined = 1;
+                fpl->refined = SPREAD_REFINED | cstep;
             }
         }
         next_exchange();

@@ -47,7 +47,7 @@ __device__ __forceinline__ void finalise_values(const EpilogueParams& p, const F
     // weightedMagnitudeSum (:95) from the moments: fc[m] = (m + 1/2) * frpb (:70), so sum fc * mag = frpb * (b1 + mag_sum / 2)
     const double wsum = p.frpb * (f.b1 + 0.5 * f.mag_sum);
     if (spec && f.mag_sum > 0.05) {                                            // :121-123
-        const float centroid = (float) (wsum / f.mag_sum);                     // :127
+        const float centroid = centroid_stepped((float) (wsum / f.mag_sum), f.refined);    // :127 (on a tie: the frame kernel's serial sums)
         const double dcnt = (double) f.cnt;
         const double inv_n = 1.0 / (dcnt > 0.0 ? dcnt : 1.0);                  // :129-130
         // :57-60 `flatnessMagnitudeSum > epsilon`: every gated bin alone exceeds epsilon (>= 0) and the terms are positive,
@@ -61,7 +61,7 @@ __device__ __forceinline__ void finalise_values(const EpilogueParams& p, const F
         // the spread's sum ((fc - centroid) / nyq)^2 * mag (:135-139) = (b2 + b1 + mag_sum/4) / M^2 - 2 cn (b1 + mag_sum/2) / M + cn^2 mag_sum;
         // where that form loses too much (the frame kernel's test) the kernel has taken the sum as the reference writes it
         double var = f.var;
-        if (!f.refined) {
+        if (!(f.refined & SPREAD_REFINED)) {
             const double cm = (double) centroid * p.inv_nyquist, rm = p.inv_bins;
             var = ((f.b2 + f.b1 + 0.25 * f.mag_sum) * rm - (cm + cm) * (f.b1 + 0.5 * f.mag_sum)) * rm + (cm * cm) * f.mag_sum;
         }

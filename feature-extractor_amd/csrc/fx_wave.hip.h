@@ -186,6 +186,37 @@ __device__ __forceinline__ double lane_get(double v, int l)
 {
     return __hiloint2double(lane_get(__double2hiint(v), l), lane_get(__double2loint(v), l));
 }
+
+// The centroid's last bit (ref SpectralCharacteristics.h:127).  (float) (weighted / magnitudeSum) is formed from the moments; where
+// the quotient sits within rounding distance of the middle between two floats, the last bits of the reference's serial sums decide
+// which of the two it is, and the kernel that holds the bins redoes them in the reference's order (FrameWave::spectral).  What it
+// finds travels in FramePart::refined: CENTROID_UP / CENTROID_DOWN = the reference's float is the next one above / below.
+enum { SPREAD_REFINED = 1, CENTROID_UP = 2, CENTROID_DOWN = 4 };
+__device__ __forceinline__ bool centroid_near_tie(double weighted, double mag_sum)
+{
+    // (only to find the neighbourhood: no division.  The hardware's reciprocal holds 2^-24; one Newton step, fused, makes that 2^-48)
+    const double r0 = __builtin_amdgcn_rcp(mag_sum);
+    const double q = weighted * __builtin_fma(r0, __builtin_fma(-mag_sum, r0, 1.0), r0);
+    const float qf = (float) q;
+    const double off = fabs(q - (double) qf);                                  // from the nearest float
+    const double half = 0.5 * ((double) __uint_as_float(__float_as_uint(qf) + 1u) - (double) qf);    // half a step above it
+    // the moment form and the serial sums differ by some 1e-15 of the quotient (up to M roundings of 1.1e-16, mostly cancelling);
+    // half a float step is 3e-8 of it.  Below a power of two the step is half as long.  NaN, inf and 0 compare false.
+    const double band = q * 4e-12;
+    return fabs(off - half) <= band || fabs(off - 0.5 * half) <= band;
+}
+__device__ __forceinline__ int centroid_step(float serial, float moments)
+{
+    const int d = (int) __float_as_uint(serial) - (int) __float_as_uint(moments);
+    return d == 1 ? CENTROID_UP : (d == -1 ? CENTROID_DOWN : 0);
+}
+__device__ __forceinline__ float centroid_stepped(float moments, int refined)
+{
+    unsigned b = __float_as_uint(moments);
+    if (refined & CENTROID_UP) b += 1u;
+    if (refined & CENTROID_DOWN) b -= 1u;
+    return __uint_as_float(b);
+}
 // lane i receives lane i-1's value (wave_shr:1); lane 0 receives `first`
 enum { DPP_WAVE_SHR1 = 0x138, DPP_ROW_SHR1 = 0x111, DPP_ROW_SHR2 = 0x112, DPP_ROW_SHR4 = 0x114, DPP_ROW_SHR8 = 0x118 };
 __device__ __forceinline__ int shift_up1(int v, int first) { return dpp_i<DPP_WAVE_SHR1, 0xF>(first, v); }

@@ -37,7 +37,8 @@ def impulse(C, T, N, at_hop=6):
 def impulse_on_boundary(C, T, N):
     """impulses exactly at the first sample of a hop: in one window the impulse is at sample N/2, in the
     next at sample 0, and re^2 is perfectly flat -- every `mag > mean` of the peak picker is an exact tie
-    decided by the rounding of the reference's serial sum"""
+    decided by the rounding of the reference's serial sum.  (Which way the tie falls is not asserted here: the
+    flat frames of tests/harmonic_cases.py are chosen so that it falls both ways, and their classes say which.)"""
     x = np.zeros((C, T, N // 2), np.float32)
     for c in range(C):
         x[c, 2 + c % 3, 0] = 0.7 / (c + 1)
