@@ -42,6 +42,12 @@ OSC_SENDER_MAX_TARGETS = 64         # FX_OSC_SENDER_MAX_TARGETS
 OSC_BUNDLE_MAX_ELEMENTS = 1024      # FX_OSC_BUNDLE_MAX_ELEMENTS
 OSC_TIMETAG_IMMEDIATE = 1           # FX_OSC_TIMETAG_IMMEDIATE
 LAUNCH_RECORD_CAP = 8
+# the offline driver (include/fx.h): FX_OFFLINE_* feature rows (ref AudioFeatures.h:20-31, less FFT), FX_OFFLINE_DO_*, FX_OFFLINE_SCRATCH_BYTES
+(OFFLINE_CENTROID, OFFLINE_SLOPE, OFFLINE_SPREAD, OFFLINE_FLATNESS, OFFLINE_FLUX, OFFLINE_ZERO_CROSSES, OFFLINE_F0, OFFLINE_HER,
+ OFFLINE_INHARMONICITY, OFFLINE_AUDIO, OFFLINE_FEATURE_ROWS) = range(11)
+OFFLINE_DO_SPECTRAL, OFFLINE_DO_HARMONIC, OFFLINE_DO_ZERO_CROSSES, OFFLINE_DO_AUDIO, OFFLINE_DO_NORMALISE_AUDIO, OFFLINE_DO_LOG_ATTACK = 1, 2, 4, 8, 16, 32
+OFFLINE_SCRATCH_BYTES = 16 << 20
+OFFLINE_WINDOWS = (256, 512, 1024, 2048, 4096)
 
 
 class OscSenderStats(ctypes.Structure):
@@ -136,6 +142,7 @@ def _prototypes():
         ("fx_offline_harmonic_characteristics", [vp, vp, i, vp, i], st), ("fx_offline_spectral_characteristics", [vp, vp, i, vp, i], st),
         ("fx_offline_get_previous_bins", [vp, dp, i], st), ("fx_offline_spectral_slope", [vp, vp, i, vp, i], st),
         ("fx_offline_auto_correlation", [vp, vp, i, vp, vp, i], st),
+        ("fx_offline_frames", [vp, vp, i, i, i, vp, vp, i], st), ("fx_offline_analyse", [vp, vp, i, i, i, i, u, vp, vp, vp, vp, i], st),
         ("fx_pack_osc12", [fp, fp], None), ("fx_pack_osc10", [fp, fp], None), ("fx_osc_encode", [cp, fp, P(ctypes.c_ubyte), i], st),
         ("fx_osc_message_bytes", [cp, i], st), ("fx_osc_encode_batch", [cp, i, i, fp, vp, i, ip], st),
         ("fx_get_osc_datagrams", [vp, cp, i, vp, i, ip, i], st),

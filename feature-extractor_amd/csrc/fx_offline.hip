@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "fx_context.h"
+#include "fx_offline_frames.h"
 
 #pragma clang fp contract(off)
 
@@ -25,6 +26,10 @@ struct fx_offline {
     int     prev_bins = 0;
     void*   d_in = nullptr;  size_t in_cap = 0;      // staging for host buffers
     void*   d_out = nullptr; size_t out_cap = 0;
+    // the offline driver (fx_offline_frames / fx_offline_analyse)
+    float*  d_table[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};    // the forward table of each window size, made on first use
+    void*   d_scratch = nullptr; size_t scratch_cap = 0;                   // magnitudes of one chunk of frames, when the caller keeps none
+    void*   d_work = nullptr; size_t work_cap = 0;                         // the per-frame results of a call [D][C][4 | 1 | 3], an energy envelope nobody asked for
 };
 
 namespace {
@@ -520,6 +525,9 @@ fx_status fx_offline_destroy(fx_offline* o)
     if (o->d_prev_bins) (void) hipFree(o->d_prev_bins);
     if (o->d_in) (void) hipFree(o->d_in);
     if (o->d_out) (void) hipFree(o->d_out);
+    for (float* t : o->d_table) if (t) (void) hipFree(t);
+    if (o->d_scratch) (void) hipFree(o->d_scratch);
+    if (o->d_work) (void) hipFree(o->d_work);
     if (o->stream) (void) hipStreamDestroy(o->stream);
     delete o;
     return FX_OK;
@@ -696,6 +704,161 @@ fx_status fx_offline_auto_correlation(fx_offline* o, float* data, int num_items,
         HIP_TRY(hipMemcpyAsync(data, d_data, in_bytes, hipMemcpyDeviceToHost, o->stream));
         HIP_TRY(hipMemcpyAsync(peak_bin, d_peak, sizeof(int) * (size_t) o->C, hipMemcpyDeviceToHost, o->stream));
         HIP_TRY(hipMemcpyAsync(frequency, d_freq, sizeof(double) * (size_t) o->C, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+    }
+    return FX_OK;
+}
+
+// ---- the offline driver: ref AudioAnalysis.h:129-251 performSpectralAnalysis into a ConcatenatedFeatureBuffer (ref AudioFeatures.h) ----
+// Its own kernels are in fx_offline_frames.hip; between them run the per-frame kernels above, launched exactly as their entries launch them.
+namespace {
+
+// what both driver entries refuse, before anything is launched or changed
+fx_status check_frames_args(fx_offline* o, const float* audio, const void* required_out, int S, int D, int N, int mem_kind)
+{
+    if (!o || !audio || !required_out) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null argument");
+    if (S < 1) return fx_fail(FX_ERR_INVALID_ARGUMENT, "num_samples %d: need at least 1", S);
+    if (D < 1) return fx_fail(FX_ERR_INVALID_ARGUMENT, "num_downsamples %d: need at least 1", D);
+    if (D > S) return fx_fail(FX_ERR_INVALID_ARGUMENT, "num_downsamples %d > num_samples %d (stepSize > 0, ref AudioAnalysis.h:139)", D, S);
+    if (!fxo::known_window(N)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "window_size %d is not one of 256, 512, 1024, 2048, 4096", N);
+    if (D == 1 && N > S) return fx_fail(FX_ERR_INVALID_ARGUMENT, "one frame of window_size %d needs as many samples, not %d (ref AudioAnalysis.h:157)", N, S);
+    if (mem_kind != FX_MEM_HOST && mem_kind != FX_MEM_DEVICE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", mem_kind);
+    return FX_OK;
+}
+
+fx_status forward_table_of(fx_offline* o, int N, const float** table)
+{
+    float*& t = o->d_table[fxo::window_slot(N)];
+    if (!t) {
+        const std::vector<float> k = fxo::forward_table(N);
+        void* q = nullptr;
+        HIP_TRY(hipMalloc(&q, k.size() * sizeof(float)));
+        const hipError_t e = hipMemcpy(q, k.data(), k.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void) hipFree(q); return fx_fail(FX_ERR_HIP, "copying the forward table failed: %s", hipGetErrorString(e)); }
+        t = static_cast<float*>(q);
+    }
+    *table = t;
+    return FX_OK;
+}
+
+} // namespace
+
+fx_status fx_offline_frames(fx_offline* o, const float* audio, int num_samples, int num_downsamples, int window_size, float* magnitudes, float* energy,
+                            int mem_kind)
+{
+    const int S = num_samples, D = num_downsamples, N = window_size, B = N / 2 + 1;
+    fx_status st = check_frames_args(o, audio, magnitudes, S, D, N, mem_kind);
+    if (st != FX_OK) return st;
+    HIP_TRY(hipSetDevice(o->device));
+    const size_t C = (size_t) o->C;
+    const size_t mag_floats = (size_t) D * C * B, env_floats = energy ? C * D : 0;
+    const float* table;
+    if ((st = forward_table_of(o, N, &table)) != FX_OK) return st;
+    const void *da, *db;
+    if ((st = stage_in(o, mem_kind, audio, sizeof(float) * C * S, nullptr, 0, &da, &db)) != FX_OK) return st;
+    float* d_mags = magnitudes; float* d_env = energy;
+    if (mem_kind == FX_MEM_HOST) {
+        if ((st = fx_grow(&o->d_out, &o->out_cap, sizeof(float) * (mag_floats + env_floats))) != FX_OK) return st;
+        d_mags = static_cast<float*>(o->d_out);
+        d_env = energy ? d_mags + mag_floats : nullptr;
+    }
+    if ((st = fxo::launch_frames(o->stream, static_cast<const float*>(da), o->C, S, D, N, 0, D, table, d_mags, d_env)) != FX_OK) return st;
+    if (mem_kind == FX_MEM_HOST) {
+        HIP_TRY(hipMemcpyAsync(magnitudes, d_mags, sizeof(float) * mag_floats, hipMemcpyDeviceToHost, o->stream));
+        if (energy) HIP_TRY(hipMemcpyAsync(energy, d_env, sizeof(float) * env_floats, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+    }
+    return FX_OK;
+}
+
+fx_status fx_offline_analyse(fx_offline* o, const float* audio, int num_samples, int num_downsamples, int window_size, int sample_rate, unsigned what,
+                             float* features, float* energy, float* log_attack_time, float* magnitudes, int mem_kind)
+{
+    const int S = num_samples, D = num_downsamples, N = window_size, B = N / 2 + 1;
+    fx_status st = check_frames_args(o, audio, features, S, D, N, mem_kind);
+    if (st != FX_OK) return st;
+    const bool spectral = what & FX_OFFLINE_DO_SPECTRAL, harmonic = what & FX_OFFLINE_DO_HARMONIC, log_attack = what & FX_OFFLINE_DO_LOG_ATTACK;
+    if ((what & FX_OFFLINE_DO_NORMALISE_AUDIO) && !(what & FX_OFFLINE_DO_AUDIO))
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "what = %u: FX_OFFLINE_DO_NORMALISE_AUDIO needs FX_OFFLINE_DO_AUDIO", what);
+    if (log_attack && !log_attack_time) return fx_fail(FX_ERR_INVALID_ARGUMENT, "FX_OFFLINE_DO_LOG_ATTACK with a null log_attack_time");
+    if (log_attack && sample_rate < 1000)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "sample_rate %d: need sample_rate >= 1000 (sampleRate / 1000 is an int division, ref AudioAnalysis.h:619)", sample_rate);
+    if (spectral && o->d_prev_bins && o->prev_bins != B)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "this analyser's previousBinMagnitudes holds %d bins (fixed by its window size, ref AudioAnalysis.h:120-121); "
+                                                "fx_offline_reset before frames of %d", o->prev_bins, B);
+    HIP_TRY(hipSetDevice(o->device));
+    const size_t C = (size_t) o->C, rows = C * D;
+    const bool need_energy = energy || log_attack, need_frames = spectral || harmonic || need_energy || magnitudes;
+    const size_t feat_floats = (size_t) FX_OFFLINE_FEATURE_ROWS * rows, mag_floats = magnitudes ? (size_t) D * C * B : 0;
+
+    // every allocation first: nothing below can fail for want of memory once the first kernel is enqueued
+    const float* table = nullptr;
+    if (need_frames && (st = forward_table_of(o, N, &table)) != FX_OK) return st;
+    const void *da, *db;
+    if ((st = stage_in(o, mem_kind, audio, sizeof(float) * C * S, nullptr, 0, &da, &db)) != FX_OK) return st;
+    const float* d_audio = static_cast<const float*>(da);
+    float* d_feat = features; float* d_env = energy; float* d_lat = log_attack_time; float* d_mags = magnitudes;
+    if (mem_kind == FX_MEM_HOST) {                                          // features | energy | log attack time | magnitudes
+        if ((st = fx_grow(&o->d_out, &o->out_cap, sizeof(float) * (feat_floats + rows + C + mag_floats))) != FX_OK) return st;
+        d_feat = static_cast<float*>(o->d_out);
+        d_env = energy ? d_feat + feat_floats : nullptr;
+        d_lat = d_feat + feat_floats + rows;
+        d_mags = magnitudes ? d_lat + C : nullptr;
+    }
+    if ((st = fx_grow(&o->d_work, &o->work_cap, sizeof(float) * 9 * rows)) != FX_OK) return st;      // out4 | slope | out3 | energy
+    float* d_out4 = static_cast<float*>(o->d_work);
+    float* d_slope = d_out4 + 4 * rows;
+    float* d_out3 = d_slope + rows;
+    if (need_energy && !d_env) d_env = d_out3 + 3 * rows;
+    // frames per chunk: all of them into the caller's magnitudes, or what the scratch holds
+    int chunk = D;
+    if (need_frames && !d_mags) {
+        const size_t frame_bytes = sizeof(float) * C * B;
+        const size_t fit = FX_OFFLINE_SCRATCH_BYTES / frame_bytes;
+        chunk = (int) (fit < 1 ? 1 : (fit > (size_t) D ? (size_t) D : fit));
+        if ((st = fx_grow(&o->d_scratch, &o->scratch_cap, frame_bytes * chunk)) != FX_OK) return st;
+    }
+    if (spectral && !o->d_prev_bins) {                                      // (as fx_offline_spectral_characteristics does on its first frame)
+        HIP_TRY(hipMalloc((void**) &o->d_prev_bins, sizeof(double) * C * B));
+        HIP_TRY(hipMemsetAsync(o->d_prev_bins, 0, sizeof(double) * C * B, o->stream));
+        o->prev_bins = B;
+    }
+
+    HIP_TRY(hipMemsetAsync(d_feat, 0, sizeof(float) * feat_floats, o->stream));        // rows not asked for are +0
+    for (int f0 = 0; need_frames && f0 < D; f0 += chunk) {
+        const int frames = D - f0 < chunk ? D - f0 : chunk;
+        float* block = d_mags ? d_mags + (size_t) f0 * C * B : static_cast<float*>(o->d_scratch);
+        if ((st = fxo::launch_frames(o->stream, d_audio, o->C, S, D, N, f0, frames, table, block, need_energy ? d_env : nullptr)) != FX_OK) return st;
+        for (int f = f0; f < f0 + frames && (spectral || harmonic); f++) {  // the order of ref AudioAnalysis.h:229-246
+            const float* m = block + (size_t) (f - f0) * C * B;
+            if (spectral) {
+                hipLaunchKernelGGL(spectral_characteristics_kernel, dim3((unsigned) o->C), dim3(NT), SPECTRAL_LDS_PER_BIN * (size_t) B, o->stream,
+                                   m, B, o->nyquist, o->d_prev_bins, d_out4 + 4 * C * f);
+                hipLaunchKernelGGL(spectral_slope_kernel, dim3((unsigned) o->C), dim3(NT), SLOPE_LDS_PER_BIN * (size_t) B, o->stream, m, B, d_slope + C * f);
+            }
+            if (harmonic)
+                hipLaunchKernelGGL(harmonic_characteristics_kernel, dim3((unsigned) o->C), dim3(NT), harmonic_lds_bytes(B), o->stream,
+                                   m, B, o->nyquist, o->d_prev_f0, d_out3 + 3 * C * f);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (spectral || harmonic)
+        if ((st = fxo::launch_scatter_rows(o->stream, spectral ? d_out4 : nullptr, spectral ? d_slope : nullptr, harmonic ? d_out3 : nullptr, o->C, D, d_feat)) != FX_OK) return st;
+    if (what & FX_OFFLINE_DO_ZERO_CROSSES) {
+        hipLaunchKernelGGL(zero_crosses_kernel, dim3((unsigned) (o->C * D)), dim3(NT), 0, o->stream, d_audio, S, D, d_feat + (size_t) FX_OFFLINE_ZERO_CROSSES * rows);
+        HIP_TRY(hipGetLastError());
+    }
+    if (what & FX_OFFLINE_DO_AUDIO) {
+        float* row = d_feat + (size_t) FX_OFFLINE_AUDIO * rows;
+        if ((st = fxo::launch_rms_row(o->stream, d_audio, o->C, S, D, row)) != FX_OK) return st;
+        if ((what & FX_OFFLINE_DO_NORMALISE_AUDIO) && (st = fxo::launch_normalise_row(o->stream, row, o->C, D)) != FX_OK) return st;
+    }
+    if (log_attack && (st = fxo::launch_log_attack_times(o->stream, d_env, o->C, D, S, sample_rate, d_lat)) != FX_OK) return st;
+    if (mem_kind == FX_MEM_HOST) {
+        HIP_TRY(hipMemcpyAsync(features, d_feat, sizeof(float) * feat_floats, hipMemcpyDeviceToHost, o->stream));
+        if (energy) HIP_TRY(hipMemcpyAsync(energy, d_env, sizeof(float) * rows, hipMemcpyDeviceToHost, o->stream));
+        if (log_attack) HIP_TRY(hipMemcpyAsync(log_attack_time, d_lat, sizeof(float) * C, hipMemcpyDeviceToHost, o->stream));
+        if (magnitudes) HIP_TRY(hipMemcpyAsync(magnitudes, d_mags, sizeof(float) * mag_floats, hipMemcpyDeviceToHost, o->stream));
         HIP_TRY(hipStreamSynchronize(o->stream));
     }
     return FX_OK;

@@ -1,0 +1,284 @@
+// fx_offline_frames.hip -- the offline driver's own kernels (include/fx.h, fx_offline_frames / fx_offline_analyse): the frame / window /
+// magnitude stage of the reference's AudioAnalyser::performSpectralAnalysis (ref AudioAnalysis.h:129-251; "ref:" citations are relative to
+// the reference's Source/), and the parts of its ConcatenatedFeatureBuffer (ref AudioFeatures.h:14-314) that are arithmetic: the downsampled
+// RMS row, its normalisation, the log attack time of every channel at once, and the placing of the per-frame results in the feature rows.
+// The entries themselves, and the per-frame kernels they run between these, are in fx_offline.hip.
+//
+// The frame kernel is the hot path of an offline analysis -- N log N a frame against the O(N) of every per-frame kernel: one workgroup per
+// (frame, channel); the window is read in sample order (coalesced; the padding rule decides per sample), multiplied by the Bartlett gain and
+// written to LDS at its leaf position of the reference FFT's recursion; the transform is the plain per-level form of fx_taps.hip (one
+// butterfly per thread and level, table twiddles, no fused multiply-add: the DAG of every transform in this library, so the same bits); the
+// magnitudes leave in bin order (coalesced) and one lane adds them up in bin order for the energy envelope.
+// LDS: N complex + N / 2 + 1 floats = 48 KB at 4096 points.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <vector>
+
+#include "fx_offline_frames.h"
+
+#pragma clang fp contract(off)
+
+namespace fxo {
+namespace {
+
+constexpr int NT = 256;
+
+// The reference FFT's factorisation of N (oracle/fx_oracle.c fft_cfg_init): radix 4 while it divides, then one radix 2.  Level k (0 = the
+// outermost call of the recursion) has twiddle stride 4^k, and each of its butterflies spans length(k) points.
+template <int N> struct Plan {
+    static constexpr int LOG = N == 256 ? 8 : N == 512 ? 9 : N == 1024 ? 10 : N == 2048 ? 11 : 12;
+    static constexpr int R4 = LOG / 2;
+    static constexpr int LEVELS = R4 + (LOG & 1);
+    static __device__ __forceinline__ int radix(int k) { return k < R4 ? 4 : 2; }
+    static __device__ __forceinline__ int stride(int k) { return 1 << (2 * k); }
+    static __device__ __forceinline__ int length(int k) { return N / (stride(k) * radix(k)); }
+    // where input sample j stands before the butterflies (the leaves of the recursion): its digits, level by level, most significant first
+    static __device__ __forceinline__ int position(int j)
+    {
+        int p = 0;
+#pragma unroll
+        for (int k = 0; k < LEVELS; k++) p += ((j >> (2 * k)) & (radix(k) - 1)) * length(k);
+        return p;
+    }
+};
+
+struct cpx { float r, i; };
+__device__ __forceinline__ cpx c_mul(cpx a, cpx b) { return cpx{a.r * b.r - a.i * b.i, a.r * b.i + a.i * b.r}; }
+__device__ __forceinline__ cpx c_add(cpx a, cpx b) { return cpx{a.r + b.r, a.i + b.i}; }
+__device__ __forceinline__ cpx c_sub(cpx a, cpx b) { return cpx{a.r - b.r, a.i - b.i}; }
+__device__ __forceinline__ cpx tw_at(const float* tw, int j)
+{
+    const float2 t = reinterpret_cast<const float2*>(tw)[j];
+    return cpx{t.x, t.y};
+}
+
+// The forward butterflies of every level, innermost first, over buf (in leaf order): fft_butterfly4 / fft_butterfly2 of the oracle,
+// operation for operation.  Ends behind a barrier.
+template <int N> __device__ void forward_transform(cpx* buf, const float* tw)
+{
+    using P = Plan<N>;
+    for (int k = P::LEVELS - 1; k >= 0; k--) {
+        const int r = P::radix(k), s = P::stride(k), L = P::length(k);
+        for (int q = threadIdx.x; q < N / r; q += NT) {
+            const int b = q / L, i = q - b * L;
+            cpx* d = buf + b * r * L + i;
+            if (r == 4) {
+                const cpx s0 = c_mul(d[L], tw_at(tw, i * s));
+                const cpx s1 = c_mul(d[2 * L], tw_at(tw, 2 * i * s));
+                const cpx s2 = c_mul(d[3 * L], tw_at(tw, 3 * i * s));
+                const cpx s3 = c_add(s0, s2), s4 = c_sub(s0, s2), s5 = c_sub(d[0], s1);
+                const cpx d0 = c_add(d[0], s1);
+                d[2 * L] = c_sub(d0, s3);
+                d[0] = c_add(d0, s3);
+                d[L] = cpx{s5.r + s4.i, s5.i - s4.r};
+                d[3 * L] = cpx{s5.r - s4.i, s5.i + s4.r};
+            } else {
+                const cpx t = c_mul(d[L], tw_at(tw, i * s));
+                d[L] = c_sub(d[0], t);
+                d[0] = c_add(d[0], t);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// block = (frame, channel): blockIdx.x = (f - first_frame) * C + c
+template <int N>
+__global__ void __launch_bounds__(NT) offline_frames_kernel(const float* __restrict__ audio, int C, int S, int D, int first_frame,
+                                                            const float* __restrict__ tw, float* __restrict__ mags, float* __restrict__ energy)
+{
+    constexpr int H = N / 2, B = N / 2 + 1;
+    __shared__ cpx buf[N];
+    __shared__ float mag[B];
+    using P = Plan<N>;
+    const int tid = threadIdx.x;
+    const int fl = blockIdx.x / C, c = blockIdx.x - fl * C, f = first_frame + fl;
+    const int step = S / D;                                                 // :135 (int division)
+    // :150-161: the window is centred on the downsample -- unless there is one frame only, which starts at sample 0
+    const long long start = D == 1 ? 0 : (long long) f * step - H;
+    const float* a = audio + (size_t) c * S;
+    for (int j = tid; j < N; j += NT) {
+        const long long i = start + j;                                      // :167
+        const float v = (i >= 0 && i < S) ? a[i] : 0.0f;                    // :169-177: zero padding for the ends
+        // scaleBufferWithBartlettWindowing (:667-676): two gain ramps, each gain the float sum of the increments 1 / H before it -- exact
+        const float w = j < H ? (float) j * (2.0f / N) : 2.0f - (float) j * (2.0f / N);
+        buf[P::position(j)] = cpx{v * w, 0.0f};                             // (always multiplied: inf * 0 = NaN, as applyGainRamp makes it)
+    }
+    __syncthreads();
+    forward_transform<N>(buf, tw);
+    // performFrequencyOnlyForwardTransform, as tools/refdiff/juce_standin.h states it: sqrt (re * re + im * im) in float, bins 0 .. N / 2
+    float* out = mags + ((size_t) fl * C + c) * B;
+    for (int b = tid; b < B; b += NT) {
+        const cpx x = buf[b];
+        const float m = sqrtf(x.r * x.r + x.i * x.i);
+        mag[b] = m;
+        out[b] = m;
+    }
+    if (!energy) return;
+    __syncthreads();
+    if (tid == 0) {                                                         // sumAccrossChannels (:705-716) of one channel: serial, in float
+        float e = 0.0f;
+#pragma unroll 8
+        for (int b = 0; b < B; b++) e += mag[b];
+        energy[(size_t) c * D + f] = e;                                     // :249
+    }
+}
+
+// ---- ref AudioFeatures.h:158-184 fillDownsampledRMSAudioChannels: lane = (channel, downsample), walking its step serially (getRMSLevel: float
+// squares, double sum in sample order, sqrt of the double mean) ----
+__global__ void __launch_bounds__(NT) rms_row_kernel(const float* __restrict__ audio, int C, int S, int D, float* __restrict__ row)
+{
+    const long long t = (long long) blockIdx.x * NT + threadIdx.x;
+    if (t >= (long long) C * D) return;
+    const int c = (int) (t / D), i = (int) (t - (long long) c * D);
+    const int spb = S / D;                                                  // :161
+    const float* a = audio + (size_t) c * S + (size_t) i * spb;
+    if (spb == 1) { row[t] = a[0]; return; }                                // :165-172: the first D samples as they are
+    double sum = 0.0;
+    for (int s = 0; s < spb; s++) { const float x = a[s]; sum += (double) (x * x); }
+    row[t] = (float) sqrt(sum / (double) spb);
+}
+
+// ---- ref AudioFeatures.h:186-195 normaliseAudioChannels, one channel's row per block.  findMinMax starts both ends from row[0] and moves on
+// `<` / `>` only: a NaN elsewhere is skipped (so one early in a thread's stride hides nothing), a NaN at row[0] stays -- thread 0's business ----
+__global__ void __launch_bounds__(NT) normalise_row_kernel(float* row, int D)
+{
+    __shared__ float s_lo[NT], s_hi[NT];
+    __shared__ float s_scale;
+    float* r = row + (size_t) blockIdx.x * D;
+    float lo = __builtin_huge_valf(), hi = -__builtin_huge_valf();          // (+inf never moves the minimum, -inf never the maximum)
+    for (int i = 1 + threadIdx.x; i < D; i += NT) { const float v = r[i]; if (v < lo) lo = v; if (v > hi) hi = v; }
+    s_lo[threadIdx.x] = lo; s_hi[threadIdx.x] = hi;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float l = r[0], h = r[0];
+        for (int k = 0; k < NT; k++) { if (s_lo[k] < l) l = s_lo[k]; if (s_hi[k] > h) h = s_hi[k]; }
+        const float al = fabsf(l), ah = fabsf(h);
+        const float m = al < ah ? ah : al;                                  // jmax (a, b) = a < b ? b : a
+        s_scale = 1.0f / m;                                                 // :193
+    }
+    __syncthreads();
+    const float scale = s_scale;
+    for (int i = threadIdx.x; i < D; i += NT) r[i] = r[i] * scale;          // :194
+}
+
+// ---- ref AudioAnalysis.h:611-622 setLogAttackTime, block = channel: fx_offline.hip's log_attack_time_kernel over the rows of energy [C][n] ----
+__global__ void __launch_bounds__(NT) log_attack_times_kernel(const float* __restrict__ energy, int n, int num_input_samples, int num_downsamples,
+                                                              int sample_rate, float* __restrict__ out)
+{
+    __shared__ float s_max[NT];
+    __shared__ int s_idx[NT];
+    const float* env = energy + (size_t) blockIdx.x * n;
+    float m = -__builtin_huge_valf();
+    bool any = false;
+    // findMinMax (...).getEnd(), :615: the maximum starts from env[0] and moves on `>` only, so a NaN anywhere but at 0 is skipped
+    for (int k = threadIdx.x; k < n; k += NT) { const float v = env[k]; if (v == v && (!any || v > m)) { m = v; any = true; } }
+    s_max[threadIdx.x] = any ? m : -__builtin_huge_valf();
+    __syncthreads();
+    if (threadIdx.x == 0) { float mm = env[0]; for (int k = 0; k < NT; k++) if (s_max[k] > mm) mm = s_max[k]; s_max[0] = mm; }      // a NaN at 0 stays: it equals no entry, i = n
+    __syncthreads();
+    const float max_energy = s_max[0];
+    int first = n;                                                          // first index holding the maximum, :616-618
+    for (int k = threadIdx.x; k < n; k += NT) if (env[k] == max_energy) { first = k; break; }
+    s_idx[threadIdx.x] = first;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int i = n;
+        for (int k = 0; k < NT; k++) if (s_idx[k] < i) i = s_idx[k];
+        const double ms_per_sample = 1.0 / (double) (sample_rate / 1000);   // :619 (sampleRate is an int: AudioFeatures.h:303)
+        const int samples_per_step = num_input_samples / num_downsamples;   // :620
+        out[blockIdx.x] = (float) log10((double) (float) (i * samples_per_step) * (float) ms_per_sample);   // :621
+    }
+}
+
+// ---- ref AudioFeatures.h:133-140 setFeatureSample, for the per-frame results of a whole call: thread = (frame, channel) ----
+enum { ROW_CENTROID = 0, ROW_SLOPE, ROW_SPREAD, ROW_FLATNESS, ROW_FLUX, ROW_ZERO_CROSSES, ROW_F0, ROW_HER, ROW_INHARMONICITY };
+__global__ void __launch_bounds__(NT) scatter_rows_kernel(const float* __restrict__ out4, const float* __restrict__ slope, const float* __restrict__ out3,
+                                                          int C, int D, float* __restrict__ features)
+{
+    const long long t = (long long) blockIdx.x * NT + threadIdx.x;          // = f * C + c
+    if (t >= (long long) C * D) return;
+    const int f = (int) (t / C), c = (int) (t - (long long) f * C);
+    const size_t rows = (size_t) C * D, at = (size_t) c * D + f;
+    if (out4) {                                                             // centroid / nyquist, spread, flatness, flux
+        features[ROW_CENTROID * rows + at] = out4[4 * t];
+        features[ROW_SPREAD * rows + at] = out4[4 * t + 1];
+        features[ROW_FLATNESS * rows + at] = out4[4 * t + 2];
+        features[ROW_FLUX * rows + at] = out4[4 * t + 3];
+    }
+    if (slope) features[ROW_SLOPE * rows + at] = slope[t];
+    if (out3) {                                                             // f0, harmonic energy ratio, inharmonicity
+        features[ROW_F0 * rows + at] = out3[3 * t];
+        features[ROW_HER * rows + at] = out3[3 * t + 1];
+        features[ROW_INHARMONICITY * rows + at] = out3[3 * t + 2];
+    }
+}
+
+unsigned blocks_for(long long items) { return (unsigned) ((items + NT - 1) / NT); }
+
+} // namespace
+
+std::vector<float> forward_table(int n)
+{
+    std::vector<float> k(2 * (size_t) n);
+    for (int i = 0; i < n; i++) {
+        const double phase = -2.0 * 3.14159265358979323846 * i / n;
+        k[2 * i] = (float) std::cos(phase);
+        k[2 * i + 1] = (float) std::sin(phase);
+    }
+    return k;
+}
+
+fx_status launch_frames(hipStream_t stream, const float* audio, int C, int S, int D, int n, int first_frame, int num_frames, const float* table,
+                        float* mags, float* energy)
+{
+    const int bins = n / 2 + 1;
+    const int per_launch = (1 << 30) / C;                                   // the grid's x extent stays below 2^31
+    for (int done = 0; done < num_frames; done += per_launch) {
+        const int frames = num_frames - done < per_launch ? num_frames - done : per_launch;
+        const dim3 grid((unsigned) ((long long) frames * C)), block(NT);
+        float* m = mags + (size_t) done * C * bins;
+        const int first = first_frame + done;
+        switch (n) {
+            case 256:  hipLaunchKernelGGL(offline_frames_kernel<256>, grid, block, 0, stream, audio, C, S, D, first, table, m, energy); break;
+            case 512:  hipLaunchKernelGGL(offline_frames_kernel<512>, grid, block, 0, stream, audio, C, S, D, first, table, m, energy); break;
+            case 1024: hipLaunchKernelGGL(offline_frames_kernel<1024>, grid, block, 0, stream, audio, C, S, D, first, table, m, energy); break;
+            case 2048: hipLaunchKernelGGL(offline_frames_kernel<2048>, grid, block, 0, stream, audio, C, S, D, first, table, m, energy); break;
+            case 4096: hipLaunchKernelGGL(offline_frames_kernel<4096>, grid, block, 0, stream, audio, C, S, D, first, table, m, energy); break;
+            default: return fx_fail(FX_ERR_INVALID_ARGUMENT, "window_size %d is not one of 256, 512, 1024, 2048, 4096", n);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return FX_OK;
+}
+
+fx_status launch_rms_row(hipStream_t stream, const float* audio, int C, int S, int D, float* row)
+{
+    hipLaunchKernelGGL(rms_row_kernel, dim3(blocks_for((long long) C * D)), dim3(NT), 0, stream, audio, C, S, D, row);
+    HIP_TRY(hipGetLastError());
+    return FX_OK;
+}
+
+fx_status launch_normalise_row(hipStream_t stream, float* row, int C, int D)
+{
+    hipLaunchKernelGGL(normalise_row_kernel, dim3((unsigned) C), dim3(NT), 0, stream, row, D);
+    HIP_TRY(hipGetLastError());
+    return FX_OK;
+}
+
+fx_status launch_log_attack_times(hipStream_t stream, const float* energy, int C, int D, int S, int sample_rate, float* out)
+{
+    hipLaunchKernelGGL(log_attack_times_kernel, dim3((unsigned) C), dim3(NT), 0, stream, energy, D, S, D, sample_rate, out);
+    HIP_TRY(hipGetLastError());
+    return FX_OK;
+}
+
+fx_status launch_scatter_rows(hipStream_t stream, const float* out4, const float* slope, const float* out3, int C, int D, float* features)
+{
+    hipLaunchKernelGGL(scatter_rows_kernel, dim3(blocks_for((long long) C * D)), dim3(NT), 0, stream, out4, slope, out3, C, D, features);
+    HIP_TRY(hipGetLastError());
+    return FX_OK;
+}
+
+} // namespace fxo

@@ -109,3 +109,105 @@ class AudioAnalyser:
         capi.check(self._lib.fx_offline_auto_correlation(self._h, data.ctypes.data_as(ctypes.c_void_p), data.shape[1],
                                                          peaks.ctypes.data_as(ctypes.c_void_p), freqs.ctypes.data_as(ctypes.c_void_p), capi.MEM_HOST))
         return data, peaks, freqs
+
+    # ---- the offline driver: audio in, the reference's feature buffer out (fx_offline_frames / fx_offline_analyse) ----
+    def _audio(self, audio):
+        """-> (the array or tensor to keep alive, its address, num_samples, memory kind, an allocator of float32 results beside it)"""
+        if _is_device_tensor(audio):
+            import torch
+            if audio.dtype != torch.float32 or audio.dim() != 2 or audio.shape[0] != self.num_channels:
+                raise ValueError("expected [%d][num_samples] float32" % self.num_channels)
+            audio = audio.contiguous()
+            torch.cuda.current_stream(audio.device).synchronize()       # the library reads it on a stream of its own
+            return audio, audio.data_ptr(), int(audio.shape[1]), capi.MEM_DEVICE, lambda *shape: torch.empty(shape, dtype=torch.float32, device=audio.device)
+        audio = self._rows(audio)
+        return audio, audio.ctypes.data, int(audio.shape[1]), capi.MEM_HOST, lambda *shape: np.empty(shape, np.float32)
+
+    def _finish(self, kind, *results):
+        """device results are read after the object's stream has run dry; each comes back as a numpy array"""
+        if kind == capi.MEM_DEVICE:
+            capi.check(self._lib.fx_offline_sync(self._h))
+        return [None if r is None else (r if isinstance(r, np.ndarray) else r.cpu().numpy()) for r in results]
+
+    def magnitude_frames(self, audio, num_downsamples, window_size):                         # ref :146-181, :667-676, :208
+        """audio [C][S] (numpy: through host memory; a CUDA torch tensor: used where it lies) -> (magnitudes [D][C][window_size / 2 + 1],
+        energy envelope [C][D]) of the windows performSpectralAnalysis cuts: one per downsample, centred on it, Bartlett-windowed."""
+        keep, address, S, kind, new = self._audio(audio)
+        D, N = int(num_downsamples), int(window_size)
+        if D < 1 or N not in capi.OFFLINE_WINDOWS:           # (the library refuses these too: the shapes below need them first)
+            raise capi.FxError(capi.FX_ERR_INVALID_ARGUMENT, "num_downsamples %d, window_size %d" % (D, N))
+        mags, energy = new(D, self.num_channels, N // 2 + 1), new(self.num_channels, D)
+        capi.check(self._lib.fx_offline_frames(self._h, address, S, D, N, _address(mags), _address(energy), kind))
+        return tuple(self._finish(kind, mags, energy))
+
+    def perform_spectral_analysis(self, audio, num_downsamples, window_size, sample_rate, spectral=True, harmonic=True, zero_crosses=True,
+                                  audio_rms=True, normalise=True, log_attack=True, keep_fft=False):          # ref :129-251
+        """The reference's offline analysis of audio [C][S], each channel a mono file of its own -> ConcatenatedFeatureBuffer.  The analysers'
+        state (previous_f0, previous_bin_magnitudes) carries on from the calls before."""
+        keep, address, S, kind, new = self._audio(audio)
+        D, N, C = int(num_downsamples), int(window_size), self.num_channels
+        if D < 1 or N not in capi.OFFLINE_WINDOWS:
+            raise capi.FxError(capi.FX_ERR_INVALID_ARGUMENT, "num_downsamples %d, window_size %d" % (D, N))
+        what = ((capi.OFFLINE_DO_SPECTRAL if spectral else 0) | (capi.OFFLINE_DO_HARMONIC if harmonic else 0)
+                | (capi.OFFLINE_DO_ZERO_CROSSES if zero_crosses else 0) | (capi.OFFLINE_DO_AUDIO if audio_rms else 0)
+                | (capi.OFFLINE_DO_NORMALISE_AUDIO if normalise else 0) | (capi.OFFLINE_DO_LOG_ATTACK if log_attack else 0))
+        features, energy = new(capi.OFFLINE_FEATURE_ROWS, C, D), new(C, D)
+        lat = new(C) if log_attack else None
+        mags = new(D, C, N // 2 + 1) if keep_fft else None
+        capi.check(self._lib.fx_offline_analyse(self._h, address, S, D, N, int(sample_rate), what, _address(features), _address(energy),
+                                                _address(lat), _address(mags), kind))
+        if spectral:
+            self._bins = N // 2 + 1
+        features, energy, lat, mags = self._finish(kind, features, energy, lat, mags)
+        return ConcatenatedFeatureBuffer(features, energy, lat, mags, D, int(sample_rate))
+
+
+def _is_device_tensor(a):
+    return type(a).__module__.split(".")[0] == "torch" and a.is_cuda
+
+
+def _address(a):
+    if a is None:
+        return None
+    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+
+
+class ConcatenatedFeatureBuffer:
+    """The results of AudioAnalyser.perform_spectral_analysis under the reference's names (ref AudioFeatures.h:14-314), on the host.
+    `feature` arguments are the FX_OFFLINE_* row numbers (capi.OFFLINE_CENTROID .. capi.OFFLINE_AUDIO)."""
+
+    def __init__(self, feature_buffer, energy_envelope, estimated_log_attack_time, magnitudes, num_downsamples, sample_rate):
+        self.feature_buffer = feature_buffer                            # [10][C][D]: featureBuffer, less its FFT part
+        self.energy_envelope = energy_envelope                          # [C][D]
+        self.estimated_log_attack_time = estimated_log_attack_time      # [C], or None if not analysed
+        self.magnitudes = magnitudes                                    # [D][C][bins], or None unless keep_fft
+        self.num_downsamples = int(num_downsamples)
+        self.sample_rate = int(sample_rate)                             # (an int: ref :301)
+        self.num_feature_channels = feature_buffer.shape[1]
+
+    def get_feature_buffer(self, feature):                                                  # ref :242-254
+        return self.feature_buffer[int(feature)].copy()
+
+    def get_feature_sample(self, feature, channel, index):                                  # ref :256-264
+        return self.feature_buffer[int(feature), int(channel), int(index)]
+
+    def get_feature_range(self, feature):                                                   # ref :208-213, findMinMax over every channel's row
+        row = self.feature_buffer[int(feature)].reshape(-1)
+        lo = hi = row[0]
+        for v in row[1:]:
+            if v < lo:
+                lo = v
+            if v > hi:
+                hi = v
+        return lo, hi
+
+    def get_average_feature_sample(self, feature, index):                                   # ref :266-275: a serial float sum
+        av = np.float32(0.0)
+        for c in range(self.num_feature_channels):
+            av = np.float32(av + self.feature_buffer[int(feature), c, int(index)])
+        return np.float32(av / np.float32(self.num_feature_channels))
+
+    def fft_bins(self, channel):                                                            # ref :142-156 setFFTBinsForSample: [bin][downsample]
+        if self.magnitudes is None:
+            raise ValueError("the analysis kept no magnitudes (keep_fft=False)")
+        return self.magnitudes[:, int(channel), :].T

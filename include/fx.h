@@ -816,6 +816,62 @@ fx_status fx_offline_spectral_slope(fx_offline* o, const float* magnitudes, int 
  * peak_bin * (nyquist / num_items) + half a bin */
 fx_status fx_offline_auto_correlation(fx_offline* o, float* data, int num_items, int* peak_bin, double* frequency, int mem_kind);
 
+/* ---- the offline driver: AudioAnalyser::performSpectralAnalysis (AudioAnalysis.h:129-251) into a ConcatenatedFeatureBuffer
+ * (AudioFeatures.h:14-314): audio in, the reference's feature buffer out ----
+ * What the reference pins (live code, held to the unmodified header by tests/golden/offline/feature_buffer.npz): the frame indexing and
+ * padding (:146-181, observable in the public member fftIn), scaleBufferWithBartlettWindowing (:667-676), analyseNormalisedZeroCrosses,
+ * setLogAttackTime, ConcatenatedFeatureBuffer::fillDownsampledRMSAudioChannels / normaliseAudioChannels and the buffer's layout
+ * (AudioFeatures.h:124-195).  What is OURS, specified here: AudioAnalysis.h:219-246 is commented out, so the reference never fills fftOut and
+ * its energyEnvelope sums uninitialised memory; this driver does what that block states, its calls in its order.  JUCE's
+ * performFrequencyOnlyForwardTransform is not in the reference tree; its arithmetic is taken as tools/refdiff/juce_standin.h states it (the
+ * forward transform, then sqrt (re * re + im * im) in float).
+ *
+ * An fx_offline stands for C = num_channels independent MONO analysers: where the reference sums (sumAccrossChannels, :705-716) or
+ * normalises (AudioFeatures.h:186-195) across the channels of one file, this is done per channel.
+ * audio [C][S] fp32; S = num_samples, D = num_downsamples, N = window_size in {256, 512, 1024, 2048, 4096}, B = N / 2 + 1.  mem_kind covers
+ * every buffer of a call: FX_MEM_HOST buffers are copied synchronously, FX_MEM_DEVICE buffers are 4-byte aligned and used asynchronously on
+ * the object's stream (fx_offline_sync waits).
+ *
+ * Frames (:146-181).  step = S div D.  If D == 1: win[j] = audio[j], 0 <= j < N.  Otherwise, for frame f: i = f * step + j - N / 2 and
+ * win[j] = audio[i] if 0 <= i < S, else +0.  Then x[j] = win[j] * w[j] with w[j] = 2j / N for j < N / 2 and 2 - 2j / N for j >= N / 2 (what
+ * the two applyGainRamp calls accumulate; exact in float).  The product is always formed: an inf under w[0] = 0 becomes NaN.
+ * Magnitudes.  X = the forward transform of x by the reference FFT's butterfly DAG (radix 4 while it divides, then one radix 2; decimation in
+ * time; table twiddles, phase in double rounded to float; plain fp32, nothing fused) -- the DAG of every transform in this library.  For
+ * 0 <= b <= N / 2: m[b] = sqrt (fl32 (fl32 (re * re) + fl32 (im * im))), the square root correctly rounded.  Frame f of channel c lies at
+ * magnitudes[(f * C + c) * B + b]: frame-major, so that every frame is the [C][B] block the per-frame entries above take.
+ * Energy (:249, :705-716 for one channel).  e = +0; for b ascending e = fl32 (e + m[b]); stored at energy[c * D + f]. */
+enum { FX_OFFLINE_CENTROID = 0, FX_OFFLINE_SLOPE, FX_OFFLINE_SPREAD, FX_OFFLINE_FLATNESS, FX_OFFLINE_FLUX, FX_OFFLINE_ZERO_CROSSES,
+       FX_OFFLINE_F0, FX_OFFLINE_HER, FX_OFFLINE_INHARMONICITY, FX_OFFLINE_AUDIO, FX_OFFLINE_FEATURE_ROWS };   /* AudioFeatures.h:20-31, less FFT */
+enum { FX_OFFLINE_DO_SPECTRAL = 1, FX_OFFLINE_DO_HARMONIC = 2, FX_OFFLINE_DO_ZERO_CROSSES = 4, FX_OFFLINE_DO_AUDIO = 8,
+       FX_OFFLINE_DO_NORMALISE_AUDIO = 16, FX_OFFLINE_DO_LOG_ATTACK = 32 };
+#define FX_OFFLINE_SCRATCH_BYTES (16u << 20)
+/* The frame / window / magnitude stage alone.  Refused (FX_ERR_INVALID_ARGUMENT, fx_last_error names the value; nothing launched): a null
+ * o, audio or magnitudes; S < 1; D < 1; D > S (step 0, the reference's jassert); N outside the set; D == 1 with N > S (:157); an unknown
+ * mem_kind. */
+fx_status fx_offline_frames(fx_offline* o, const float* audio, int num_samples, int num_downsamples, int window_size,
+                            float* magnitudes /* [D][C][N/2+1] */, float* energy /* [C][D] or NULL */, int mem_kind);
+/* The whole analysis; bit-identical to calling the pieces.  For f ascending, on frame f's [C][B] block: (1) fx_offline_spectral_characteristics,
+ * out4 -> rows CENTROID, SPREAD, FLATNESS, FLUX at index f; (2) fx_offline_spectral_slope -> row SLOPE; (3) fx_offline_harmonic_characteristics,
+ * out3 -> rows F0, HER, INHARMONICITY (the order of :229-246); (1)-(2) under DO_SPECTRAL, (3) under DO_HARMONIC.  The object's state
+ * (previousBinMagnitudes, previousF0) enters the call as it stands and leaves as the last frame left it.  Then, independent of the loop:
+ *   DO_ZERO_CROSSES     fx_offline_zero_crosses into row ZERO_CROSSES.
+ *   DO_AUDIO            fillDownsampledRMSAudioChannels (AudioFeatures.h:158-184), spb = S div D.  If spb == 1: row[i] = audio[i], i < D.
+ *                       Otherwise row[i] = fl32 (sqrt_f64 (sum / fl64 (spb))), sum = +0.0 (fp64) and, for s ascending over the step,
+ *                       sum += fl64 (fl32 (a * a)); the sum is serial.
+ *   DO_NORMALISE_AUDIO  (needs DO_AUDIO) AudioFeatures.h:186-195 with the stand-in's findMinMax: lo = hi = row[0]; for i >= 1: if
+ *                       row[i] < lo then lo = row[i]; if row[i] > hi then hi = row[i]; m = jmax (|lo|, |hi|) with jmax (a, b) = a < b ? b : a;
+ *                       row[i] = row[i] * (1.0f / m).  Exactly these comparisons: they fix what a NaN does; an all-zero row becomes NaN.
+ *   DO_LOG_ATTACK       setLogAttackTime (:611-622) of each channel's energy row into log_attack_time[c].
+ * features[(r * C + c) * D + i] is the reference's arrayStartIndex with numFeatureChannels = C; rows not asked for are +0.
+ * With magnitudes != NULL the whole [D][C][B] goes to the caller; with NULL the call works through a scratch the object owns, in chunks of
+ * F = max (1, FX_OFFLINE_SCRATCH_BYTES div (4 * C * B)) frames: the same bits either way.
+ * Refused before any launch or state change, besides fx_offline_frames' list (features takes the place of magnitudes): DO_NORMALISE_AUDIO
+ * without DO_AUDIO; DO_LOG_ATTACK with a null log_attack_time or sample_rate < 1000 (fx_offline_log_attack_time's rule); DO_SPECTRAL while
+ * the object's previousBinMagnitudes holds another number of bins (fx_offline_spectral_characteristics' rule). */
+fx_status fx_offline_analyse(fx_offline* o, const float* audio, int num_samples, int num_downsamples, int window_size, int sample_rate,
+                             unsigned what, float* features /* [10][C][D] */, float* energy /* [C][D] or NULL */,
+                             float* log_attack_time /* [C] or NULL */, float* magnitudes /* [D][C][N/2+1] or NULL */, int mem_kind);
+
 /* ---- OSC sink helpers (host side, no GPU) ---- */
 /* Re-order one 12-slot vector into the wire order of
  * sender.send(bundleAddress, onset, rms, f0, centroid, slope, spread, flatness,

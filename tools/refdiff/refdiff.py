@@ -194,3 +194,40 @@ def legacy_auto_correlation(data, nyquist):
     out = _legacy(7, C, B, 0, 0, float(nyquist), data)
     n = C * B * 2 * 4
     return np.frombuffer(out[:n], np.float32).reshape(C, B, 2).copy(), np.frombuffer(out[n:], np.float64).copy()
+
+
+# ---- the offline analysis up to the feature buffer (AudioAnalysis.h:129-251, AudioFeatures.h:124-195; refdiff_buffer.cpp) ----
+def build_buffer():
+    os.makedirs(BUILD, exist_ok=True)
+    exe = os.path.join(BUILD, "refdiff_buffer")
+    srcs = [os.path.join(HERE, "refdiff_buffer.cpp"), os.path.join(HERE, "juce_standin.h")]
+    if os.path.exists(exe) and all(os.path.getmtime(s) <= os.path.getmtime(exe) for s in srcs):
+        return exe
+    subprocess.check_call(["g++", "-std=c++14", "-O2", "-w", "-ffp-contract=off", "-fno-fast-math", "-DREFDIFF_LOG10_CR",
+                           "-I", REFERENCE, "-I", HERE, srcs[0], "-o", exe])
+    return exe
+
+
+def _buffer(op, audio, num_downsamples, window_size):
+    import tempfile
+    audio = np.ascontiguousarray(audio, np.float32).reshape(-1)
+    exe = build_buffer()
+    with tempfile.TemporaryDirectory() as tmp:
+        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        with open(fin, "wb") as f:
+            f.write(struct.pack("<4i", op, audio.shape[0], int(num_downsamples), int(window_size)))
+            f.write(audio.tobytes())
+        subprocess.check_call([exe, fin, fout])
+        return np.fromfile(fout, np.float32)
+
+
+def buffer_last_frame(audio, num_downsamples, window_size):
+    """audio [S] (one channel) -> fftIn [window_size] after AudioAnalyser::performSpectralAnalysis (harmonic analysis off): the last frame's
+    windowed input."""
+    return _buffer(1, audio, num_downsamples, window_size)
+
+
+def buffer_audio_row(audio, num_downsamples):
+    """audio [S] (one channel) -> (the Audio row [D] after fillDownsampledRMSAudioChannels, and after normaliseAudioChannels)"""
+    out = _buffer(2, audio, num_downsamples, 0)
+    return out[:num_downsamples].copy(), out[num_downsamples:].copy()
