@@ -48,6 +48,8 @@ LAUNCH_RECORD_CAP = 8
 OFFLINE_DO_SPECTRAL, OFFLINE_DO_HARMONIC, OFFLINE_DO_ZERO_CROSSES, OFFLINE_DO_AUDIO, OFFLINE_DO_NORMALISE_AUDIO, OFFLINE_DO_LOG_ATTACK = 1, 2, 4, 8, 16, 32
 OFFLINE_SCRATCH_BYTES = 16 << 20
 OFFLINE_WINDOWS = (256, 512, 1024, 2048, 4096)
+OFFLINE_SORT_CHUNK = 8192           # FX_OFFLINE_SORT_CHUNK: the longest row fx_offline_feature_distribution sorts wholly in LDS
+OFFLINE_SMOOTHED_FEATURES, OFFLINE_MAX_SMOOTHING_DEPTH = 9, 64      # SmoothedFeatures' rows (ref AudioFeatures.h:360), fx_offline_smoothing's depths
 
 
 class OscSenderStats(ctypes.Structure):
@@ -143,6 +145,8 @@ def _prototypes():
         ("fx_offline_get_previous_bins", [vp, dp, i], st), ("fx_offline_spectral_slope", [vp, vp, i, vp, i], st),
         ("fx_offline_auto_correlation", [vp, vp, i, vp, vp, i], st),
         ("fx_offline_frames", [vp, vp, i, i, i, vp, vp, i], st), ("fx_offline_analyse", [vp, vp, i, i, i, i, u, vp, vp, vp, vp, i], st),
+        ("fx_offline_feature_ranges", [vp, vp, i, i, vp, i], st), ("fx_offline_feature_distribution", [vp, vp, i, i, i, vp, i], st),
+        ("fx_offline_smoothing", [vp, i], st), ("fx_offline_smooth_rows", [vp, vp, i, i, i, vp, i], st), ("fx_offline_get_smoothing", [vp, fp, fp], st),
         ("fx_pack_osc12", [fp, fp], None), ("fx_pack_osc10", [fp, fp], None), ("fx_osc_encode", [cp, fp, P(ctypes.c_ubyte), i], st),
         ("fx_osc_message_bytes", [cp, i], st), ("fx_osc_encode_batch", [cp, i, i, fp, vp, i, ip], st),
         ("fx_get_osc_datagrams", [vp, cp, i, vp, i, ip, i], st),

@@ -13,24 +13,9 @@
 
 #include "fx_context.h"
 #include "fx_offline_frames.h"
+#include "fx_offline_object.h"
 
 #pragma clang fp contract(off)
-
-struct fx_offline {
-    int device = 0;
-    int C = 0;
-    double nyquist = 24000.0;
-    hipStream_t stream = nullptr;
-    double* d_prev_f0 = nullptr;        // [C] previousF0 of each channel's analyser (ref AudioAnalysis.h:109,293,697)
-    double* d_prev_bins = nullptr;      // [C][prev_bins] previousBinMagnitudes of each channel's analyser (ref :120-121,510,700); null until first used
-    int     prev_bins = 0;
-    void*   d_in = nullptr;  size_t in_cap = 0;      // staging for host buffers
-    void*   d_out = nullptr; size_t out_cap = 0;
-    // the offline driver (fx_offline_frames / fx_offline_analyse)
-    float*  d_table[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};    // the forward table of each window size, made on first use
-    void*   d_scratch = nullptr; size_t scratch_cap = 0;                   // magnitudes of one chunk of frames, when the caller keeps none
-    void*   d_work = nullptr; size_t work_cap = 0;                         // the per-frame results of a call [D][C][4 | 1 | 3], an energy envelope nobody asked for
-};
 
 namespace {
 
@@ -528,6 +513,8 @@ fx_status fx_offline_destroy(fx_offline* o)
     for (float* t : o->d_table) if (t) (void) hipFree(t);
     if (o->d_scratch) (void) hipFree(o->d_scratch);
     if (o->d_work) (void) hipFree(o->d_work);
+    if (o->d_smooth_current) (void) hipFree(o->d_smooth_current);
+    if (o->d_smooth_history) (void) hipFree(o->d_smooth_history);
     if (o->stream) (void) hipStreamDestroy(o->stream);
     delete o;
     return FX_OK;

@@ -159,7 +159,62 @@ class AudioAnalyser:
         if spectral:
             self._bins = N // 2 + 1
         features, energy, lat, mags = self._finish(kind, features, energy, lat, mags)
-        return ConcatenatedFeatureBuffer(features, energy, lat, mags, D, int(sample_rate))
+        return ConcatenatedFeatureBuffer(features, energy, lat, mags, D, int(sample_rate), analyser=self)
+
+    # ---- what the reference derives from a feature buffer (fx_offline_feature_ranges / _distribution / _smooth_rows) ----
+    def _feature_rows(self, rows, least=1):
+        """rows [R][C][D] (numpy: through host memory; a CUDA torch tensor: used where it lies) -> (the array or tensor to keep alive, its
+        address, R, D, memory kind, an allocator of float32 results beside it)"""
+        if _is_device_tensor(rows):
+            import torch
+            if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[1] != self.num_channels or rows.shape[0] < least:
+                raise ValueError("expected [>= %d][%d][num_downsamples] float32" % (least, self.num_channels))
+            rows = rows.contiguous()
+            torch.cuda.current_stream(rows.device).synchronize()         # the library reads it on a stream of its own
+            return rows, rows.data_ptr(), int(rows.shape[0]), int(rows.shape[2]), capi.MEM_DEVICE, lambda *shape: torch.empty(shape, dtype=torch.float32, device=rows.device)
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 3 or rows.shape[1] != self.num_channels or rows.shape[0] < least:
+            raise ValueError("expected [>= %d][%d][num_downsamples] float32" % (least, self.num_channels))
+        return rows, rows.ctypes.data, int(rows.shape[0]), int(rows.shape[2]), capi.MEM_HOST, lambda *shape: np.empty(shape, np.float32)
+
+    def feature_ranges(self, rows):                                                          # ref AudioFeatures.h:208-213, per row and channel
+        """rows [R][C][D] -> [R][C][2]: getFeatureRange's (start, end) of every row and channel"""
+        keep, address, R, D, kind, new = self._feature_rows(rows)
+        out = new(R, self.num_channels, 2)
+        capi.check(self._lib.fx_offline_feature_ranges(self._h, address, R, D, _address(out), kind))
+        return self._finish(kind, out)[0]
+
+    def discrete_feature_distribution(self, rows, num_brackets):                             # ref AudioFeatures.h:215-240
+        """rows [R][C][D] -> [R][C][num_brackets]: getDiscreteFeatureDistribution of every row and channel"""
+        keep, address, R, D, kind, new = self._feature_rows(rows)
+        nb = int(num_brackets)
+        if nb < 1:                                           # (the library refuses it too: the shape below needs it first)
+            raise capi.FxError(capi.FX_ERR_INVALID_ARGUMENT, "num_brackets %d" % nb)
+        out = new(R, self.num_channels, nb)
+        capi.check(self._lib.fx_offline_feature_distribution(self._h, address, R, D, nb, _address(out), kind))
+        return self._finish(kind, out)[0]
+
+    def smoothing(self, depth):                                                              # ref AudioFeatures.h:358-369
+        """construct every channel's SmoothedFeatures (depth 1 .. 64) anew; 0 frees them"""
+        capi.check(self._lib.fx_offline_smoothing(self._h, int(depth)))
+        self._smoothing_depth = int(depth)
+
+    def smooth_rows(self, rows, first=0, count=None):                                        # ref AudioFeatures.h:371-379
+        """rows [R >= 9][C][D]: updateValues on columns first .. first + count - 1 (count None: to the end) -> current values [9][C][count]"""
+        keep, address, R, D, kind, new = self._feature_rows(rows, capi.OFFLINE_SMOOTHED_FEATURES)
+        count = D - int(first) if count is None else int(count)
+        out = new(capi.OFFLINE_SMOOTHED_FEATURES, self.num_channels, max(count, 1))
+        capi.check(self._lib.fx_offline_smooth_rows(self._h, address, D, int(first), count, _address(out), kind))
+        return self._finish(kind, out)[0]
+
+    def smoothed_state(self):                                                                # ref AudioFeatures.h:382-383
+        """-> (currentFeatureValues [9][C], featureHistory [9][C][depth]) of the channels' smoothers"""
+        depth = getattr(self, "_smoothing_depth", 0)
+        current = np.empty((capi.OFFLINE_SMOOTHED_FEATURES, self.num_channels), np.float32)
+        history = np.empty((capi.OFFLINE_SMOOTHED_FEATURES, self.num_channels, depth), np.float32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        capi.check(self._lib.fx_offline_get_smoothing(self._h, current.ctypes.data_as(fp), history.ctypes.data_as(fp)))
+        return current, history
 
 
 def _is_device_tensor(a):
@@ -176,7 +231,8 @@ class ConcatenatedFeatureBuffer:
     """The results of AudioAnalyser.perform_spectral_analysis under the reference's names (ref AudioFeatures.h:14-314), on the host.
     `feature` arguments are the FX_OFFLINE_* row numbers (capi.OFFLINE_CENTROID .. capi.OFFLINE_AUDIO)."""
 
-    def __init__(self, feature_buffer, energy_envelope, estimated_log_attack_time, magnitudes, num_downsamples, sample_rate):
+    def __init__(self, feature_buffer, energy_envelope, estimated_log_attack_time, magnitudes, num_downsamples, sample_rate, analyser=None):
+        self._analyser = analyser                                       # the AudioAnalyser whose GPU derives ranges and distributions
         self.feature_buffer = feature_buffer                            # [10][C][D]: featureBuffer, less its FFT part
         self.energy_envelope = energy_envelope                          # [C][D]
         self.estimated_log_attack_time = estimated_log_attack_time      # [C], or None if not analysed
@@ -201,6 +257,19 @@ class ConcatenatedFeatureBuffer:
                 hi = v
         return lo, hi
 
+    def _gpu(self):
+        if self._analyser is None:
+            raise ValueError("this buffer was made without an analyser (ConcatenatedFeatureBuffer(..., analyser=...))")
+        return self._analyser
+
+    def feature_ranges(self):                                                               # ref :208-213, per row and channel, on the GPU
+        """-> [10][C][2]: every row's (start, end), each channel a file of its own"""
+        return self._gpu().feature_ranges(self.feature_buffer)
+
+    def get_discrete_feature_distribution(self, feature, num_brackets):                     # ref :215-240, on the GPU
+        """-> [C][num_brackets]"""
+        return self._gpu().discrete_feature_distribution(self.feature_buffer[int(feature)][None], num_brackets)[0]
+
     def get_average_feature_sample(self, feature, index):                                   # ref :266-275: a serial float sum
         av = np.float32(0.0)
         for c in range(self.num_feature_channels):
@@ -211,3 +280,54 @@ class ConcatenatedFeatureBuffer:
         if self.magnitudes is None:
             raise ValueError("the analysis kept no magnitudes (keep_fft=False)")
         return self.magnitudes[:, int(channel), :].T
+
+
+class Range:
+    """JUCE's Range<float> as far as FeatureSpace uses it: the constructor keeps end >= start, and each setter moves the other end along
+    (tools/refdiff/juce_standin.h:55-66)."""
+
+    def __init__(self, start=0.0, end=0.0):
+        start, end = np.float32(start), np.float32(end)
+        self.start, self.end = start, (start if end < start else end)
+
+    def set_start(self, start):
+        self.start = np.float32(start)
+        if self.end < self.start:
+            self.end = self.start
+
+    def set_end(self, end):
+        self.end = np.float32(end)
+        if self.end < self.start:
+            self.start = self.end
+
+    def __iter__(self):
+        return iter((self.start, self.end))
+
+
+class FeatureSpace:
+    """ref AudioFeatures.h:319-349: four ranges that describe a file, folded over a corpus by compare_and_update_ranges.  A handful of
+    floats per file: host arithmetic, fed by the GPU's ranges (from_buffer)."""
+
+    def __init__(self, attack=None, centroid_range=None, slope_range=None, crosses_range=None):
+        self.attack_range = Range() if attack is None else Range(attack, 0.0)               # :331
+        self.spectral_centroid_range = centroid_range if centroid_range is not None else Range()
+        self.spectral_slope_range = slope_range if slope_range is not None else Range()
+        self.zero_crosses_range = crosses_range if crosses_range is not None else Range()
+
+    @staticmethod
+    def compare_and_update_ranges(existing_range, new_range):                               # :337-343, as written: both tests are `<`
+        if new_range.start < existing_range.start:
+            existing_range.set_start(new_range.start)
+        if new_range.end < existing_range.end:
+            existing_range.set_end(new_range.end)
+
+    @classmethod
+    def from_buffer(cls, buffer, channel, ranges=None):
+        """the space of one channel (a mono file) of an analysed buffer: its estimated log attack time and the GPU's centroid, slope and
+        zero-crossing ranges (ranges: buffer.feature_ranges(), when the caller already has them)"""
+        if buffer.estimated_log_attack_time is None:
+            raise ValueError("the analysis estimated no log attack time (log_attack=False)")
+        ranges = buffer.feature_ranges() if ranges is None else ranges
+        c = int(channel)
+        return cls(buffer.estimated_log_attack_time[c], Range(*ranges[capi.OFFLINE_CENTROID, c]), Range(*ranges[capi.OFFLINE_SLOPE, c]),
+                   Range(*ranges[capi.OFFLINE_ZERO_CROSSES, c]))

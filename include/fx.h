@@ -872,6 +872,53 @@ fx_status fx_offline_analyse(fx_offline* o, const float* audio, int num_samples,
                              unsigned what, float* features /* [10][C][D] */, float* energy /* [C][D] or NULL */,
                              float* log_attack_time /* [C] or NULL */, float* magnitudes /* [D][C][N/2+1] or NULL */, int mem_kind);
 
+/* ---- what the reference derives from a feature buffer: ranges, discrete distributions, smoothed features (AudioFeatures.h:208-240,
+ * :356-421) ----
+ * rows is [R][C][D] fp32, any R = num_rows rows of a feature buffer: rows[(r * C + c) * D + i] is the reference's arrayStartIndex with
+ * numFeatureChannels = C (fx_offline_analyse's features with R = FX_OFFLINE_FEATURE_ROWS is the whole buffer).  As everywhere in the
+ * driver a channel is a mono file: what the reference takes over numDownsamples * numFeatureChannels samples is taken per channel.
+ * FX_MEM_HOST buffers are copied synchronously, FX_MEM_DEVICE buffers are 4-byte aligned and used asynchronously on the object's stream
+ * (fx_offline_sync waits).  Every entry refuses (FX_ERR_INVALID_ARGUMENT, fx_last_error names the value; nothing launched, no state
+ * changed): a null argument, num_rows < 1, num_downsamples < 1, num_rows * C > 2^31 - 1, an unknown mem_kind, and what it lists itself. */
+/* getFeatureRange (AudioFeatures.h:208-213) of every row and channel, with the stand-in's findMinMax (the chain DO_NORMALISE_AUDIO states):
+ * lo = hi = row[0]; for i >= 1 ascending: if row[i] < lo then lo = row[i]; if row[i] > hi then hi = row[i].  out[(r * C + c) * 2] = lo,
+ * [.. + 1] = hi.  Exactly these comparisons: a NaN at row[0] is both ends for ever; a NaN elsewhere is stepped over; among values that
+ * compare equal the FIRST occurrence wins, which decides the sign of a zero extreme (+0, -0 gives lo = +0; -0, +0 gives lo = -0). */
+fx_status fx_offline_feature_ranges(fx_offline* o, const float* rows, int num_rows, int num_downsamples, float* out /* [R][C][2] */, int mem_kind);
+/* getDiscreteFeatureDistribution (AudioFeatures.h:215-240) of every (row, channel): sorted = the row's D values ascending; step = D div
+ * num_brackets; for bracket b: av = +0.0f; for s from b * step to (b + 1) * step - 1 ascending av = fl32 (av + sorted[s]);
+ * out[(r * C + c) * num_brackets + b] = fl32 (av / fl32 (step)).  The sum is serial fp32 in sorted order; the D - num_brackets * step largest
+ * values are not used; step == 0 (num_brackets > D) is 0.0f / 0.0f: every bracket NaN, as in the reference.
+ * Where the reference is undefined, OURS: the order is by value (-0 and +0 in either order: from av = +0.0f it cannot change a sum); every
+ * NaN sorts after +inf (std::sort on a NaN is undefined); subnormals are ordered as the numbers they are, never flushed (the sort key is
+ * the float's bits: b ^ 0x80000000 for b >= 0, ~b for b < 0, 0xFFFFFFFF for a NaN).
+ * A row of up to FX_OFFLINE_SORT_CHUNK values is sorted by one workgroup wholly in LDS, which then walks the brackets, a lane each.  8192
+ * keys = 32 KiB at the most (five workgroups in a CU's 160 KiB, where 16384 keys would leave two), and the allocation is the row's power
+ * of two: the common D of a few thousand takes 16 KiB or less, so the CU's 32 waves, not its LDS, bound it at eight workgroups.  Longer rows are padded to a power of two P in the object's scratch,
+ * max (1, FX_OFFLINE_SCRATCH_BYTES div (4 * P)) rows at a time: chunks sorted in LDS, bitonic steps of stride >= chunk in global memory, the
+ * rest of each merge in LDS again.  The same bits whichever path and however the rows are grouped.
+ * Refused as well: num_brackets < 1; num_downsamples > FX_OFFLINE_SCRATCH_BYTES / 4 (one padded row exceeds the scratch). */
+#define FX_OFFLINE_SORT_CHUNK 8192
+fx_status fx_offline_feature_distribution(fx_offline* o, const float* rows, int num_rows, int num_downsamples, int num_brackets,
+                                          float* out /* [R][C][num_brackets] */, int mem_kind);
+/* SmoothedFeatures (AudioFeatures.h:356-421), one per channel, its state on the device.  depth in [1, 64] constructs every channel's
+ * smoother anew (:358-369): currentFeatureValues[9] = 0, featureHistory[9][depth] = 0; depth 0 frees it; anything else is refused (the
+ * reference's historyLength - 1 on a size_t makes 0 a crash there).  Another object than the analyser in the reference: fx_offline_reset
+ * does not touch it.  Synchronises the object's stream. */
+fx_status fx_offline_smoothing(fx_offline* o, int depth);
+/* updateValues (AudioFeatures.h:371-379) for i = first .. first + count - 1 ascending, on the buffer whose sample 0 is column i of rows
+ * (R >= 9 rows, CENTROID .. INHARMONICITY leading; new = rows[(f * C + c) * D + i]).  updateHistory (:399-409): history[k] = history[k + 1]
+ * for k < depth - 1, history[depth - 1] = current.  Then for features f = 0 .. 8 (:387-394, :411-420): av = +0.0f; av = fl32 (av + history[k])
+ * for k ascending; av = fl32 (av / fl32 (fl32 (depth) + 1)) (:418, (float) historyLength + 1); current = fl32 (av + fl32 (fl32 (new - av) *
+ * 0.5f)) (JUCE_LIVE_CONSTANT (0.5f); nothing fused).  out[(f * C + c) * count + (i - first)] = current after update i; out may be NULL.
+ * first = 0, count = 1 is the reference's call; count = D smooths whole rows in one launch.  The state carries from call to call.
+ * Refused as well: no smoother constructed; first < 0; count < 1; first + count > D. */
+fx_status fx_offline_smooth_rows(fx_offline* o, const float* rows, int num_downsamples, int first, int count,
+                                 float* out /* [9][C][count] or NULL */, int mem_kind);
+/* The smoothers' state (AudioFeatures.h:382-383) on the host, after everything enqueued so far: currentFeatureValues and featureHistory
+ * (oldest entry first); either may be NULL.  FX_ERR_INVALID_ARGUMENT without a smoother. */
+fx_status fx_offline_get_smoothing(fx_offline* o, float* current /* [9][C] */, float* history /* [9][C][depth] */);
+
 /* ---- OSC sink helpers (host side, no GPU) ---- */
 /* Re-order one 12-slot vector into the wire order of
  * sender.send(bundleAddress, onset, rms, f0, centroid, slope, spread, flatness,

@@ -727,11 +727,65 @@ public:
         if (peakBins != nullptr) *peakBins = peaks;
         return freqs;
     }
+    // ref AudioFeatures.h:208-213, per row and channel: rows [numRows][channels][numDownsamples] -> [numRows][channels][2] = (start, end)
+    std::vector<float> getFeatureRanges (const float* rows, int numRows, int numDownsamples)
+    {
+        std::vector<float> out ((std::size_t) numRows * channels * 2);
+        check (fx_offline_feature_ranges (off, rows, numRows, numDownsamples, out.data(), FX_MEM_HOST));
+        return out;
+    }
+    // ref AudioFeatures.h:215-240, per row and channel: -> [numRows][channels][numBrackets]
+    std::vector<float> getDiscreteFeatureDistribution (const float* rows, int numRows, int numDownsamples, int numBrackets)
+    {
+        std::vector<float> out ((std::size_t) numRows * channels * (std::size_t) (numBrackets > 0 ? numBrackets : 0));
+        check (fx_offline_feature_distribution (off, rows, numRows, numDownsamples, numBrackets, out.data(), FX_MEM_HOST));
+        return out;
+    }
     fx_offline* handle() { return off; }
 
 private:
     fx_offline* off = nullptr;
     int channels;
+};
+
+// JUCE's Range<float> as far as FeatureSpace uses it: the constructor keeps end >= start, and each setter moves the other end along.
+class Range
+{
+public:
+    Range() = default;
+    Range (float rangeStart, float rangeEnd) : start (rangeStart), end (rangeEnd < rangeStart ? rangeStart : rangeEnd) {}
+    float getStart() const { return start; }
+    float getEnd() const { return end; }
+    void setStart (float newStart) { start = newStart; if (end < newStart) end = newStart; }
+    void setEnd (float newEnd) { end = newEnd; if (newEnd < start) start = newEnd; }
+
+private:
+    float start = 0.0f, end = 0.0f;
+};
+
+// ref Source/AudioFeatures.h:319-349: four ranges that describe a file, folded over a corpus by compareAndUpdateRanges.  A handful of
+// floats per file, so it stays on the host; fx_offline_feature_ranges feeds it (fromRanges).
+struct FeatureSpace
+{
+    FeatureSpace() = default;
+    FeatureSpace (float attack, Range centroidRange, Range slopeRange, Range crossesRange)                  // ref :327-335
+    :   attackRange (Range (attack, 0.0f)), spectralCentroidRange (centroidRange), spectralSlopeRange (slopeRange), zeroCrossesRange (crossesRange)
+    {}
+    // ref :337-343, as written: both tests are `<`, and the setters couple the two ends
+    static void compareAndUpdateRanges (Range& existingRange, Range& newRange)
+    {
+        if (newRange.getStart() < existingRange.getStart()) existingRange.setStart (newRange.getStart());
+        if (newRange.getEnd() < existingRange.getEnd()) existingRange.setEnd (newRange.getEnd());
+    }
+    // one channel (a mono file) of an analysed buffer: ranges [>= FX_OFFLINE_ZERO_CROSSES + 1][numChannels][2] of fx_offline_feature_ranges
+    // on fx_offline_analyse's features, logAttackTime [numChannels]
+    static FeatureSpace fromRanges (const float* ranges, const float* logAttackTime, int numChannels, int channel)
+    {
+        auto range = [&] (int row) { const float* p = ranges + ((std::size_t) row * numChannels + channel) * 2; return Range (p[0], p[1]); };
+        return FeatureSpace (logAttackTime[channel], range (FX_OFFLINE_CENTROID), range (FX_OFFLINE_SLOPE), range (FX_OFFLINE_ZERO_CROSSES));
+    }
+
+    Range attackRange, spectralCentroidRange, spectralSlopeRange, zeroCrossesRange;
 };
 
 // The datagram OSCSender::send (bundleAddress, onset, rmsLevel, f0, centroid, slope, spread, flatness,

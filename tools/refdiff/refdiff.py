@@ -231,3 +231,56 @@ def buffer_audio_row(audio, num_downsamples):
     """audio [S] (one channel) -> (the Audio row [D] after fillDownsampledRMSAudioChannels, and after normaliseAudioChannels)"""
     out = _buffer(2, audio, num_downsamples, 0)
     return out[:num_downsamples].copy(), out[num_downsamples:].copy()
+
+
+# ---- what the reference derives from a feature buffer (AudioFeatures.h:208-240, :319-349, :356-421; refdiff_stats.cpp) ----
+def build_stats():
+    os.makedirs(BUILD, exist_ok=True)
+    exe = os.path.join(BUILD, "refdiff_stats")
+    srcs = [os.path.join(HERE, "refdiff_stats.cpp"), os.path.join(HERE, "juce_standin.h")]
+    if os.path.exists(exe) and all(os.path.getmtime(s) <= os.path.getmtime(exe) for s in srcs):
+        return exe
+    subprocess.check_call(["g++", "-std=c++14", "-O2", "-w", "-ffp-contract=off", "-fno-fast-math", "-DREFDIFF_LOG10_CR",
+                           "-I", REFERENCE, "-I", HERE, srcs[0], "-o", exe])
+    return exe
+
+
+def _stats(op, a, b, payload):
+    import tempfile
+    exe = build_stats()
+    with tempfile.TemporaryDirectory() as tmp:
+        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        with open(fin, "wb") as f:
+            f.write(struct.pack("<4i", op, int(a), int(b), 0))
+            f.write(np.ascontiguousarray(payload, np.float32).tobytes())
+        subprocess.check_call([exe, fin, fout])
+        return np.fromfile(fout, np.float32)
+
+
+def stats_feature_range(row):
+    """row [D] (one channel) -> float32 [2]: getFeatureRange's start and end"""
+    row = np.ascontiguousarray(row, np.float32).reshape(-1)
+    return _stats(1, row.shape[0], 0, row)
+
+
+def stats_distribution(row, num_brackets):
+    """row [D] (one channel, no NaN) -> getDiscreteFeatureDistribution [num_brackets]"""
+    row = np.ascontiguousarray(row, np.float32).reshape(-1)
+    assert not np.isnan(row).any(), "std::sort is undefined on a NaN"
+    return _stats(2, row.shape[0], num_brackets, row)
+
+
+def stats_smoothing(depth, values):
+    """values [updates][9]: one SmoothedFeatures (depth), updateValues on a one-sample buffer per row -> (currentFeatureValues after each
+    update [updates][9], featureHistory at the end [9][depth])"""
+    values = np.ascontiguousarray(values, np.float32).reshape(-1, 9)
+    out = _stats(3, depth, values.shape[0], values)
+    n = values.shape[0] * 9
+    return out[:n].reshape(-1, 9).copy(), out[n:].reshape(9, int(depth)).copy()
+
+
+def stats_feature_space(spaces):
+    """spaces [n][7] = attack, then (start, end) of the centroid, slope and zero-crossing ranges: FeatureSpace of each; space 0 as constructed
+    and after compareAndUpdateRanges with each later one -> [n][8], the four ranges' (start, end)"""
+    spaces = np.ascontiguousarray(spaces, np.float32).reshape(-1, 7)
+    return _stats(4, spaces.shape[0], 0, spaces).reshape(-1, 8).copy()
