@@ -32,9 +32,75 @@ fx_status fx_fail(fx_status code, const char* fmt, ...)
 fx_status fx_check_call(int sample_format, int in_kind, int out_kind)
 {
     if (!known_format(sample_format)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown sample format %d", sample_format);
-    for (int kind : {in_kind, out_kind})
-        if (kind != FX_MEM_HOST && kind != FX_MEM_DEVICE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", kind);
+    const fx_status st = fx_check_memory_kind(in_kind);
+    return st != FX_OK ? st : fx_check_memory_kind(out_kind);
+}
+
+fx_status fx_check_memory_kind(int kind)
+{
+    if (kind != FX_MEM_HOST && kind != FX_MEM_DEVICE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", kind);
     return FX_OK;
+}
+
+// ---- what the attached units share (fx_context.h states each contract) ----
+fx_status fx_check_channel_list(const fx_context* c, const int* channels, int num_channels)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    if (num_channels < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative channel count %d", num_channels);
+    if (num_channels > 0 && !channels) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null channel list with %d entries", num_channels);
+    return FX_OK;
+}
+
+fx_status fx_check_channel_entries(const fx_context* c, const int* channels, int num_channels)
+{
+    for (int i = 0; i < num_channels; i++)
+        if (channels[i] < 0 || channels[i] >= c->C)
+            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: channel %d out of range [0,%d)", i, channels[i], c->C);
+    return FX_OK;
+}
+
+fx_status fx_require_device()
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) { (void) hipGetLastError(); return fx_fail(FX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)"); }
+    return FX_OK;
+}
+
+void fx_free_device(std::initializer_list<void*> bufs)
+{
+    for (void* b : bufs) if (b) (void) hipFree(b);
+}
+
+fx_status fx_reserve_list(fx_context* c, fx_staged_list* list, size_t entries, size_t entry_bytes)
+{
+    if (entries <= list->cap) return FX_OK;
+    size_t want = entries;
+    if (want < list->cap + list->cap / 2) want = list->cap + list->cap / 2;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    void* h = nullptr;
+    HIP_TRY(hipHostMalloc(&h, want * entry_bytes, hipHostMallocDefault));
+    void* d = nullptr;
+    {
+        const hipError_t e = hipMalloc(&d, want * entry_bytes);
+        if (e != hipSuccess) {
+            (void) hipHostFree(h);
+            return fx_fail(fx_hip_status(e), "allocating the track list failed: %s", hipGetErrorString(e));
+        }
+    }
+    void* old_d = list->device; void* old_h = list->pinned;
+    list->device = d; list->pinned = h; list->cap = want;
+    const hipError_t freed_d = old_d ? hipFree(old_d) : hipSuccess;
+    const hipError_t freed_h = old_h ? hipHostFree(old_h) : hipSuccess;
+    HIP_TRY(freed_d);
+    HIP_TRY(freed_h);
+    return FX_OK;
+}
+
+void fx_release_list(fx_staged_list* list)
+{
+    if (list->device) (void) hipFree(list->device);
+    if (list->pinned) (void) hipHostFree(list->pinned);
+    *list = fx_staged_list();
 }
 
 // Scratch that follows the largest call seen.  Growing frees and reallocates (hipFree waits for the device), so a
@@ -57,7 +123,7 @@ fx_status fx_grow(void** ptr, size_t* cap, size_t need)
     void* p = nullptr;
     hipError_t e = hipMalloc(&p, want);
     if (e != hipSuccess && want != need) { (void) hipGetLastError(); want = need; e = hipMalloc(&p, want); }
-    if (e != hipSuccess) return fx_fail(e == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e));
+    if (e != hipSuccess) return fx_fail(fx_hip_status(e), "hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e));
     *ptr = p;
     *cap = want;
     return FX_OK;
@@ -368,9 +434,8 @@ fx_status fx_destroy(fx_context* c)
     if (c->display_release) c->display_release(c);
     if (c->clips_release) c->clips_release(c);
     if (c->monitor_release) c->monitor_release(c);
-    void* bufs[] = {c->d_tw, c->d_prev, c->d_tail[0], c->d_tail[1], c->d_hist, c->d_latest,
-                    c->d_raw, c->d_part, c->d_in, c->d_out_raw, c->d_queue, c->d_carry[0], c->d_carry[1], c->d_hops, c->d_osc, c->d_chan};
-    for (void* b : bufs) if (b) (void) hipFree(b);
+    fx_free_device({c->d_tw, c->d_prev, c->d_tail[0], c->d_tail[1], c->d_hist, c->d_latest,
+                    c->d_raw, c->d_part, c->d_in, c->d_out_raw, c->d_queue, c->d_carry[0], c->d_carry[1], c->d_hops, c->d_osc, c->d_chan});
     if (c->h_err) (void) hipHostFree(c->h_err);
     if (c->h_chan_stage) (void) hipHostFree(c->h_chan_stage);
     for (int i = 0; i < 3; i++) if (c->ev[i]) (void) hipEventDestroy(c->ev[i]);

@@ -433,8 +433,7 @@ void clips_release(fx_context* c)
     fx_clips* s = c->clips;
     if (!s) return;
     for (clip_bank& b : s->banks) if (b.owned && b.mem) (void) hipFree(b.mem);
-    void* bufs[] = {s->d_rows[0], s->d_rows[1], s->d_commands, s->d_live, s->d_planar, s->d_pairs, s->d_rated};
-    for (void* b : bufs) if (b) (void) hipFree(b);
+    fx_free_device({s->d_rows[0], s->d_rows[1], s->d_commands, s->d_live, s->d_planar, s->d_pairs, s->d_rated});
     delete s;
     c->clips = nullptr;
 }
@@ -466,7 +465,7 @@ fx_status clips_state(fx_context* c, fx_clips** out)
         if (e != hipSuccess) {
             for (int k = 0; k < 2; k++) if (s->d_rows[k]) (void) hipFree(s->d_rows[k]);
             delete s;
-            return fx_fail(e == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "allocating the transport table failed: %s", hipGetErrorString(e));
+            return fx_fail(fx_hip_status(e), "allocating the transport table failed: %s", hipGetErrorString(e));
         }
         c->clips = s;
         c->clips_release = clips_release;
@@ -563,23 +562,6 @@ fx_status refresh_rated(fx_context* c, fx_clips* s)
     if (list.empty()) return FX_OK;
     HIP_TRY(hipMemcpy(s->d_rated, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice));
     s->num_rated = (int) list.size();
-    return FX_OK;
-}
-
-// fx_reset_channels' rules for a list, without the range of its entries (check_entries, once the call's own values are known good)
-fx_status check_list(const fx_context* c, const int* channels, int num_channels)
-{
-    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
-    if (num_channels < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative channel count %d", num_channels);
-    if (num_channels > 0 && !channels) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null channel list with %d entries", num_channels);
-    return FX_OK;
-}
-
-fx_status check_entries(const fx_context* c, const int* channels, int num_channels)
-{
-    for (int i = 0; i < num_channels; i++)
-        if (channels[i] < 0 || channels[i] >= c->C)
-            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: channel %d out of range [0,%d)", i, channels[i], c->C);
     return FX_OK;
 }
 
@@ -693,12 +675,12 @@ fx_status fx_destroy_clips(fx_context* c, int first_id)
 
 fx_status fx_set_channel_clips(fx_context* c, const int* channels, int num_channels, const int* clip_ids, const int* loop)
 {
-    fx_status st = check_list(c, channels, num_channels);
+    fx_status st = fx_check_channel_list(c, channels, num_channels);
     if (st != FX_OK || num_channels == 0) return st;
     if (!clip_ids) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null clip id list with %d entries", num_channels);
     for (int i = 0; i < num_channels; i++)
         if (clip_ids[i] != -1 && !bank_of(c, clip_ids[i])) return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: unknown clip id %d", i, clip_ids[i]);
-    if ((st = check_entries(c, channels, num_channels)) != FX_OK) return st;
+    if ((st = fx_check_channel_entries(c, channels, num_channels)) != FX_OK) return st;
     bool any_rated = false;
     for (int i = 0; i < num_channels; i++) {
         const clip_bank* b = bank_of(c, clip_ids[i]);
@@ -780,12 +762,12 @@ fx_status fx_get_resampler_table(float* out, int capacity, int* zero_crossings, 
 
 fx_status fx_set_channel_sources(fx_context* c, const int* channels, int num_channels, const int* types)
 {
-    fx_status st = check_list(c, channels, num_channels);
+    fx_status st = fx_check_channel_list(c, channels, num_channels);
     if (st != FX_OK || num_channels == 0) return st;
     if (!types) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null source list with %d entries", num_channels);
     for (int i = 0; i < num_channels; i++)
         if (types[i] != FX_SOURCE_INPUT && types[i] != FX_SOURCE_FILE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: unknown source %d", i, types[i]);
-    if ((st = check_entries(c, channels, num_channels)) != FX_OK) return st;
+    if ((st = fx_check_channel_entries(c, channels, num_channels)) != FX_OK) return st;
     HIP_TRY(hipSetDevice(c->device));
     fx_clips* s = nullptr;
     if ((st = clips_state(c, &s)) != FX_OK) return st;
@@ -801,11 +783,11 @@ fx_status fx_set_channel_sources(fx_context* c, const int* channels, int num_cha
 
 fx_status fx_transport(fx_context* c, const int* channels, int num_channels, int command)
 {
-    fx_status st = check_list(c, channels, num_channels);
+    fx_status st = fx_check_channel_list(c, channels, num_channels);
     if (st != FX_OK) return st;
     if (command < FX_PLAY || command > FX_RESTART) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown transport command %d", command);
     if (num_channels == 0) return FX_OK;
-    if ((st = check_entries(c, channels, num_channels)) != FX_OK) return st;
+    if ((st = fx_check_channel_entries(c, channels, num_channels)) != FX_OK) return st;
     if (command == FX_PLAY)
         for (int i = 0; i < num_channels; i++)
             if (!c->clips || c->clips->clip_of[(size_t) channels[i]] < 0)

@@ -165,7 +165,7 @@ fx_status fx_comm_create(fx_context* c, int rank, int world, const void* unique_
     m->rank = rank;
     m->world = world;
     auto bail = [&](fx_status s) { fx_comm_release(c); return s; };
-#define M_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return bail(fx_fail(e_ == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); } while (0)
+#define M_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return bail(fx_fail(fx_hip_status(e_), "%s failed: %s", #expr, hipGetErrorString(e_))); } while (0)
 #define M_NCCL(expr) do { ncclResult_t r_ = (expr); if (r_ != ncclSuccess) return bail(fx_fail(FX_ERR_HIP, "%s failed: %s", #expr, rccl()->GetErrorString(r_))); } while (0)
     ncclUniqueId id;
     memcpy(&id, unique_id, sizeof id);

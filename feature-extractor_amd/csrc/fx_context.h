@@ -1,11 +1,19 @@
 // fx_context.h -- the context behind the C ABI (include/fx.h), shared by the shim's host units (fx_capi.cpp, fx_plan.cpp, fx_stream.cpp,
 // fx_comm.cpp) and the units that attach through its hooks (fx_taps.hip, fx_interleave.hip, fx_events.hip, fx_tracks.hip,
 // fx_osc_table.hip, fx_osc_bundle.hip, fx_track_state.hip, fx_display.hip, fx_clips.hip, fx_monitor.hip).  Internal.
+//
+// What a new attached unit uses instead of copying its neighbour: a list of tracks is judged by fx_check_channel_list and
+// fx_check_channel_entries (the call's own values between the two), a memory kind by fx_check_memory_kind (or fx_check_call, with a
+// sample format); a list that travels through pinned memory to the device lives in a fx_staged_list (fx_reserve_list /
+// fx_release_list), other scratch on fx_grow; a unit that allocates before any analysis call asks fx_require_device first; a HIP
+// error becomes a status by HIP_TRY or fx_hip_status; the release hook frees its device buffers with fx_free_device.  All of it is
+// defined in fx_capi.cpp, so the fake-HIP host builds (build.py, HOST_SOURCES) bring it along.
 #ifndef FX_CONTEXT_H
 #define FX_CONTEXT_H
 
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -13,19 +21,32 @@
 
 fx_status fx_fail(fx_status code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+inline fx_status fx_hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP; }
 #define HIP_TRY(expr)                                                                           \
     do {                                                                                        \
         hipError_t e_ = (expr);                                                                 \
         if (e_ != hipSuccess)                                                                   \
-            return fx_fail(e_ == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP,       \
-                           "%s failed: %s", #expr, hipGetErrorString(e_));                     \
+            return fx_fail(fx_hip_status(e_), "%s failed: %s", #expr, hipGetErrorString(e_));  \
     } while (0)
 
 inline bool known_format(int f) { return f == FX_SAMPLE_F32 || f == FX_SAMPLE_F16 || f == FX_SAMPLE_S16 || f == FX_SAMPLE_S24; }
 inline size_t sample_size(int f) { return f == FX_SAMPLE_F32 ? 4 : (f == FX_SAMPLE_S24 ? 3 : 2); }
 // A call's sample format and the memory kinds of its input and results (an entry point passes what it has): FX_ERR_INVALID_ARGUMENT
-// for an unknown one, the format's refusal first.
+// for an unknown one, the format's refusal first.  fx_check_memory_kind: one kind alone, "unknown memory kind %d".
 fx_status fx_check_call(int sample_format, int in_kind = FX_MEM_HOST, int out_kind = FX_MEM_HOST);
+fx_status fx_check_memory_kind(int kind);
+
+// The contract of every entry that takes a list of tracks, in two steps because a setter judges the values it brings between them
+// ("the call's own values, then the range of its entries"); no device use.  fx_check_channel_list: "null context", "negative channel
+// count %d", "null channel list with %d entries".  fx_check_channel_entries (of a list that passed the first): the first entry outside
+// [0, C), "entry %d: channel %d out of range [0,%d)".
+fx_status fx_check_channel_list(const fx_context* ctx, const int* channels, int num_channels);
+fx_status fx_check_channel_entries(const fx_context* ctx, const int* channels, int num_channels);
+
+// FX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)", unless the runtime reports a device
+fx_status fx_require_device();
+// hipFree of every pointer that is not null, in order; failures are ignored (a release hook has nobody to tell)
+void fx_free_device(std::initializer_list<void*> bufs);
 
 // Scratch that follows the largest call seen (fx_capi.cpp): *ptr holds at least `need` bytes afterwards, or is null (capacity 0) with
 // FX_ERR_OUT_OF_MEMORY / FX_ERR_HIP.  What the buffer held is not kept.
@@ -37,6 +58,21 @@ template <typename T> fx_status fx_grow(T** ptr, size_t* cap, size_t need)
     *ptr = static_cast<T*>(p);
     return st;
 }
+
+// A list a call fills on the host and a kernel reads: pinned memory (what an upload in flight reads) and its device copy, `cap`
+// entries each.  fx_reserve_list: room for `entries` of entry_bytes (the same size at every call); no HIP call when they fit.  It
+// grows by at least half again, as fx_grow: a host whose lists get longer does not pay a free (it waits for the device) and a pinned
+// allocation per call.  Growing waits for the context's stream first (a copy in flight may read the old pair), allocates the new
+// pair before the old one goes -- a failed allocation ("allocating the track list failed: %s") leaves the old lists in place -- and
+// attempts both frees before it reports the first that failed: the new lists are in place either way.  What the lists held is not kept.
+// fx_release_list: frees both (nothing to do for an empty list) and leaves the list empty.
+struct fx_staged_list {
+    void*  pinned = nullptr;
+    void*  device = nullptr;
+    size_t cap = 0;
+};
+fx_status fx_reserve_list(fx_context* ctx, fx_staged_list* list, size_t entries, size_t entry_bytes);
+void fx_release_list(fx_staged_list* list);
 
 struct fx_comm;     // fx_comm.cpp
 void fx_comm_release(fx_context* ctx);   // called by fx_destroy

@@ -376,8 +376,7 @@ void display_release(fx_context* c)
 {
     fx_display* d = c->display;
     if (!d) return;
-    void* bufs[] = {d->d_state[0], d->d_state[1], d->d_levels, d->d_list, d->d_out};
-    for (void* b : bufs) if (b) (void) hipFree(b);
+    fx_free_device({d->d_state[0], d->d_state[1], d->d_levels, d->d_list, d->d_out});
     delete d;
     c->display = nullptr;
 }
@@ -449,18 +448,12 @@ fx_status display_launch(fx_context* c, const fx_tap_source& src, int T)
     return FX_OK;
 }
 
+// the list contract of fx_context.h, with this unit's own rule: a null list of C entries means every track
 fx_status check_list(const fx_context* c, const int* channels, int n, bool null_is_all)
 {
-    if (n < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative channel count %d", n);
-    if (!channels) {
-        if (null_is_all && n == c->C) return FX_OK;
-        if (n > 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null channel list with %d entries", n);
-        return FX_OK;
-    }
-    for (int i = 0; i < n; i++)
-        if (channels[i] < 0 || channels[i] >= c->C)
-            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: channel %d out of range [0,%d)", i, channels[i], c->C);
-    return FX_OK;
+    if (null_is_all && !channels && n >= 0 && n == c->C) return FX_OK;
+    const fx_status st = fx_check_channel_list(c, channels, n);
+    return st != FX_OK ? st : fx_check_channel_entries(c, channels, n);
 }
 
 } // namespace
@@ -475,7 +468,7 @@ fx_status fx_enable_display(fx_context* c, int samples_per_block, int buffer_siz
     if (buffer_size > 0 && (samples_per_block < 1 || samples_per_block > fxk::MAX_SAMPLES_PER_BLOCK))
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "samples_per_block %d: 1 .. %d", samples_per_block, fxk::MAX_SAMPLES_PER_BLOCK);
     if (buffer_size == 0 && !c->display) return FX_OK;
-    { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess || n < 1) { (void) hipGetLastError(); return fx_fail(FX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)"); } }
+    { const fx_status st = fx_require_device(); if (st != FX_OK) return st; }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));        // launches in flight write the display that is about to go
     if (buffer_size == 0) {
@@ -505,8 +498,7 @@ fx_status fx_enable_display(fx_context* c, int samples_per_block, int buffer_siz
     };
     const fx_status st = build();
     if (st != FX_OK) {
-        void* bufs[] = {d->d_state[0], d->d_state[1], d->d_levels};
-        for (void* b : bufs) if (b) (void) hipFree(b);
+        fx_free_device({d->d_state[0], d->d_state[1], d->d_levels});
         delete d;
         return st;
     }
@@ -544,8 +536,7 @@ fx_status fx_clear_display_channels(fx_context* c, const int* channels, int num_
 fx_status fx_get_display(fx_context* c, const int* channels, int num_channels, float* levels, int mem_kind)
 {
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
-    if (mem_kind != FX_MEM_HOST && mem_kind != FX_MEM_DEVICE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", mem_kind);
-    { const fx_status st = check_list(c, channels, num_channels, true); if (st != FX_OK) return st; }
+    { fx_status st = fx_check_memory_kind(mem_kind); if (st == FX_OK) st = check_list(c, channels, num_channels, true); if (st != FX_OK) return st; }
     fx_display* d = c->display;
     if (!d) return fx_fail(FX_ERR_INVALID_ARGUMENT, "the audio display is not enabled on this context (fx_enable_display)");
     if (num_channels == 0) return FX_OK;

@@ -185,8 +185,7 @@ void events_release(fx_context* c)
 {
     fx_events* e = c->events;
     if (!e) return;
-    void* bufs[] = {e->d_ring, e->d_state, e->d_masks};
-    for (void* b : bufs) if (b) (void) hipFree(b);
+    fx_free_device({e->d_ring, e->d_state, e->d_masks});
     delete e;
     c->events = nullptr;
 }

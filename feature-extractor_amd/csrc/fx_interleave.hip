@@ -155,8 +155,7 @@ void interleave_release(fx_context* c)
 {
     fx_interleave* s = c->interleave;
     if (!s) return;
-    void* bufs[] = {s->d_map, s->d_src, s->d_planar};
-    for (void* b : bufs) if (b) (void) hipFree(b);
+    fx_free_device({s->d_map, s->d_src, s->d_planar});
     delete s;
     c->interleave = nullptr;
 }

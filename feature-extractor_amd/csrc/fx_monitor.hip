@@ -316,8 +316,7 @@ void monitor_release(fx_context* c)
 {
     fx_monitor* m = c->monitor;
     if (!m) return;
-    void* bufs[] = {m->d_sends, m->d_part, m->d_out, m->d_listen};
-    for (void* b : bufs) if (b) (void) hipFree(b);
+    fx_free_device({m->d_sends, m->d_part, m->d_out, m->d_listen});
     delete m;
     c->monitor = nullptr;
 }
@@ -380,7 +379,7 @@ fx_status fx_enable_monitor(fx_context* c, int enable)
     // (fx_destroy_clips' rule for loaded clips: what a track still uses is not freed under it)
     if (!enable && !c->monitor->listeners.empty())
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "track %d listens to the monitor's output (fx_set_channel_listen)", c->monitor->listeners[0].track);
-    { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess || n < 1) { (void) hipGetLastError(); return fx_fail(FX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)"); } }
+    { const fx_status st = fx_require_device(); if (st != FX_OK) return st; }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));        // ticks in flight write the monitor that is about to go; copies in flight read it
     if (!enable) {
@@ -408,7 +407,7 @@ fx_status fx_enable_monitor(fx_context* c, int enable)
         if (q) (void) hipFree(q);
         if (ql) (void) hipFree(ql);
         delete m;
-        return fx_fail(e == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "allocating the send table failed: %s", hipGetErrorString(e));
+        return fx_fail(fx_hip_status(e), "allocating the send table failed: %s", hipGetErrorString(e));
     }
     m->d_sends = static_cast<fxk::MonitorSend*>(q);
     m->d_listen = static_cast<fxk::ListenEntry*>(ql);
@@ -421,17 +420,14 @@ fx_status fx_enable_monitor(fx_context* c, int enable)
 
 fx_status fx_set_channel_monitor(fx_context* c, const int* channels, int num_channels, const int* on, const float* left, const float* right)
 {
-    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
-    if (num_channels < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative channel count %d", num_channels);
-    if (num_channels > 0 && !channels) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null channel list with %d entries", num_channels);
+    fx_status st = fx_check_channel_list(c, channels, num_channels);
+    if (st != FX_OK) return st;
     // the call's own values, then the range of its entries (fx_set_channel_clips' order)
     for (int i = 0; i < num_channels; i++) {
         if (left && !std::isfinite(left[i])) return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: the left gain %g is not a finite number", i, left[i]);
         if (right && !std::isfinite(right[i])) return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: the right gain %g is not a finite number", i, right[i]);
     }
-    for (int i = 0; i < num_channels; i++)
-        if (channels[i] < 0 || channels[i] >= c->C)
-            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: channel %d out of range [0,%d)", i, channels[i], c->C);
+    if ((st = fx_check_channel_entries(c, channels, num_channels)) != FX_OK) return st;
     fx_monitor* m = c->monitor;
     if (!m) return fx_fail(FX_ERR_INVALID_ARGUMENT, "the monitor is not enabled on this context (fx_enable_monitor)");
     if (num_channels == 0) return FX_OK;
@@ -476,17 +472,14 @@ fx_status fx_get_channel_monitor(fx_context* c, int* on, float* left, float* rig
 
 fx_status fx_set_channel_listen(fx_context* c, const int* channels, int num_channels, const int* listen)
 {
-    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
-    if (num_channels < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative channel count %d", num_channels);
-    if (num_channels > 0 && !channels) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null channel list with %d entries", num_channels);
+    fx_status st = fx_check_channel_list(c, channels, num_channels);
+    if (st != FX_OK) return st;
     if (num_channels > 0 && !listen) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null listen list with %d entries", num_channels);
     // the call's own values, then the range of its entries (fx_set_channel_monitor's order)
     for (int i = 0; i < num_channels; i++)
         if (listen[i] != FX_LISTEN_SELF && listen[i] != FX_LISTEN_LEFT && listen[i] != FX_LISTEN_RIGHT)
             return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: unknown listen %d", i, listen[i]);
-    for (int i = 0; i < num_channels; i++)
-        if (channels[i] < 0 || channels[i] >= c->C)
-            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: channel %d out of range [0,%d)", i, channels[i], c->C);
+    if ((st = fx_check_channel_entries(c, channels, num_channels)) != FX_OK) return st;
     fx_monitor* m = c->monitor;
     if (!m) return fx_fail(FX_ERR_INVALID_ARGUMENT, "the monitor is not enabled on this context (fx_enable_monitor)");
     if (num_channels == 0) return FX_OK;
@@ -532,7 +525,7 @@ fx_status fx_get_monitor(fx_context* c, float* out, int capacity, int* num_sampl
     if (num_samples) *num_samples = 0;
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
     if (!out) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null output pointer");
-    if (mem_kind != FX_MEM_HOST && mem_kind != FX_MEM_DEVICE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", mem_kind);
+    { const fx_status st = fx_check_memory_kind(mem_kind); if (st != FX_OK) return st; }
     const fx_monitor* m = c->monitor;
     if (!m) return fx_fail(FX_ERR_INVALID_ARGUMENT, "the monitor is not enabled on this context (fx_enable_monitor)");
     if (num_samples) *num_samples = m->n;            // (also where the room is refused: a host learns what to bring)

@@ -6,9 +6,9 @@
 //
 // The frame kernel is the hot path of an offline analysis -- N log N a frame against the O(N) of every per-frame kernel: one workgroup per
 // (frame, channel); the window is read in sample order (coalesced; the padding rule decides per sample), multiplied by the Bartlett gain and
-// written to LDS at its leaf position of the reference FFT's recursion; the transform is the plain per-level form of fx_taps.hip (one
-// butterfly per thread and level, table twiddles, no fused multiply-add: the DAG of every transform in this library, so the same bits); the
-// magnitudes leave in bin order (coalesced) and one lane adds them up in bin order for the energy envelope.
+// written to LDS at its leaf position of the reference FFT's recursion; the transform is the plain per-level form of fx_plain_fft.hip.h, which
+// fx_taps.hip runs too (one butterfly per thread and level, table twiddles, no fused multiply-add: the DAG of every transform in this
+// library, so the same bits); the magnitudes leave in bin order (coalesced) and one lane adds them up in bin order for the energy envelope.
 // LDS: N complex + N / 2 + 1 floats = 48 KB at 4096 points.
 #include <hip/hip_runtime.h>
 
@@ -24,64 +24,8 @@ namespace {
 
 constexpr int NT = 256;
 
-// The reference FFT's factorisation of N (oracle/fx_oracle.c fft_cfg_init): radix 4 while it divides, then one radix 2.  Level k (0 = the
-// outermost call of the recursion) has twiddle stride 4^k, and each of its butterflies spans length(k) points.
-template <int N> struct Plan {
-    static constexpr int LOG = N == 256 ? 8 : N == 512 ? 9 : N == 1024 ? 10 : N == 2048 ? 11 : 12;
-    static constexpr int R4 = LOG / 2;
-    static constexpr int LEVELS = R4 + (LOG & 1);
-    static __device__ __forceinline__ int radix(int k) { return k < R4 ? 4 : 2; }
-    static __device__ __forceinline__ int stride(int k) { return 1 << (2 * k); }
-    static __device__ __forceinline__ int length(int k) { return N / (stride(k) * radix(k)); }
-    // where input sample j stands before the butterflies (the leaves of the recursion): its digits, level by level, most significant first
-    static __device__ __forceinline__ int position(int j)
-    {
-        int p = 0;
-#pragma unroll
-        for (int k = 0; k < LEVELS; k++) p += ((j >> (2 * k)) & (radix(k) - 1)) * length(k);
-        return p;
-    }
-};
-
-struct cpx { float r, i; };
-__device__ __forceinline__ cpx c_mul(cpx a, cpx b) { return cpx{a.r * b.r - a.i * b.i, a.r * b.i + a.i * b.r}; }
-__device__ __forceinline__ cpx c_add(cpx a, cpx b) { return cpx{a.r + b.r, a.i + b.i}; }
-__device__ __forceinline__ cpx c_sub(cpx a, cpx b) { return cpx{a.r - b.r, a.i - b.i}; }
-__device__ __forceinline__ cpx tw_at(const float* tw, int j)
-{
-    const float2 t = reinterpret_cast<const float2*>(tw)[j];
-    return cpx{t.x, t.y};
-}
-
-// The forward butterflies of every level, innermost first, over buf (in leaf order): fft_butterfly4 / fft_butterfly2 of the oracle,
-// operation for operation.  Ends behind a barrier.
-template <int N> __device__ void forward_transform(cpx* buf, const float* tw)
-{
-    using P = Plan<N>;
-    for (int k = P::LEVELS - 1; k >= 0; k--) {
-        const int r = P::radix(k), s = P::stride(k), L = P::length(k);
-        for (int q = threadIdx.x; q < N / r; q += NT) {
-            const int b = q / L, i = q - b * L;
-            cpx* d = buf + b * r * L + i;
-            if (r == 4) {
-                const cpx s0 = c_mul(d[L], tw_at(tw, i * s));
-                const cpx s1 = c_mul(d[2 * L], tw_at(tw, 2 * i * s));
-                const cpx s2 = c_mul(d[3 * L], tw_at(tw, 3 * i * s));
-                const cpx s3 = c_add(s0, s2), s4 = c_sub(s0, s2), s5 = c_sub(d[0], s1);
-                const cpx d0 = c_add(d[0], s1);
-                d[2 * L] = c_sub(d0, s3);
-                d[0] = c_add(d0, s3);
-                d[L] = cpx{s5.r + s4.i, s5.i - s4.r};
-                d[3 * L] = cpx{s5.r - s4.i, s5.i + s4.r};
-            } else {
-                const cpx t = c_mul(d[L], tw_at(tw, i * s));
-                d[L] = c_sub(d[0], t);
-                d[0] = c_add(d[0], t);
-            }
-        }
-        __syncthreads();
-    }
-}
+// the plan, the complex helpers and plain_transform: the one statement of the reference FFT's DAG
+#include "fx_plain_fft.hip.h"
 
 // block = (frame, channel): blockIdx.x = (f - first_frame) * C + c
 template <int N>
@@ -91,7 +35,7 @@ __global__ void __launch_bounds__(NT) offline_frames_kernel(const float* __restr
     constexpr int H = N / 2, B = N / 2 + 1;
     __shared__ cpx buf[N];
     __shared__ float mag[B];
-    using P = Plan<N>;
+    using P = PlainPlan<N>;
     const int tid = threadIdx.x;
     const int fl = blockIdx.x / C, c = blockIdx.x - fl * C, f = first_frame + fl;
     const int step = S / D;                                                 // :135 (int division)
@@ -106,7 +50,7 @@ __global__ void __launch_bounds__(NT) offline_frames_kernel(const float* __restr
         buf[P::position(j)] = cpx{v * w, 0.0f};                             // (always multiplied: inf * 0 = NaN, as applyGainRamp makes it)
     }
     __syncthreads();
-    forward_transform<N>(buf, tw);
+    plain_transform<N, false, NT>(buf, tw);
     // performFrequencyOnlyForwardTransform, as tools/refdiff/juce_standin.h states it: sqrt (re * re + im * im) in float, bins 0 .. N / 2
     float* out = mags + ((size_t) fl * C + c) * B;
     for (int b = tid; b < B; b += NT) {

@@ -373,7 +373,7 @@ fx_status fx_offline_smoothing(fx_offline* o, int depth)
         if (e != hipSuccess) {
             (void) hipFree(current);
             if (history) (void) hipFree(history);
-            return fx_fail(e == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "constructing the smoothers failed: %s", hipGetErrorString(e));
+            return fx_fail(fx_hip_status(e), "constructing the smoothers failed: %s", hipGetErrorString(e));
         }
     }
     if (o->d_smooth_current) (void) hipFree(o->d_smooth_current);

@@ -6,9 +6,8 @@
 // first frame analyses, by ONE launch of fx_taps_kernel (one workgroup per armed channel) on the context's stream, ahead of every launch
 // of the call that changes the context's state.  The kernel reads the window where the analysis kernels read it -- the carried tail, the
 // caller's hops / frame / [pending | block] stream, widened by the same widen_one -- and restates the reference's arithmetic plainly:
-// the transforms run the reference FFT's butterfly DAG (JUCE 4.2 kiss-style radix-4/2 decimation in time, table twiddles, no fused
-// multiply-add) one butterfly per thread and level through LDS, and the serial parts (the low-pass, the fp32 running sum, the lag walk)
-// on one lane.  Off the hot path: clarity before speed.
+// the transforms run the reference FFT's butterfly DAG as fx_plain_fft.hip.h states it (one butterfly per thread and level through
+// LDS), and the serial parts (the low-pass, the fp32 running sum, the lag walk) on one lane.  Off the hot path: clarity before speed.
 //
 // Nothing in the shim's host units (build.py, HOST_SOURCES) refers to this unit: fx_request_taps installs the context's two hooks (fx_context.h), and the analysis entry
 // points call them only when channels are armed.
@@ -54,72 +53,8 @@ struct TapsParams {
     int           channels[FX_MAX_TAP_CHANNELS];
 };
 
-// The reference FFT's factorisation of N (fx_oracle.c fft_cfg_init): radix 4 while it divides, then one radix 2.  Level k (0 = the
-// outermost call of fft_perform) has twiddle stride 4^k, and each of its butterflies spans length(k) points.
-template <int N> struct TapPlan {
-    static constexpr int LOG = N == 256 ? 8 : N == 512 ? 9 : N == 1024 ? 10 : N == 2048 ? 11 : 12;
-    static constexpr int R4 = LOG / 2;
-    static constexpr int LEVELS = R4 + (LOG & 1);
-    static __device__ __forceinline__ int radix(int k) { return k < R4 ? 4 : 2; }
-    static __device__ __forceinline__ int stride(int k) { return 1 << (2 * k); }
-    static __device__ __forceinline__ int length(int k) { return N / (stride(k) * radix(k)); }
-    // the input element that lands at position p of the output before the butterflies (the leaves of the recursion)
-    static __device__ __forceinline__ int source(int p)
-    {
-        int idx = 0;
-        for (int k = 0; k < LEVELS; k++) {
-            const int L = length(k), j = p / L;
-            p -= j * L;
-            idx += j * stride(k);
-        }
-        return idx;
-    }
-};
-
-struct cpx { float r, i; };
-__device__ __forceinline__ cpx c_mul(cpx a, cpx b) { return cpx{a.r * b.r - a.i * b.i, a.r * b.i + a.i * b.r}; }
-__device__ __forceinline__ cpx c_add(cpx a, cpx b) { return cpx{a.r + b.r, a.i + b.i}; }
-__device__ __forceinline__ cpx c_sub(cpx a, cpx b) { return cpx{a.r - b.r, a.i - b.i}; }
-template <bool INV> __device__ __forceinline__ cpx tw_at(const float* tw, int j)
-{
-    const float2 t = reinterpret_cast<const float2*>(tw)[j];
-    return cpx{t.x, INV ? -t.y : t.y};
-}
-
-// The butterflies of every level, innermost first, over buf (already in leaf order).  fft_butterfly4 / fft_butterfly2 of the oracle,
-// operation for operation.
-template <int N, bool INV> __device__ void transform(cpx* buf, const float* tw)
-{
-    using P = TapPlan<N>;
-    for (int k = P::LEVELS - 1; k >= 0; k--) {
-        const int r = P::radix(k), s = P::stride(k), L = P::length(k);
-        for (int q = threadIdx.x; q < N / r; q += TAP_THREADS) {
-            const int b = q / L, i = q - b * L;
-            cpx* d = buf + b * r * L + i;
-            if (r == 4) {
-                const cpx s0 = c_mul(d[L], tw_at<INV>(tw, i * s));
-                const cpx s1 = c_mul(d[2 * L], tw_at<INV>(tw, 2 * i * s));
-                const cpx s2 = c_mul(d[3 * L], tw_at<INV>(tw, 3 * i * s));
-                const cpx s3 = c_add(s0, s2), s4 = c_sub(s0, s2), s5 = c_sub(d[0], s1);
-                const cpx d0 = c_add(d[0], s1);
-                d[2 * L] = c_sub(d0, s3);
-                d[0] = c_add(d0, s3);
-                if (INV) {
-                    d[L] = cpx{s5.r - s4.i, s5.i + s4.r};
-                    d[3 * L] = cpx{s5.r + s4.i, s5.i - s4.r};
-                } else {
-                    d[L] = cpx{s5.r + s4.i, s5.i - s4.r};
-                    d[3 * L] = cpx{s5.r - s4.i, s5.i + s4.r};
-                }
-            } else {
-                const cpx t = c_mul(d[L], tw_at<INV>(tw, i * s));
-                d[L] = c_sub(d[0], t);
-                d[0] = c_add(d[0], t);
-            }
-        }
-        __syncthreads();
-    }
-}
+// the plan, the complex helpers and plain_transform: the one statement of the reference FFT's DAG
+#include "fx_plain_fft.hip.h"
 
 // sample j of the channel's first new hop (hop_mode 1) or of its first frame (hop_mode 0), widened as the analysis kernels widen it
 template <int FMT> __device__ __forceinline__ float first_sample(const fx_tap_source& src, int c, int j)
@@ -164,7 +99,7 @@ __global__ void __launch_bounds__(TAP_THREADS) fx_taps_kernel(const TapsParams p
     float* o_ac = out + 5 * N;
     float* o_cnd = out + 6 * N;
     float* o_lag = out + 7 * N;
-    using P = TapPlan<N>;
+    using P = PlainPlan<N>;
 
     // the overlapped window (RealTimeAudioDataOverlapper::getNextBuffer, RealTimeAudioAnalysis.h:205-228)
     switch (p.src.sample_format) {
@@ -182,7 +117,7 @@ __global__ void __launch_bounds__(TAP_THREADS) fx_taps_kernel(const TapsParams p
         buf[q] = cpx{aux[k] * p.ramp[k], 0.0f};
     }
     __syncthreads();
-    transform<N, false>(buf, p.tw);
+    plain_transform<N, false, TAP_THREADS>(buf, p.tw);
     for (int q = tid; q < N; q += TAP_THREADS) reinterpret_cast<float2*>(o_spec)[q] = float2{buf[q].r, buf[q].i};
 
     // harmonic analyser: one-pole low-pass (RealTimeAudioAnalysis.h:106-125; serial), Bartlett window, forward transform (RealTimeAnalyser.h:152-160)
@@ -199,7 +134,7 @@ __global__ void __launch_bounds__(TAP_THREADS) fx_taps_kernel(const TapsParams p
         buf[q] = cpx{aux[k] * p.ramp[k], 0.0f};
     }
     __syncthreads();
-    transform<N, false>(buf, p.tw);
+    plain_transform<N, false, TAP_THREADS>(buf, p.tw);
     for (int q = tid; q < N; q += TAP_THREADS) {
         reinterpret_cast<float2*>(o_pitch)[q] = float2{buf[q].r, buf[q].i};
         aux[q] = buf[q].r * buf[q].r;        // getComplexConjugateMultiplication (PitchAnalyser.h:83-108): re * re, imag 0
@@ -209,7 +144,7 @@ __global__ void __launch_bounds__(TAP_THREADS) fx_taps_kernel(const TapsParams p
     // getAutoCorrelationFromConjugateMultiplication (:110-127): inverse transform, 1/N, v[s] = d[s] * d[s] * s
     for (int q = tid; q < N; q += TAP_THREADS) buf[q] = cpx{aux[P::source(q)], 0.0f};
     __syncthreads();
-    transform<N, true>(buf, p.tw);
+    plain_transform<N, true, TAP_THREADS>(buf, p.tw);
     const float scale = 1.0f / N;
     for (int s = tid; s < N; s += TAP_THREADS) {
         const float d = buf[s].r * scale;

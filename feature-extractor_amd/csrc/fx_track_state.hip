@@ -126,9 +126,9 @@ hipError_t launch_unpack_tracks_kernel(const TrackStateParams& p, hipStream_t st
 #endif
 
 struct fx_track_state {
-    fxk::TrackEntry* h_entries = nullptr;   // pinned: the list an upload in flight reads
-    fxk::TrackEntry* d_entries = nullptr;
-    size_t cap = 0;                         // entries both hold
+    fx_staged_list entries;                 // of fxk::TrackEntry
+    fxk::TrackEntry* h_entries() const { return static_cast<fxk::TrackEntry*>(entries.pinned); }
+    fxk::TrackEntry* d_entries() const { return static_cast<fxk::TrackEntry*>(entries.device); }
     unsigned char* d_records = nullptr;     // a call whose buffer is host memory: the records of one chunk (at most SCRATCH_BYTES)
     size_t records_cap = 0;
 };
@@ -142,8 +142,7 @@ void track_state_release(fx_context* c)
     fx_track_state* t = c->track_state;
     if (!t) return;
     if (t->d_records) (void) hipFree(t->d_records);
-    if (t->d_entries) (void) hipFree(t->d_entries);
-    if (t->h_entries) (void) hipHostFree(t->h_entries);
+    fx_release_list(&t->entries);
     delete t;
     c->track_state = nullptr;
 }
@@ -153,13 +152,10 @@ size_t record_bytes(const fx_context* c) { return fxk::track_record_pieces(c->N)
 // the list and the buffer, fx_reset_channels' rules for the first: every entry is checked before anything is touched, no device use
 fx_status check_call(const fx_context* c, const int* channels, int num_channels, const void* buffer, size_t bytes, int mem_kind, bool import)
 {
-    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
-    if (num_channels < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative channel count %d", num_channels);
-    if (num_channels > 0 && !channels) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null channel list with %d entries", num_channels);
-    for (int i = 0; i < num_channels; i++)
-        if (channels[i] < 0 || channels[i] >= c->C)
-            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: channel %d out of range [0,%d)", i, channels[i], c->C);
-    if (mem_kind != FX_MEM_HOST && mem_kind != FX_MEM_DEVICE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", mem_kind);
+    fx_status st = fx_check_channel_list(c, channels, num_channels);
+    if (st == FX_OK) st = fx_check_channel_entries(c, channels, num_channels);
+    if (st == FX_OK) st = fx_check_memory_kind(mem_kind);
+    if (st != FX_OK) return st;
     if (num_channels == 0) return FX_OK;
     if (import) {
         // (the order of two writes to one slot would decide the result)
@@ -189,8 +185,7 @@ size_t chunk_records(const fx_context* c)
     return n ? n : 1;
 }
 
-// room for n entries in the pinned and the device list and for `records` records in the device scratch; growing waits for the
-// stream first (a copy in flight may read the old ones)
+// room for n entries in the pinned and the device list (fx_reserve_list, fx_context.h) and for `records` records in the device scratch
 fx_status reserve(fx_context* c, size_t n, size_t records)
 {
     if (!c->track_state) {
@@ -199,28 +194,7 @@ fx_status reserve(fx_context* c, size_t n, size_t records)
         c->track_state_release = track_state_release;
     }
     fx_track_state* t = c->track_state;
-    if (n > t->cap) {
-        size_t want = n;
-        if (want < t->cap + t->cap / 2) want = t->cap + t->cap / 2;
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        // the new pair is allocated first, so a failed allocation leaves the old lists in place
-        void* h = nullptr;
-        HIP_TRY(hipHostMalloc(&h, want * sizeof(fxk::TrackEntry), hipHostMallocDefault));
-        void* d = nullptr;
-        {
-            const hipError_t e = hipMalloc(&d, want * sizeof(fxk::TrackEntry));
-            if (e != hipSuccess) {
-                (void) hipHostFree(h);
-                return fx_fail(e == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "allocating the track list failed: %s", hipGetErrorString(e));
-            }
-        }
-        fxk::TrackEntry* old_d = t->d_entries; fxk::TrackEntry* old_h = t->h_entries;
-        t->d_entries = static_cast<fxk::TrackEntry*>(d); t->h_entries = static_cast<fxk::TrackEntry*>(h); t->cap = want;
-        const hipError_t freed_d = old_d ? hipFree(old_d) : hipSuccess;
-        const hipError_t freed_h = old_h ? hipHostFree(old_h) : hipSuccess;
-        HIP_TRY(freed_d);
-        HIP_TRY(freed_h);
-    }
+    { const fx_status st = fx_reserve_list(c, &t->entries, n, sizeof(fxk::TrackEntry)); if (st != FX_OK) return st; }
     if (records) return fx_grow(&t->d_records, &t->records_cap, records * record_bytes(c));
     return FX_OK;
 }
@@ -254,7 +228,7 @@ fxk::TrackHeader header_of(const fx_context* c, const fxk::ChannelSettings& r, f
 fxk::TrackStateParams params_of(fx_context* c, size_t first, size_t n, unsigned char* records)
 {
     fxk::TrackStateParams p;
-    p.entries = c->track_state->d_entries + first;
+    p.entries = c->track_state->d_entries() + first;
     p.n = (int) n;
     p.C = c->C;
     p.row_pieces = c->N / 8;                    // N/2 * 4 bytes in 16-byte pieces
@@ -313,12 +287,12 @@ fx_status fx_export_channels(fx_context* c, const int* channels, int num_channel
     const fxk::ChannelSettings wide = {c->gain, c->onset_multiplier, c->onset_window, c->onset_type, c->onset_reset_frame, 0};
     for (int i = 0; i < num_channels; i++) {
         const size_t ch = (size_t) channels[i];
-        fxk::TrackEntry& e = t->h_entries[i];
+        fxk::TrackEntry& e = t->h_entries()[i];
         memset(&e, 0, sizeof e);
         e.header = c->chan.empty() ? header_of(c, wide, c->onset_sensitivity) : header_of(c, c->chan[ch], c->chan_sensitivity[ch]);
         e.channel = channels[i];
     }
-    HIP_TRY(hipMemcpyAsync(t->d_entries, t->h_entries, (size_t) num_channels * sizeof(fxk::TrackEntry), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(t->d_entries(), t->h_entries(), (size_t) num_channels * sizeof(fxk::TrackEntry), hipMemcpyHostToDevice, c->stream));
     // (the stream orders a chunk's copy out of the scratch before the next chunk's launch into it)
     for (size_t first = 0; first < total; first += chunk) {
         const size_t n = total - first < chunk ? total - first : chunk;
@@ -372,12 +346,12 @@ fx_status fx_import_channels(fx_context* c, const int* channels, int num_channel
     }
     if ((st = fx_upload_channel_rows(c, rows, sensitivity)) != FX_OK) return st;
     for (int i = 0; i < num_channels; i++) {
-        fxk::TrackEntry& e = t->h_entries[i];
+        fxk::TrackEntry& e = t->h_entries()[i];
         memset(&e, 0, sizeof e);
         e.header = headers[(size_t) i];
         e.channel = channels[i];
     }
-    HIP_TRY(hipMemcpyAsync(t->d_entries, t->h_entries, (size_t) num_channels * sizeof(fxk::TrackEntry), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(t->d_entries(), t->h_entries(), (size_t) num_channels * sizeof(fxk::TrackEntry), hipMemcpyHostToDevice, c->stream));
     for (size_t first = 0; first < total; first += chunk) {
         const size_t n = total - first < chunk ? total - first : chunk;
         if (host) HIP_TRY(hipMemcpyAsync(t->d_records, static_cast<const unsigned char*>(in) + first * rec, n * rec, hipMemcpyHostToDevice, c->stream));

@@ -71,9 +71,7 @@ hipError_t launch_reset_channels_kernel(const ResetParams& p, hipStream_t stream
 #endif
 
 struct fx_tracks {
-    int*   h_list = nullptr;        // pinned: the list an upload in flight reads
-    int*   d_list = nullptr;
-    size_t cap = 0;                 // entries both hold
+    fx_staged_list list;            // of int
 };
 
 namespace {
@@ -82,8 +80,7 @@ void tracks_release(fx_context* c)
 {
     fx_tracks* t = c->tracks;
     if (!t) return;
-    if (t->d_list) (void) hipFree(t->d_list);
-    if (t->h_list) (void) hipHostFree(t->h_list);
+    fx_release_list(&t->list);
     delete t;
     c->tracks = nullptr;
 }
@@ -91,16 +88,11 @@ void tracks_release(fx_context* c)
 // every entry is checked before anything is touched: no device use
 fx_status check_list(const fx_context* c, const int* channels, int num_channels)
 {
-    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
-    if (num_channels < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative channel count %d", num_channels);
-    if (num_channels > 0 && !channels) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null channel list with %d entries", num_channels);
-    for (int i = 0; i < num_channels; i++)
-        if (channels[i] < 0 || channels[i] >= c->C)
-            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: channel %d out of range [0,%d)", i, channels[i], c->C);
-    return FX_OK;
+    const fx_status st = fx_check_channel_list(c, channels, num_channels);
+    return st != FX_OK ? st : fx_check_channel_entries(c, channels, num_channels);
 }
 
-// room for n entries in the pinned and the device list; growing waits for the stream first (a copy in flight may read the old ones)
+// room for n entries in the pinned and the device list (fx_reserve_list, fx_context.h)
 fx_status reserve_list(fx_context* c, size_t n)
 {
     if (!c->tracks) {
@@ -108,41 +100,18 @@ fx_status reserve_list(fx_context* c, size_t n)
         if (!c->tracks) return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
         c->tracks_release = tracks_release;
     }
-    fx_tracks* t = c->tracks;
-    if (n <= t->cap) return FX_OK;
-    // grows by at least half again, as fx_grow() (fx_context.h): a host whose lists get longer does not pay a free (it waits for the device)
-    // and a pinned allocation per call.  The new pair is allocated first, so a failed allocation leaves the old lists in place.
-    size_t want = n;
-    if (want < t->cap + t->cap / 2) want = t->cap + t->cap / 2;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    void* h = nullptr;
-    HIP_TRY(hipHostMalloc(&h, want * sizeof(int), hipHostMallocDefault));
-    void* d = nullptr;
-    {
-        const hipError_t e = hipMalloc(&d, want * sizeof(int));
-        if (e != hipSuccess) {
-            (void) hipHostFree(h);
-            return fx_fail(e == hipErrorOutOfMemory ? FX_ERR_OUT_OF_MEMORY : FX_ERR_HIP, "allocating the track list failed: %s", hipGetErrorString(e));
-        }
-    }
-    int* old_d = t->d_list; int* old_h = t->h_list;
-    t->d_list = static_cast<int*>(d); t->h_list = static_cast<int*>(h); t->cap = want;
-    // (both frees are attempted before either failure is reported; the new lists are in place either way)
-    const hipError_t freed_d = old_d ? hipFree(old_d) : hipSuccess;
-    const hipError_t freed_h = old_h ? hipHostFree(old_h) : hipSuccess;
-    HIP_TRY(freed_d);
-    HIP_TRY(freed_h);
-    return FX_OK;
+    return fx_reserve_list(c, &c->tracks->list, n, sizeof(int));
 }
 
 // the list to the device and the one launch, on the context's stream (idle when this is called: the pinned list is free)
 fx_status clear_rows(fx_context* c, const int* channels, int num_channels, unsigned clear)
 {
     fx_tracks* t = c->tracks;
-    memcpy(t->h_list, channels, (size_t) num_channels * sizeof(int));
-    HIP_TRY(hipMemcpyAsync(t->d_list, t->h_list, (size_t) num_channels * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    int* d_list = static_cast<int*>(t->list.device);
+    memcpy(t->list.pinned, channels, (size_t) num_channels * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(d_list, t->list.pinned, (size_t) num_channels * sizeof(int), hipMemcpyHostToDevice, c->stream));
     fxk::ResetParams p;
-    p.list = t->d_list;
+    p.list = d_list;
     p.n = num_channels;
     p.C = c->C;
     p.row_pieces = c->N / 8;                    // N/2 * 4 bytes in 16-byte pieces
