@@ -18,10 +18,36 @@ struct BlockStream {
     long long            in_row_bytes;
 };
 
-// dwords that need only dword alignment (the hardware's requirement for a multi-dword global access)
-struct __attribute__((packed, aligned(4))) dwords4 { unsigned x, y, z, w; };
+// N dwords that need only dword alignment (the hardware's requirement for a multi-dword global access).  Four and two are vectors, so
+// that they can also be read and written through a pointer that says "global memory" (the Global* forms: where the compiler sees only a
+// pointer read from a table it would emit a flat access); there is no vector of three.
+typedef unsigned __attribute__((vector_size(16), aligned(4))) dwords4;
+typedef unsigned __attribute__((vector_size(8), aligned(4))) dwords2;
 struct __attribute__((packed, aligned(4))) dwords3 { unsigned x, y, z; };
-struct __attribute__((packed, aligned(4))) dwords2 { unsigned x, y; };
+typedef const dwords4 __attribute__((address_space(1)))* GlobalDwords4;
+typedef dwords4 __attribute__((address_space(1)))* GlobalDwords4Out;
+typedef const unsigned __attribute__((address_space(1)))* GlobalDword;
+
+// The 16 bytes at ANY byte address of global memory, in two halves.  The load: the four aligned dwords around them from `base` (the
+// address less its low two bits, `sh`), and the fifth dword where `fifth` is not zero -- it holds bytes of the piece only when sh != 0
+// and the piece is a whole 16 bytes, and each caller has its own argument for why it lies inside its memory, so each passes its own
+// condition (as a value, compared behind the four-dword load: a bool formed in front of it schedules fx_monitor_mix_kernel differently).
+// The shift (v_alignbyte_b32) is a step of its own: a caller with many loads in flight shifts each when its turn comes.  (`sh` is
+// formed where the address is: handing the pointer to a helper for its low bits changes fx_reblock.hip's code.)
+struct RawPiece { dwords4 q; unsigned q4; };
+__device__ __forceinline__ RawPiece load_raw_piece(const unsigned char* base, unsigned fifth)
+{
+    RawPiece r;
+    r.q = *(GlobalDwords4) base;
+    r.q4 = 0;
+    if (fifth != 0) r.q4 = *(GlobalDword) (base + 16);
+    return r;
+}
+__device__ __forceinline__ uint4 shifted_piece(const RawPiece& r, unsigned sh)
+{
+    return uint4{__builtin_amdgcn_alignbyte(r.q[1], r.q[0], sh), __builtin_amdgcn_alignbyte(r.q[2], r.q[1], sh),
+                 __builtin_amdgcn_alignbyte(r.q[3], r.q[2], sh), __builtin_amdgcn_alignbyte(r.q4, r.q[3], sh)};
+}
 
 // the same stream from byte `shift` on (a multiple of 16: whole hops): wave-uniform arithmetic, so a launch that analyses hop k of a block
 // pays for it in scalar registers, not in every lane's addresses
@@ -48,13 +74,8 @@ __device__ __forceinline__ void stream_piece16(const BlockStream& s, long long t
         // (pointer arithmetic, not an integer round trip: the compiler keeps the global address space and emits global_load_dwordx4)
         const unsigned char* at = s.block_row + b0;
         const unsigned sh = (unsigned) (reinterpret_cast<uintptr_t>(at) & 3);
-        const unsigned char* base = at - sh;
-        const dwords4 q = *reinterpret_cast<const dwords4*>(base);
-        const unsigned q4 = *reinterpret_cast<const unsigned*>(base + 16);
-        v[0] = __builtin_amdgcn_alignbyte(q.y, q.x, sh);
-        v[1] = __builtin_amdgcn_alignbyte(q.z, q.y, sh);
-        v[2] = __builtin_amdgcn_alignbyte(q.w, q.z, sh);
-        v[3] = __builtin_amdgcn_alignbyte(q4, q.w, sh);
+        const uint4 q = shifted_piece(load_raw_piece(at - sh, 1u), sh);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
     } else if (d0 + 16 <= s.carry_bytes) {
         // wholly inside the pending samples: the carry row starts on a 16-byte boundary and so does this piece
         const uint4 q = *reinterpret_cast<const uint4*>(s.carry_row + d0);
@@ -78,8 +99,8 @@ __device__ __forceinline__ void stream_piece16(const BlockStream& s, long long t
                 for (int k = 0; k < 3; k++) if (w + k < end) q[j] |= (unsigned) w[k] << (8 * k);
             }
         }
-#pragma unroll
-        for (int j = 0; j < 4; j++) v[j] = __builtin_amdgcn_alignbyte(q[j + 1], q[j], sh);
+        const uint4 r = shifted_piece(RawPiece{dwords4{q[0], q[1], q[2], q[3]}, q[4]}, sh);
+        v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
     } else {
         // across the boundary between the pending samples and the block (pending counts that are no multiple of 16 bytes): byte by byte
 #pragma unroll
@@ -95,7 +116,7 @@ __device__ __forceinline__ void stream_piece16(const BlockStream& s, long long t
 }
 
 // The 4 * BYTES bytes of four consecutive samples of BYTES bytes each, starting at sample i (a multiple of 4) of the stream; all of
-// them inside the stream.  Returned as fetch_four returns them (fx_frame_kernel.hip.h): the first 4 * BYTES bytes of the uint4.
+// them inside the stream.  Returned as fetch_four returns them (fx_samples.hip.h): the first 4 * BYTES bytes of the uint4.
 template <int BYTES> __device__ __forceinline__ uint4 stream_four(const BlockStream& s, int i)
 {
     constexpr int W = 4 * BYTES;                       // 16, 12 or 8
@@ -119,13 +140,15 @@ template <int BYTES> __device__ __forceinline__ uint4 stream_four(const BlockStr
         if constexpr (BYTES == 4) {
             // (four-byte samples: the block starts on a dword -- the API asks for that -- and rows and pending counts are whole samples)
             const dwords4 q = *reinterpret_cast<const dwords4*>(at);
-            r.x = q.x; r.y = q.y; r.z = q.z; r.w = q.w;
+            r.x = q[0]; r.y = q[1]; r.z = q[2]; r.w = q[3];
         } else if constexpr (BYTES == 3) {
-            const dwords4 q = *reinterpret_cast<const dwords4*>(base);
-            r.x = __builtin_amdgcn_alignbyte(q.y, q.x, sh); r.y = __builtin_amdgcn_alignbyte(q.z, q.y, sh); r.z = __builtin_amdgcn_alignbyte(q.w, q.z, sh);
+            // (twelve bytes: the four dwords hold them at any shift)
+            const uint4 q = shifted_piece(load_raw_piece(base, 0u), sh);
+            r.x = q.x; r.y = q.y; r.z = q.z;
         } else {
-            const dwords3 q = *reinterpret_cast<const dwords3*>(base);
-            r.x = __builtin_amdgcn_alignbyte(q.y, q.x, sh); r.y = __builtin_amdgcn_alignbyte(q.z, q.y, sh);
+            const dwords3 d = *reinterpret_cast<const dwords3*>(base);
+            const uint4 q = shifted_piece(RawPiece{dwords4{d.x, d.y, d.z, 0u}, 0u}, sh);
+            r.x = q.x; r.y = q.y;
         }
         return r;
     }
@@ -158,7 +181,7 @@ __device__ __forceinline__ void stream_keep_rest(const BlockStream& s, long long
 // What the host must have made sure of before a block-fed launch (FrameParams::block_mode): the kernels index on trust.
 static inline bool block_feed_valid(int n, const FrameParams& p)
 {
-    const long long esz = p.sample_format == FX_SAMPLE_F32 ? 4 : (p.sample_format == FX_SAMPLE_S24 ? 3 : 2);
+    const long long esz = sample_bytes(p.sample_format);
     const long long hop = (long long) (n / 2) * esz, total = (long long) p.blk_carry_bytes + p.blk_in_row_bytes;
     return n >= 1024 && p.T >= 1 && p.T <= 4096 && p.hop_mode == 1 && p.in && p.blk_carry_in && p.blk_carry_out && p.blk_carry_in != p.blk_carry_out &&
            p.blk_carry_bytes >= 0 && p.blk_carry_bytes < hop && p.blk_carry_bytes % esz == 0 && p.blk_in_row_bytes > 0 && p.blk_in_row_bytes % esz == 0 &&

@@ -34,11 +34,10 @@
 
 namespace fxk {
 
-// (the load stage's widen_one, fx_frame_kernel.hip.h: what the resampler makes of a clip's bytes is what the analysis kernels would)
-#include "fx_wave.hip.h"
-#include "fx_fft.hip.h"
-#include "fx_blocks.hip.h"
-#include "fx_frame_kernel.hip.h"
+// (the load stage's widen_one: what the resampler makes of a clip's bytes is what the analysis kernels would)
+#include "fx_wave.hip.h"          // f4
+#include "fx_samples.hip.h"
+#include "fx_blocks.hip.h"        // the shifted 16-byte read
 
 namespace {
 
@@ -84,10 +83,6 @@ template <int B> __device__ __forceinline__ RowStream row_stream(const GatherPar
 }
 
 constexpr int GATHER_THREADS = 256;
-// four dwords that need only dword alignment (dwords4 of fx_blocks.hip.h, as a type that can be read through a global pointer)
-typedef unsigned __attribute__((vector_size(16), aligned(4))) quad;
-typedef const quad __attribute__((address_space(1)))* GlobalQuad;
-typedef const unsigned __attribute__((address_space(1)))* GlobalDword;
 
 // The staging buffer is one run of C * n * B bytes from a 16-byte boundary, and thread g of the launch writes its 16-byte piece g with
 // one global_store_dwordx4 -- whatever n * B makes of the rows' alignment, and with every lane busy when rows are short (441 / 480 /
@@ -144,16 +139,10 @@ template <int B> __device__ __forceinline__ void gather_piece(const GatherParams
             if (x + 16 <= st.lim) {
                 const unsigned char* at = st.base + x;
                 const unsigned sh = (unsigned) (reinterpret_cast<uintptr_t>(at) & 3);
-                const unsigned char* lo = at - sh;
-                // (clips and live blocks are device memory: said to the compiler, which sees only a pointer read from the table, so that
-                // it emits global_load_dwordx4 and not a flat load)
-                const quad q = *(GlobalQuad) lo;
-                unsigned q4 = 0;
-                if (sh) q4 = *(GlobalDword) (lo + 16);                          // (sh == 0: the fifth dword holds no byte of the run)
-                v[0] = __builtin_amdgcn_alignbyte(q[1], q[0], sh);
-                v[1] = __builtin_amdgcn_alignbyte(q[2], q[1], sh);
-                v[2] = __builtin_amdgcn_alignbyte(q[3], q[2], sh);
-                v[3] = __builtin_amdgcn_alignbyte(q4, q[3], sh);
+                // (clips and live blocks are device memory: load_raw_piece says so to the compiler, which sees only a pointer read from
+                // the table, so that it emits global_load_dwordx4 and not a flat load.  sh == 0: the fifth dword holds no byte of the run)
+                const uint4 q = shifted_piece(load_raw_piece(at - sh, sh), sh);
+                v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
             } else if (st.loop || x < st.lim) {
                 bytewise = true;                                                // a seam or an end inside the piece
             }
@@ -291,12 +280,7 @@ fx_clip_resample_kernel(const ResampleParams p)
         const long long want = (long long) ((double) (k + b) * r) + J - lo + 1;
         const int count = want < RS_SPAN ? (int) want : RS_SPAN;
         __syncthreads();                                        // the run before has read its span
-        switch (row.format) {
-            case FX_SAMPLE_F16: fill_span<FX_SAMPLE_F16>(span, row, lo, count, tid); break;
-            case FX_SAMPLE_S16: fill_span<FX_SAMPLE_S16>(span, row, lo, count, tid); break;
-            case FX_SAMPLE_S24: fill_span<FX_SAMPLE_S24>(span, row, lo, count, tid); break;
-            default:            fill_span<FX_SAMPLE_F32>(span, row, lo, count, tid); break;
-        }
+        FX_FORMAT(row.format, fill_span<FMT>(span, row, lo, count, tid));
         __syncthreads();
         const long long i = a + tid;
         if (i <= b) {

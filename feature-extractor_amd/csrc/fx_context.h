@@ -30,7 +30,7 @@ inline fx_status fx_hip_status(hipError_t e) { return e == hipErrorOutOfMemory ?
     } while (0)
 
 inline bool known_format(int f) { return f == FX_SAMPLE_F32 || f == FX_SAMPLE_F16 || f == FX_SAMPLE_S16 || f == FX_SAMPLE_S24; }
-inline size_t sample_size(int f) { return f == FX_SAMPLE_F32 ? 4 : (f == FX_SAMPLE_S24 ? 3 : 2); }
+inline size_t sample_size(int f) { return (size_t) fxk::sample_bytes(f); }
 // A call's sample format and the memory kinds of its input and results (an entry point passes what it has): FX_ERR_INVALID_ARGUMENT
 // for an unknown one, the format's refusal first.  fx_check_memory_kind: one kind alone, "unknown memory kind %d".
 fx_status fx_check_call(int sample_format, int in_kind = FX_MEM_HOST, int out_kind = FX_MEM_HOST);

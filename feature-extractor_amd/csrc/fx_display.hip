@@ -43,10 +43,9 @@
 
 namespace fxk {
 
-#include "fx_wave.hip.h"
-#include "fx_fft.hip.h"
-#include "fx_blocks.hip.h"
-#include "fx_frame_kernel.hip.h"
+#include "fx_wave.hip.h"          // lane_get
+#include "fx_samples.hip.h"
+#include "fx_blocks.hip.h"        // BlockStream
 
 namespace {
 
@@ -113,9 +112,6 @@ __device__ __forceinline__ Seg seg_shfl_up(const Seg& s, int d)
     return Seg{__shfl_up(s.lo, d, 64), __shfl_up(s.hi, d, 64), __shfl_up(s.f, d, 64)};
 }
 
-struct __attribute__((packed, aligned(4))) floats4 { float x, y, z, w; };      // (a multi-dword global access needs dword alignment only)
-struct __attribute__((packed, aligned(4))) floats2 { float x, y; };
-
 // Where fp32 samples i .. i + DISPLAY_PER_LANE - 1 of the call lie in one piece of memory, or null: they straddle the pending samples
 // and the block, or two frames.  Two 16-byte loads per lane instead of eight 4-byte ones (the texture path moves whole lines).
 __device__ __forceinline__ const float* display_run(const DisplayParams& p, const unsigned char* row, const unsigned char* carry_row, int i)
@@ -169,7 +165,7 @@ template <int FMT> __device__ __forceinline__ void display_wave(const DisplayPar
     if (chunk == 0 && lane == 0 && f == 0 && land_from <= 0) levels[n0] = float2{s0.lo, s0.hi};
     if (a >= b) return;
 
-    const float gain = p.chan ? *(UniformFloatPtr) &p.chan[__builtin_amdgcn_readfirstlane(c)].gain : p.gain;
+    const float gain = channel_gain(p.chan, p.gain, c);
     const bool scale = p.src.hop_mode && gain != 1.0f;         // ref AudioDataCollector.h:88, as the load stage applies it
     const unsigned char* row = static_cast<const unsigned char*>(p.src.in) + (long long) c * p.src.in_row_bytes;
     const unsigned char* carry_row = p.src.carry ? p.src.carry + (long long) c * p.src.carry_row_bytes : nullptr;
@@ -197,8 +193,8 @@ template <int FMT> __device__ __forceinline__ void display_wave(const DisplayPar
         if (run) {
 #pragma unroll
             for (int q = 0; q < DISPLAY_PER_LANE / 4; q++) {
-                const floats4 v = reinterpret_cast<const floats4*>(run)[q];
-                x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
+                const dwords4 v = reinterpret_cast<const dwords4*>(run)[q];        // (a run starts on a dword boundary and no more)
+                x[4 * q] = __uint_as_float(v[0]); x[4 * q + 1] = __uint_as_float(v[1]); x[4 * q + 2] = __uint_as_float(v[2]); x[4 * q + 3] = __uint_as_float(v[3]);
             }
         } else {
 #pragma unroll
@@ -292,12 +288,7 @@ __global__ void __launch_bounds__(DISPLAY_THREADS) fx_display_kernel(const Displ
     const unsigned track = w / (unsigned) p.chunks;
     if (track >= (unsigned) p.C) return;
     const int c = (int) track, chunk = (int) (w - track * (unsigned) p.chunks);
-    switch (p.src.sample_format) {
-        case FX_SAMPLE_F16: display_wave<FX_SAMPLE_F16>(p, c, chunk, lane); break;
-        case FX_SAMPLE_S16: display_wave<FX_SAMPLE_S16>(p, c, chunk, lane); break;
-        case FX_SAMPLE_S24: display_wave<FX_SAMPLE_S24>(p, c, chunk, lane); break;
-        default:            display_wave<FX_SAMPLE_F32>(p, c, chunk, lane); break;
-    }
+    FX_FORMAT(p.src.sample_format, display_wave<FMT>(p, c, chunk, lane));
 }
 
 // New components (keep_next 0: levels, value, sub and next zero) or clear() (keep_next 1: next stays) for the listed tracks, or for
@@ -353,6 +344,9 @@ __global__ void __launch_bounds__(DISPLAY_THREADS) fx_display_get_kernel(const D
         if (from >= p.L) from -= p.L;
         v[q] = p.levels[(long long) c * p.L + from];
     }
+    // (floats from a dword boundary, not dwords4 / dwords2 of fx_blocks.hip.h: stored as unsigned words, this kernel's code comes out different)
+    struct __attribute__((packed, aligned(4))) floats4 { float x, y, z, w; };
+    struct __attribute__((packed, aligned(4))) floats2 { float x, y; };
     if (e0 + 1 < entries) *reinterpret_cast<floats4*>(p.out + 2 * e0) = floats4{v[0].x, v[0].y, v[1].x, v[1].y};
     else *reinterpret_cast<floats2*>(p.out + 2 * e0) = floats2{v[0].x, v[0].y};
 }

@@ -15,6 +15,9 @@ constexpr int MAX_ONSET_WINDOW = 32;
 // calls of at most this many frames per channel run finalise + smoothing/onset + history as one kernel (a quarter wavefront per channel)
 constexpr int FUSED_TAIL_MAX_FRAMES = 8;
 
+// bytes of one sample of a wire format (FX_SAMPLE_*, include/fx.h; what they widen to: fx_samples.hip.h)
+__host__ __device__ constexpr int sample_bytes(int fmt) { return fmt == FX_SAMPLE_F32 ? 4 : (fmt == FX_SAMPLE_S24 ? 3 : 2); }
+
 // What the frame kernel leaves per frame: every reduction over samples / bins / lags is done, the
 // scalar tail (pow, log10, sqrt, a few divisions) is not.  One thread per frame finishes it in
 // fx_finalise_kernel, where 64 frames share an instruction instead of one.
@@ -173,11 +176,12 @@ struct EpilogueParams {
 // with the launches on the context's stream) at a uniform address is an s_load_dword into an SGPR, like the kernel argument it stands
 // in for -- no vector register, no vector-memory instruction.
 typedef const float __attribute__((address_space(4)))* UniformFloatPtr;
-__device__ __forceinline__ float channel_gain(const FrameParams& p, int c)
+__device__ __forceinline__ float channel_gain(const ChannelSettings* chan, float gain, int c)
 {
-    if (!p.chan) return p.gain;
-    return *(UniformFloatPtr) &p.chan[__builtin_amdgcn_readfirstlane(c)].gain;
+    if (!chan) return gain;
+    return *(UniformFloatPtr) &chan[__builtin_amdgcn_readfirstlane(c)].gain;
 }
+__device__ __forceinline__ float channel_gain(const FrameParams& p, int c) { return channel_gain(p.chan, p.gain, c); }
 // What channel c's onset detector runs with (not uniform: the tails hold several channels in a wavefront).
 struct OnsetSettings { long long reset_frame; int window, type; float multiplier; };
 __device__ __forceinline__ OnsetSettings onset_settings(const EpilogueParams& p, int c)

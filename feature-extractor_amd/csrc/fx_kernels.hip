@@ -39,6 +39,7 @@ namespace fxk {
 
 #include "fx_wave.hip.h"
 #include "fx_fft.hip.h"
+#include "fx_samples.hip.h"
 #include "fx_blocks.hip.h"
 #include "fx_frame_kernel.hip.h"
 

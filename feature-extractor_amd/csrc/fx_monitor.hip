@@ -32,11 +32,10 @@
 
 namespace fxk {
 
-// (the load stage's widen_four / widen_one, fx_frame_kernel.hip.h: what the monitor makes of a sample is what the analysis kernels do)
-#include "fx_wave.hip.h"
-#include "fx_fft.hip.h"
-#include "fx_blocks.hip.h"
-#include "fx_frame_kernel.hip.h"
+// (the load stage's widen_four: what the monitor makes of a sample is what the analysis kernels do)
+#include "fx_wave.hip.h"          // f4
+#include "fx_samples.hip.h"
+#include "fx_blocks.hip.h"        // the shifted 16-byte read, dwords4
 
 namespace {
 
@@ -60,36 +59,21 @@ struct MixParams {
 constexpr int MIX_THREADS = 64;     // one wavefront: no barrier, and short blocks (441 / 480 / 512 samples) still spread over the chip
 constexpr int MIX_UNROLL = 32;      // rows whose loads are in flight before the first of them is added: a group is two round trips
 
-typedef unsigned __attribute__((vector_size(16), aligned(4))) quad;     // (fx_clips.hip: four dwords from any dword boundary)
-typedef const quad __attribute__((address_space(1)))* GlobalQuad;
-typedef const unsigned __attribute__((address_space(1)))* GlobalDword;
-
 // samples a lane mixes: 16 bytes of fp32 or of a 16-bit format, 12 bytes of packed 24-bit samples (which one 16-byte load covers at
 // any byte alignment)
 __host__ __device__ constexpr int lane_samples(int fmt) { return fmt == FX_SAMPLE_F16 || fmt == FX_SAMPLE_S16 ? 8 : 4; }
 
 // The PB (12 or 16) bytes of a row from byte `lane_off` (a multiple of 4) on.  Rows start at c * n * B bytes: any 2-byte boundary for
 // the 16-bit formats and any byte for packed s24.  So the piece is read as the gather reads a clip: the aligned dwords around it with
-// one global_load_dwordx4 (and a fifth dword where 16 bytes straddle five: RawPiece), shifted into place with v_alignbyte_b32 once
-// the row's turn in the sum has come (shifted_piece; shifting at the load would wait for it).  The shift is the row's, the same in
+// one global_load_dwordx4 (and a fifth dword where 16 bytes straddle five: RawPiece, fx_blocks.hip.h), shifted into place with v_alignbyte_b32
+// once the row's turn in the sum has come (shifted_piece; shifting at the load would wait for it).  The shift is the row's, the same in
 // every lane, and 0 for fp32.  A lane's piece may run past its row's end into the next row, and the last row's into the MIX_SLACK
 // bytes that follow the block (fx_context.h, monitor_launch): those samples are not stored.
-struct RawPiece { quad q; unsigned q4; };
 template <int B> __device__ __forceinline__ unsigned row_shift(long long row_off) { return B == 4 ? 0u : (unsigned) row_off & 3u; }
 template <int B, int PB> __device__ __forceinline__ RawPiece load_piece(const unsigned char* in, long long row_off, long long lane_off)
 {
     const unsigned sh = row_shift<B>(row_off);
-    const unsigned char* lo = in + (row_off - sh) + lane_off;
-    RawPiece r;
-    r.q = *(GlobalQuad) lo;
-    r.q4 = 0;
-    if (PB == 16 && sh != 0) r.q4 = *(GlobalDword) (lo + 16);
-    return r;
-}
-__device__ __forceinline__ uint4 shifted_piece(const RawPiece& r, unsigned sh)
-{
-    return uint4{__builtin_amdgcn_alignbyte(r.q[1], r.q[0], sh), __builtin_amdgcn_alignbyte(r.q[2], r.q[1], sh),
-                 __builtin_amdgcn_alignbyte(r.q[3], r.q[2], sh), __builtin_amdgcn_alignbyte(r.q4, r.q[3], sh)};
+    return load_raw_piece(in + (row_off - sh) + lane_off, PB == 16 ? sh : 0u);
 }
 // a lane reads at most the 20 bytes from the dword boundary below its piece, and its piece starts inside the block
 constexpr int MIX_SLACK = 32;
@@ -218,14 +202,12 @@ constexpr int LISTEN_THREADS = 64;      // one wavefront, lanes along the sample
 constexpr int LISTEN_QUADS = 2;         // 16-byte pieces a lane moves, both loads in flight before the first store
 constexpr int LISTEN_TILE = LISTEN_THREADS * 4 * LISTEN_QUADS;     // 512 samples: a 441- / 480- / 512-sample tick is one wavefront a listener
 
-typedef quad __attribute__((address_space(1)))* GlobalQuadOut;
-
 // Workgroup (one wavefront) w copies samples [tile * 512, +512) of output row list[w / tiles].output over row list[w / tiles].track of
 // the planar block, bit for bit (the words move as unsigned: a NaN keeps its payload).  Piece j of lane l is the four samples from
 // tile * 512 + j * 256 + 4 l on: a wavefront's loads and stores are 1 KB of consecutive addresses.  The source row starts on a 32-byte
 // boundary (stride is a multiple of 8), so a piece is one aligned 16-byte load, also where the row ends inside it: the padding up to
 // `stride` is allocated, read and not stored.  The destination row starts at track * n floats -- a dword boundary and no more when
-// n % 4 != 0 -- so a piece is stored as four dwords from a dword boundary (`quad`), and the n % 4 samples of the tail one dword at a
+// n % 4 != 0 -- so a piece is stored as four dwords from a dword boundary (dwords4), and the n % 4 samples of the tail one dword at a
 // time: nothing is stored past the row's end, where the next track's row begins.  Every offset is 64-bit (65 536 tracks x 8193 samples
 // x 4 bytes pass 2^31).  The entry is the same in every lane: it arrives through the scalar cache.
 __global__ void __launch_bounds__(LISTEN_THREADS)
@@ -246,7 +228,7 @@ fx_monitor_listen_kernel(const ListenParams p)
     for (int j = 0; j < LISTEN_QUADS; j++) {
         const long long i = i0 + (long long) j * (LISTEN_THREADS * 4);
         if (i + 4 <= p.n) {
-            *(GlobalQuadOut) (dst + i) = quad{v[j].x, v[j].y, v[j].z, v[j].w};
+            *(GlobalDwords4Out) (dst + i) = dwords4{v[j].x, v[j].y, v[j].z, v[j].w};
         } else if (i < p.n) {
             const int left = (int) (p.n - i);       // 1 .. 3
             dst[i] = v[j].x;
@@ -279,6 +261,7 @@ hipError_t launch_monitor_kernels(MixParams p, float* part, float* out, int samp
     const long long elements = 2ll * p.stride;
     if (wgs > 0x7fffffffll || elements > 0x7fffffffll) return hipErrorInvalidValue;
     const dim3 grid((unsigned) wgs), block(MIX_THREADS);
+    // (not FX_FORMAT: an unknown format is refused here, and the code object keeps its kernels in this order)
     switch (sample_format) {
         case FX_SAMPLE_F32: hipLaunchKernelGGL(fx_monitor_mix_kernel<FX_SAMPLE_F32>, grid, block, 0, stream, p); break;
         case FX_SAMPLE_F16: hipLaunchKernelGGL(fx_monitor_mix_kernel<FX_SAMPLE_F16>, grid, block, 0, stream, p); break;

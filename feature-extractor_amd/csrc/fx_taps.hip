@@ -27,10 +27,9 @@
 
 namespace fxk {
 
-#include "fx_wave.hip.h"
-#include "fx_fft.hip.h"
-#include "fx_blocks.hip.h"
-#include "fx_frame_kernel.hip.h"
+#include "fx_wave.hip.h"          // f4
+#include "fx_samples.hip.h"
+#include "fx_blocks.hip.h"        // BlockStream
 
 namespace {
 
@@ -71,7 +70,8 @@ template <int FMT> __device__ __forceinline__ float first_sample(const fx_tap_so
 template <int N, int FMT> __device__ void load_window(const TapsParams& p, int c, float* win)
 {
     constexpr int H = N / 2;
-    // (c is the workgroup's channel: uniform, the gain a scalar as in the analysis kernels -- channel_gain)
+    // (c is the workgroup's channel: uniform, the gain a scalar as in the analysis kernels -- channel_gain, fx_kernels.h, written out:
+    // through the helper this kernel's code comes out different)
     const float gain = p.chan ? *(UniformFloatPtr) &p.chan[__builtin_amdgcn_readfirstlane(c)].gain : p.gain;
     for (int i = threadIdx.x; i < N; i += TAP_THREADS) {
         float x;
@@ -102,12 +102,7 @@ __global__ void __launch_bounds__(TAP_THREADS) fx_taps_kernel(const TapsParams p
     using P = PlainPlan<N>;
 
     // the overlapped window (RealTimeAudioDataOverlapper::getNextBuffer, RealTimeAudioAnalysis.h:205-228)
-    switch (p.src.sample_format) {
-        case FX_SAMPLE_F16: load_window<N, FX_SAMPLE_F16>(p, c, aux); break;
-        case FX_SAMPLE_S16: load_window<N, FX_SAMPLE_S16>(p, c, aux); break;
-        case FX_SAMPLE_S24: load_window<N, FX_SAMPLE_S24>(p, c, aux); break;
-        default:            load_window<N, FX_SAMPLE_F32>(p, c, aux); break;
-    }
+    FX_FORMAT(p.src.sample_format, (load_window<N, FMT>(p, c, aux)));
     __syncthreads();
     for (int i = tid; i < N; i += TAP_THREADS) o_win[i] = aux[i];
 
