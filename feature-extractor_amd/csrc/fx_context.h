@@ -178,6 +178,8 @@ struct fx_context {
     float* d_out_raw = nullptr;   // staging for host output
     float* d_out_sm = nullptr;
     size_t raw_cap = 0, in_cap = 0, out_cap = 0;
+    float* d_flux_park = nullptr; // FrameParams::flux_park: [C][wavefronts per channel][N/2], 1024-point batch calls with both analysers (flux_park_need)
+    size_t flux_park_cap = 0;
 
     unsigned char* d_osc = nullptr;   // [C][stride]: fx_get_osc_datagrams' messages before they go to a host buffer
     size_t osc_cap = 0;

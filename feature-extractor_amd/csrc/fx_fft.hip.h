@@ -40,6 +40,8 @@ template <int N> struct Geo {
     static constexpr int HBUF_B = 4 * BIMG + 2 * M + 16;
     static constexpr int BUF_B0 = CBUF_B > RBUF_B ? (CBUF_B > HBUF_B ? CBUF_B : HBUF_B) : (RBUF_B > HBUF_B ? RBUF_B : HBUF_B);
     static constexpr int BUF_BYTES = (BUF_B0 > 4 * N ? BUF_B0 : 4 * N) + 15 & ~15;     // 16-byte multiple, >= N floats (lag-scan spill)
+    // (1024 points: the batch kernel keeps a wavefront's flux image in bytes 5632 .. 8708 of this buffer -- FluxRuns, fx_frame_kernel.hip.h.
+    // A section that comes to write past byte 5632 must be added to FluxRuns<N>::LIVE_BYTES, whose static assert then moves or refuses the image.)
     static constexpr int LOG2N  = (N == 256) ? 8 : (N == 512) ? 9 : (N == 1024) ? 10 : (N == 2048) ? 11 : 12;
     // first FFT pass: R inputs per item, G items per lane, R*G == P
     static constexpr int RA     = (N == 256) ? 4 : ((N == 512 || N == 2048) ? 8 : 16);
@@ -281,6 +283,8 @@ constexpr unsigned lds_exchange_kinds(const char* text, unsigned shipped)
     for (; *text >= '0' && *text <= '9'; text++) v = 10 * v + (unsigned) (*text - '0');
     return v;
 }
+// (the same reading under a neutral name, for the switches that are not masks of transform kinds)
+constexpr unsigned costing_switch(const char* text, unsigned shipped) { return lds_exchange_kinds(text, shipped); }
 constexpr unsigned LDS_EXCHANGE_KINDS = lds_exchange_kinds(FX_XK_TEXT(FX_EXP_LDS_EXCHANGE), 0u);
 static_assert(LDS_EXCHANGE_KINDS <= 15u, "FX_EXP_LDS_EXCHANGE: a mask of the four transform kinds");
 
@@ -292,6 +296,7 @@ static_assert(LDS_EXCHANGE_KINDS <= 15u, "FX_EXP_LDS_EXCHANGE: a mask of the fou
 // Layout: [item][11] float2, no padding (rows of 88 B: the 16 lanes of a ds_write_b64 group and the 32 of a ds_read_b64 group fall
 // on distinct banks; lanes that want the same element of the same item read one address).
 template <int N> struct RealExchange {
+    // (the rows end at byte 8 * row(N / RA): at 1024 points the largest live image of the wave's buffer, FluxRuns<N>::LIVE_BYTES)
     // 1024 (un-split, one item per lane) and 4096 (split, two per half): 16-element items, next pass at stride 16.
     // 2048 (split) has 8-element items (a radix-2 and a radix-4 stage) of which only e[6] = conj(e[2]) is exact: 7 stores of 8 are
     // the same four store instructions and the sign flips cost 1 % (measured, profiles/r03_variants.txt): not used there.

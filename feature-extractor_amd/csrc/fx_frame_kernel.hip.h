@@ -23,6 +23,12 @@
 #define FX_STOP(k, ...)
 #endif
 #define FX_KEEP(v) asm volatile("" :: "v"(v))
+// Costing builds only (tools/build_variants.py small name=-DFX_EXP_FLUX_NO_WAIT=1): the 1024-point batch forms do not wait for their turn at
+// the channel's flux state.  The work is the same -- the same loads, stores, fence and counter store -- and the flux column is garbage; what the
+// build measures is the ceiling of any scheme that removes the per-frame hand-over (profiles/flux_runs_bound.txt).  Read as a constant
+// expression like FX_EXP_LDS_EXCHANGE: spelled out, the macro's own name stands here when nothing defines it.
+constexpr unsigned FLUX_NO_WAIT = costing_switch(FX_XK_TEXT(FX_EXP_FLUX_NO_WAIT), 0u);
+static_assert(FLUX_NO_WAIT <= 1u, "FX_EXP_FLUX_NO_WAIT: 0 or 1");
 
 // ---------------------------------------------------------------------------------------------
 // frame load: global -> real LDS image, 16 B per lane, coalesced
@@ -256,7 +262,9 @@ template <int N> struct Occ {
     // CH*K a multiple of 4, sharing one twiddle table:
     //   <= 512 points : 1 x 8, three workgroups per CU    -> 6 waves per SIMD, <= 80 VGPRs (the 4 KB images leave the LDS room;
     //                   +6 % at 512 points over 4 waves per SIMD, round 3: the kernels are bound by latency, not by issue)
-    //   1024 points   : 1 x 8, two workgroups per CU      -> 4 waves per SIMD, <= 128 VGPRs (all the LDS holds)
+    //   1024 points   : 1 x 8, two workgroups per CU      -> 4 waves per SIMD, <= 128 VGPRs (all the LDS holds: 8 KB of twiddles, eight
+    //                   8720-byte buffers and 3 KB for the channel's flux image; the form that keeps the flux state by runs -- FluxRuns,
+    //                   below -- has every wavefront's image and flag inside its buffer and no channel image: 77 952 B a workgroup)
     //   2048 points   : 3 x 4 = 12 waves, one workgroup   -> 3 per SIMD, <= 168 VGPRs
     //   4096 points   : 1 x 8 (the 160 KB to the byte: 24 KB of twiddles -- CompactTw -- and eight 17 KB buffers, the flux state
     //                   in global memory; until round 4 seven wavefronts beside the whole 32 KB table and the state's LDS image)
@@ -270,13 +278,88 @@ template <int N> struct FrameLds {
     static constexpr bool WIDE = N == 4096;
     static constexpr int TW_ENTRIES = WIDE ? CompactTw<N>::ENTRIES : N;
     static constexpr int WIDE_TURN_ENTRY = WIDE ? CompactTw<N>::OFF_GAP : 0;      // [channels <= 8][2] ints in the image's 128-byte gap
-    __host__ __device__ static constexpr int prev_floats(bool direct) { return (direct || WIDE) ? 0 : Geo<N>::BIMG + (Geo<N>::BQ ? 0 : 4); }
-    __host__ __device__ static constexpr size_t bytes(int ch, int k, bool direct)
+    // runs: the form that keeps the flux state by runs (FluxRuns, below): every wavefront's image and flag are inside its own buffer, so the
+    // layout has no channel image and no turn counter
+    __host__ __device__ static constexpr int prev_floats(bool direct, bool runs = false) { return (direct || WIDE || runs) ? 0 : Geo<N>::BIMG + (Geo<N>::BQ ? 0 : 4); }
+    __host__ __device__ static constexpr size_t bytes(int ch, int k, bool direct, bool runs = false)
     {
-        return sizeof(f2) * TW_ENTRIES + (size_t) ch * sizeof(float) * prev_floats(direct) + (size_t) ch * k * Geo<N>::BUF_BYTES;
+        return sizeof(f2) * TW_ENTRIES + (size_t) ch * sizeof(float) * prev_floats(direct, runs) + (size_t) ch * k * Geo<N>::BUF_BYTES;
     }
 };
 static_assert(FrameLds<4096>::bytes(1, 8, false) <= 160 * 1024 && FrameLds<4096>::bytes(8, 1, true) <= 160 * 1024, "eight 4096-point wavefronts per CU");
+
+// Flux state by runs (the 1024-point batch form with both analysers; fx_flux_runs.h).  Everywhere else a channel's wavefronts take frames
+// round robin and every frame waits for its turn at the channel's one flux image; the eight wavefronts then move as a convoy, and one
+// late frame (the data-dependent lag search) stalls all behind it: 2.6 % of the kernel, measured with the wait compiled out
+// (profiles/flux_runs_bound.txt).  Here a wavefront analyses a contiguous run of the unit's frames against a flux image of its OWN, kept
+// in the part of its buffer that no section writes since the second exchange left LDS, and the state crosses from wavefront to wavefront
+// once per run:
+//   - wavefront 0 starts from the channel's state;
+//   - any other wavefront whose first frame is accepted (the usual case) parks that frame's re in global memory (FrameParams::flux_park,
+//     one coalesced 2 KB store per run), leaves its flux open and carries on; when its run is over it waits for its predecessor's
+//     "run finished" flag and forms the parked frame's flux against the predecessor's final image -- the same terms in the same lanes
+//     through the same reduction, so the bits are those of the serial order;
+//   - frames that are NOT accepted (silence, NaN, a track below about -60 dB) before the run's first accepted one need nothing from the
+//     predecessor: they replace nothing, and a frame that is not accepted has no flux (the reference leaves the feature alone,
+//     SpectralCharacteristics.h:121-123; fx_finalise_kernel reads FramePart::flux under the same test of the same mag_sum).  So nothing
+//     inside a run ever waits for another wavefront, and a silent channel's wavefronts run side by side like any other's;
+//   - a wavefront that accepted nothing at all takes its predecessor's final image as its own before it says "finished".
+// By induction every wavefront's image at the end of its run is the channel's state after the run's last frame; the last one's goes to
+// FrameParams::prev_re.  All waits are behind the runs, on wavefronts of the same workgroup (resident), each on its predecessor only,
+// wavefront 0 on nobody: what is waited for is the skew between runs of equal length, plus an image copy per wavefront of a chain that
+// accepted nothing.  The bound is FrameParams::spin_limit polls per frame of the run (the skew grows with the run), reported through
+// FrameParams::err like the hand-over between work units.
+// The flag is the int behind the wavefront's image, in its own buffer; this form's layout has no channel image (FrameLds::prev_floats).
+#include "fx_flux_runs.h"
+template <int N> struct FluxRuns {
+    static constexpr bool AVAILABLE = N == 1024 && LDS_EXCHANGE_KINDS == 0u && FLUX_NO_WAIT == 0u;      // (a costing build that keeps a complex image keeps the turns)
+    static constexpr int max2(int a, int b) { return a > b ? a : b; }
+    // the end of the largest image a section leaves in the wave's buffer: the real image, the first exchange's rows, the harmonic
+    // scratch (bins image + peak list), the lag scan's plain image -- and the whole complex image where a costing build keeps the LDS
+    // form of the second exchange (such a build has no room for the image: AVAILABLE)
+    static constexpr int LIVE_BYTES = max2(max2(max2(Geo<N>::RBUF_B, 8 * RealExchange<N>::row(N / Geo<N>::RA)), max2(Geo<N>::HBUF_B, 4 * N)),
+                                           LDS_EXCHANGE_KINDS != 0u ? Geo<N>::CBUF_B : 0);
+    static constexpr int IMAGE_BYTES = 4 * Geo<N>::BIMG;
+    static constexpr int OFF = FLUX_IMAGE_1024.offset_bytes / 4;                 // floats from the start of the wave's buffer
+    static constexpr int FLAG = OFF + Geo<N>::BIMG;                              // the "run finished" flag: the int behind the image
+    static constexpr bool PLACED = FLUX_IMAGE_1024.fits(Geo<N>::BUF_BYTES, IMAGE_BYTES + 4, LIVE_BYTES);
+};
+static_assert(!FluxRuns<1024>::AVAILABLE || FluxRuns<1024>::PLACED, "flux runs: the wavefront's flux image overlaps a live image or leaves the wavefront's buffer");
+static_assert(Geo<1024>::BUF_BYTES % 4 == 0, "flux runs: the predecessor's image and flag are one buffer back");
+template <int N, bool SPEC, bool HARM, bool DIRECT, bool BLOCKS> constexpr bool flux_runs_form() { return FluxRuns<N>::AVAILABLE && SPEC && HARM && !DIRECT && !BLOCKS; }
+
+// what a wavefront of that form carries from frame to frame of its run (wave-uniform)
+struct FluxRunState {
+    bool own;           // the wavefront's image is the channel's state before the frame at hand
+    bool parked;        // the run's first accepted frame left its flux open
+    int  parked_t;      // ... that frame
+    int  row;           // the wavefront's row of FrameParams::flux_park
+};
+
+// the flux sum's terms of one lane (ref SpectralCharacteristics.h:76-79)
+template <int U> __device__ __forceinline__ double flux_terms(const float (&re)[U], const float (&pvf)[U])
+{
+    double flux = 0.0;
+#pragma unroll
+    for (int j = 0; j < U; j++) {
+        const double pv = (double) pvf[j];
+        const double v = (double) re[j];
+        const double diff = v * v - pv * pv;                       // :76
+        flux += fmax(diff, 0.0);                                   // :77-79 (a NaN difference adds nothing, as `if (diff > 0)`)
+    }
+    return flux;
+}
+// wait for the predecessor's run (bounded; a wait that gives up says so where the host looks at its next synchronisation)
+// `frames`: the run's length -- the wait is for the skew between two runs, which grows with them, so the bound does too
+__device__ __forceinline__ void flux_wait_pred(const FrameParams& p, const int* pred_done, int lane, int frames)
+{
+    const unsigned long long limit = (unsigned long long) p.spin_limit * (unsigned long long) (frames > 1 ? frames : 1);
+    unsigned long long spins = 0;
+    bool there;
+    while (!(there = __hip_atomic_load(pred_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != 0) && ++spins < limit)
+        __builtin_amdgcn_s_sleep(2);
+    if (!there && lane == 0) __hip_atomic_store(p.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // One wavefront's view of the frame it is analysing: where its buffers are and the constants every section
 // uses.  The member functions are the sections of the reference's two run() loops in the order the kernel
@@ -292,7 +375,8 @@ static_assert(FrameLds<4096>::bytes(1, 8, false) <= 160 * 1024 && FrameLds<4096>
 // N/2 samples of [the channel's pending samples | its block] -- fx_push_samples without the re-blocking pass (FrameParams::block_mode).
 // LCG: the groups of the wavefront's record of lane-derived constants (LaneConsts; the 1024-point batch kernel), 0 = no record: `lc` is
 // then never read and every section forms what it needs from the lane number, frame by frame.
-template <int N, bool DIRECT = false, bool HOIST = false, bool WIDE = false, bool BLOCKS = false, unsigned LCG = 0u> struct FrameWave {
+// RUNS: the flux state by runs (FluxRuns): `rs` is the wavefront's run state, `prev` / `turn` are not used.
+template <int N, bool DIRECT = false, bool HOIST = false, bool WIDE = false, bool BLOCKS = false, unsigned LCG = 0u, bool RUNS = false> struct FrameWave {
     typedef Geo<N> G;
     typedef LaneConsts<N, LCG> LCT;
     static constexpr int M = G::M, P = G::P, U = G::U, HALF = N / 2;
@@ -312,6 +396,7 @@ template <int N, bool DIRECT = false, bool HOIST = false, bool WIDE = false, boo
     float  scale;       // JUCE inverse-transform scale 1/N
     int    c, T, t;     // channel, frames in this call, this frame
     const LCT* lc = nullptr;    // the wavefront's lane-derived constants (LCG != 0)
+    FluxRunState* rs = nullptr; // RUNS: what the wavefront carries through its run
 
     // |re| of the raw spectrum around and inside the lane's bins, kept from the harmonic FFT to the harmonic tail
     struct HarmonicSpectrum { float hre[U]; float left2, left1, right1; double sum, max; };
@@ -395,16 +480,19 @@ FX_MARK("load");
         if constexpr (LCT::REV) { static_assert(G::GA == 1, "one first-pass item per lane"); return lc->rbase; }
         else return rbuf + first_pass_rbase<N>(lane, g);
     }
-    __device__ __forceinline__ double sum_squares(int lane, float (&xr)[P]) const
+    // the frame, in registers, in the order the first FFT pass consumes it; the LDS buffer is free again after this read
+    __device__ __forceinline__ void raw_to_regs(int lane, float (&xr)[P]) const
     {
-FX_MARK("rms");
-        // the frame, in registers, in the order the first FFT pass consumes it; the LDS buffer is
-        // free again after this read
 #pragma unroll
         for (int g = 0; g < G::GA; g++)
 #pragma unroll
             for (int j = 0; j < G::RA; j++) xr[g * G::RA + j] = first_pass_from(lane, g)[first_pass_rstep<N>(j)];
         wave_fence();
+    }
+    __device__ __forceinline__ double sum_squares(int lane, float (&xr)[P]) const
+    {
+FX_MARK("rms");
+        raw_to_regs(lane, xr);
         double s = 0.0;
 #pragma unroll
         for (int i = 0; i < P; i++) s += (double) (xr[i] * xr[i]);
@@ -529,12 +617,11 @@ FX_MARK("flatprod");
         if constexpr (LCT::IMAGES) return lc->left2 + LaneOffsets<N>::left_back(2);
         else return reinterpret_cast<const float*>(cbuf) + bimg<N>(U * lane);
     }
-    __device__ __forceinline__ void spectral(int lane, const float (&xr)[P], double sum_sq) const
+    // a3 + a4: the Bartlett-windowed frame's transform; leaves re of bins < M in the wave's buffer (own_bins) and returns the lane's
+    // max(|re|, |im|) over bins < M/2
+    __device__ __forceinline__ float spectral_transform(int lane, const float (&xr)[P]) const
     {
         float spec_aux = 0.0f;
-FX_MARK("spec_fft");
-        // ---------------- spectral analyser (ref RealTimeAnalyser.h:212-224) -----------------------
-        lane = FX_OPQ(0, lane);
         {
             float xw[P];                                                       // a3 Bartlett window
             // sample index of input j of item g is nlow + ITEMS_A*r(j) with nlow < ITEMS_A, so it lies in
@@ -555,6 +642,14 @@ FX_MARK("spec_fft");
             }
             spec_aux = fft_from_regs<N, false, OUT_RE_LOW_MAXABS, WIDE>(xw, cbuf, tw, p.first_tw, lane, 0.0f, nullptr, twr, tw_global(), lc);   // a4
         }
+        return spec_aux;
+    }
+    __device__ __forceinline__ void spectral(int lane, const float (&xr)[P], double sum_sq) const
+    {
+FX_MARK("spec_fft");
+        // ---------------- spectral analyser (ref RealTimeAnalyser.h:212-224) -----------------------
+        lane = FX_OPQ(0, lane);
+        const float spec_aux = spectral_transform(lane, xr);
         FX_STOP(6, FX_KEEP(spec_aux); return);
 FX_MARK("spec_sums");
         {
@@ -613,6 +708,7 @@ FX_MARK("flux");
             double flux = 0.0;
             {
                 float pvf[U];
+                bool open = false;                                                      // RUNS: left open (nothing to subtract yet; wave-uniform)
                 if constexpr (DIRECT) {
                     float* state = p.prev_re + (size_t) c * M + U * lane;              // the lane's U bins, coalesced (16-byte pieces from 512 points on)
                     lds_load_block<U>(state, pvf);                                      // (plain wide loads / stores: global memory here)
@@ -627,23 +723,39 @@ FX_MARK("flux");
                     if (accepted) lds_store_block<U>(state, re);                        // :138
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                     if (lane == 0) __hip_atomic_store(turn, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                } else if constexpr (RUNS) {
+                    // the wavefront's own image, FluxRuns<N>::OFF floats behind the bins image the transform left: no counter, no fence
+                    float* mine = const_cast<float*>(own_bins(lane)) + FluxRuns<N>::OFF;
+                    if (rs->own) {
+                        lds_load_block<U>(mine, pvf);
+                        if (accepted) lds_store_block<U>(mine, re);                     // :138 (only on the accepted path)
+                    } else if (accepted) {
+                        // the run's first frame: its flux stays open until the predecessor's run is over (frame_kernel_body)
+                        lds_store_block<U>(p.flux_park + ((size_t) rs->row * M + U * lane), re);
+                        lds_store_block<U>(mine, re);
+                        open = true;
+                        rs->parked = true;
+                        rs->parked_t = t;
+                        rs->own = true;
+                    } else {
+                        // not accepted, and nothing accepted in the run before it: the state is still the predecessor's, which nobody
+                        // waits for here (its whole run: a silent channel would run its wavefronts one after the other).  Nor is it
+                        // needed: a frame that is not accepted has no flux -- the reference leaves the feature alone (:121-123) and
+                        // fx_finalise_kernel reads FramePart::flux under the same test of the same mag_sum -- and replaces nothing
+                        open = true;
+                    }
                 } else {
                     // (the hand-over costs 2 % of the kernel, and not because of the length of this section: round 2, profiles/NOTEBOOK.md (ix))
-                    while (__hip_atomic_load(turn, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != t)
-                        __builtin_amdgcn_s_sleep(1);
+                    if constexpr (!(FLUX_NO_WAIT != 0u && N == 1024))
+                        while (__hip_atomic_load(turn, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != t)
+                            __builtin_amdgcn_s_sleep(1);
                     // the turn is held for two LDS reads and two writes only: the next frame's wave is usually waiting for it
                     lds_load_block<U>(prev + bimg<N>(U * lane), pvf);
                     if (accepted) lds_store_block<U>(prev + bimg<N>(U * lane), re);     // :138 (only on the accepted path)
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                     if (lane == 0) __hip_atomic_store(turn, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
-#pragma unroll
-                for (int j = 0; j < U; j++) {
-                    const double pv = (double) pvf[j];
-                    const double v = (double) re[j];
-                    const double diff = v * v - pv * pv;                       // :76
-                    flux += fmax(diff, 0.0);                                   // :77-79 (a NaN difference adds nothing, as `if (diff > 0)`)
-                }
+                if (!RUNS || !open) flux = flux_terms<U>(re, pvf);
             }
             FX_STOP(8, FX_KEEP(mag_sum); FX_KEEP(b1); FX_KEEP(b2); FX_KEEP(lhr); FX_KEEP(max_mag); FX_KEEP(maxabs); FX_KEEP(flat_sum); FX_KEEP(cnt);
                        FX_KEEP(floc.mant); FX_KEEP(floc.exp); FX_KEEP(femin); FX_KEEP(femax); FX_KEEP(flux); return);
@@ -1118,7 +1230,8 @@ __device__ __forceinline__ void frame_kernel_body(const FrameParams& p_arg)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     //   WIDE (4096 points): compact twiddle image, the hand-over counters (8 bytes per channel) in its gap | one buffer per wave
     constexpr bool WIDE = FrameLds<N>::WIDE;
-    constexpr int PREV_FLOATS = FrameLds<N>::prev_floats(DIRECT);
+    constexpr bool RUNS = flux_runs_form<N, SPEC, HARM, DIRECT, BLOCKS>();       // the flux state by runs (FluxRuns): no channel image
+    constexpr int PREV_FLOATS = FrameLds<N>::prev_floats(DIRECT, RUNS);
     constexpr size_t WAVE_BYTES = G::BUF_BYTES;
     const int CH = p.ch_per_wg, K = p.waves_per_ch;
     f2*    tw    = reinterpret_cast<f2*>(smem);                             // [N], or the compact image
@@ -1186,6 +1299,19 @@ __device__ __forceinline__ void frame_kernel_body(const FrameParams& p_arg)
         }
         __syncthreads();
     }
+    // the flux state by runs: wavefront 0 of a channel starts from the channel's state, in its own image; every flag down
+    float* own_image = rbuf + FluxRuns<N>::OFF;
+    int* run_done = reinterpret_cast<int*>(rbuf + FluxRuns<N>::FLAG);           // this wavefront's "run finished"; the predecessor's is one buffer back
+    if constexpr (RUNS) {
+        if (live) {
+            if (slot == 0) {
+                float st[G::U];
+                lds_load_block<G::U>(p.prev_re + (size_t) c * M + G::U * lane0, st);
+                lds_store_block<G::U>(own_image + bimg<N>(G::U * lane0), st);
+            }
+            if (lane0 == 0) *run_done = 0;
+        }
+    } else
     if (live && !DIRECT) {
         if constexpr (!WIDE)
             for (int i = lane0 + 64 * slot; i < M; i += 64 * K) prev[bimg<N>(i)] = p.prev_re[(size_t) c * M + i];
@@ -1220,14 +1346,18 @@ __device__ __forceinline__ void frame_kernel_body(const FrameParams& p_arg)
         if (lane0 == 0) v = __hip_atomic_fetch_add(turn + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         return __builtin_amdgcn_readfirstlane(v);
     };
-    for (int t = live ? (CLAIM ? next_frame(0) : t_begin + slot) : t_end; t < t_end; t = next_frame(t)) {
+    // RUNS: the wavefront's contiguous run of the unit's frames (flux_run_begin) instead of every K-th
+    FluxRunState frs{slot == 0, false, 0, c * K + slot};
+    const int t_first = RUNS ? t_begin + flux_run_begin(t_end - t_begin, K, slot) : t_begin + slot;
+    const int t_stop = RUNS ? t_begin + flux_run_begin(t_end - t_begin, K, slot + 1) : t_end;
+    for (int t = live ? (CLAIM ? next_frame(0) : t_first) : t_stop; t < t_stop; t = RUNS ? t + 1 : next_frame(t)) {
         constexpr bool HOIST = SPEC && !HARM && N == 1024;       // (see FX_OPQ)
         const int lane = LaneConsts<N, LCG>::TOP ? lane0 : FX_OPQ(15, lane0);
         // uniform per-frame results go to LDS as soon as they exist instead of occupying ~28 VGPRs
         // in every lane for the whole frame
         FramePart* fpl = p.part + ((size_t) c * T + t);
         if (lane == 0) fpl->flags = 0;            // the harmonic tail sets it; the other fields are read only where written
-        const FrameWave<N, DIRECT, HOIST, WIDE, BLOCKS, LCG> w{p, tw, &twr, prev, turn, cbuf, rbuf, fpl, nyquist, rnyq, frpb, scale, c, T, t, &lcs};
+        const FrameWave<N, DIRECT, HOIST, WIDE, BLOCKS, LCG, RUNS> w{p, tw, &twr, prev, turn, cbuf, rbuf, fpl, nyquist, rnyq, frpb, scale, c, T, t, &lcs, &frs};
 
         const double ssq_lane = w.load_frame(lane);
         float xr[P];
@@ -1254,7 +1384,7 @@ __device__ __forceinline__ void frame_kernel_body(const FrameParams& p_arg)
         }
         FX_STOP(6, continue); FX_STOP(7, continue); FX_STOP(8, continue); FX_STOP(9, continue); FX_STOP(10, continue);
         if constexpr (HARM) {
-            typename FrameWave<N, DIRECT, HOIST, WIDE, BLOCKS, LCG>::HarmonicSpectrum hs;
+            typename FrameWave<N, DIRECT, HOIST, WIDE, BLOCKS, LCG, RUNS>::HarmonicSpectrum hs;
             if constexpr (G::SPLIT) w.template load_raw<true>(lane, xr);
             w.harmonic_spectrum(lane, xr, hs);
             FX_STOP(11, FX_KEEP(hs.sum); FX_KEEP(hs.max); FX_KEEP(hs.left2); FX_KEEP(hs.left1); FX_KEEP(hs.right1); for (int j = 0; j < G::U; j++) FX_KEEP(hs.hre[j]); continue);
@@ -1270,16 +1400,53 @@ __device__ __forceinline__ void frame_kernel_body(const FrameParams& p_arg)
     }
 
     if constexpr (DIRECT) return;                       // (the flux state was replaced in place)
+    // (RUNS: the lane number formed anew behind the frame loop -- v_mbcnt -- so that nothing compared with it in the prologue stays in a
+    // register, or in scratch, across the loop: the kernel is at its 128 VGPRs)
+    const int lane_e = RUNS ? (int) __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : lane0;
+    if constexpr (RUNS) {
+        if (live && t_first < t_stop) {
+            // The run is over.  With a frame accepted the image is final: say so first -- the successor may be waiting -- then close the
+            // flux that frame left open against the predecessor's final image.  With nothing accepted the image IS the predecessor's:
+            // take it, then say so.
+            if (frs.own) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                if (lane_e == 0) __hip_atomic_store(run_done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            if (slot > 0) {
+                flux_wait_pred(p, run_done - G::BUF_BYTES / 4, lane_e, t_stop - t_first);
+                float re[G::U], pvf[G::U];
+                lds_load_block<G::U>(own_image - G::BUF_BYTES / 4 + bimg<N>(G::U * lane_e), pvf);
+                if (!frs.own) {
+                    lds_store_block<G::U>(own_image + bimg<N>(G::U * lane_e), pvf);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    if (lane_e == 0) __hip_atomic_store(run_done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                if (frs.parked) {
+                    lds_load_block<G::U>(p.flux_park + ((size_t) frs.row * M + G::U * lane_e), re);
+                    // (the frame's other recorded sums went through their reduction with a zero in the flux's place; here the zeros are theirs)
+                    double flux = flux_terms<G::U>(re, pvf), z1 = 0.0, z2 = 0.0, z3 = 0.0;
+                    wave_sum4(lane_e, flux, z1, z2, z3);
+                    if (lane_e == 0) p.part[(size_t) c * T + frs.parked_t].flux = flux;
+                }
+            }
+        }
+        __syncthreads();
+        if (live) {
+            const float* last = reinterpret_cast<const float*>(per_wave + WAVE_BYTES * (chl * K + flux_last_slot(t_end - t_begin, K))) + FluxRuns<N>::OFF;
+            for (int i = lane_e + 64 * slot; i < M; i += 64 * K) p.prev_re[(size_t) c * M + i] = last[bimg<N>(i)];
+        }
+    } else {
     __syncthreads();
     if constexpr (!WIDE)                                // (WIDE: in place as well)
         if (live)
-            for (int i = lane0 + 64 * slot; i < M; i += 64 * K) p.prev_re[(size_t) c * M + i] = prev[bimg<N>(i)];
+            for (int i = lane_e + 64 * slot; i < M; i += 64 * K) p.prev_re[(size_t) c * M + i] = prev[bimg<N>(i)];
+    }
     if (chunk + 1 < p.num_chunks) {
         // hand the flux state to the next chunk's workgroup: every storing wave's stores done, the barrier, one lane's
         // agent-scope release, then the count (MI355X guide, producer form)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (live && slot == 0 && lane0 == 0 && !(p.debug_flags & 1u)) {
+        if (live && slot == 0 && lane_e == 0 && !(p.debug_flags & 1u)) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __hip_atomic_store(p.queue + 1 + c, (unsigned) (chunk + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -133,6 +133,9 @@ struct FrameParams {
     const unsigned char* blk_carry_in;
     unsigned char*       blk_carry_out;
     const ChannelSettings* chan;    // per-track settings, or null: hop-mode input of channel c is scaled by chan[c].gain instead of `gain` (channel_gain)
+    // The 1024-point batch form with both analysers (flux state by runs, fx_flux_runs.h): [C][waves_per_ch][N/2] floats, where a wavefront
+    // parks the re of its run's first frame until its predecessor's run is over.  Scratch: nothing in it outlives the launch.
+    float*       flux_park;
 };
 
 struct EpilogueParams {

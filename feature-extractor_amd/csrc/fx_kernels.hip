@@ -8,7 +8,8 @@
 //     barriers inside a frame, only wave-local LDS exchanges through one buffer per wave.
 //   * the only frame-to-frame dependency on this path, the spectral-flux state
 //     (previousBinMagnitudes, ref SpectralCharacteristics.h:203), is handed from the wave of frame
-//     t-1 to the wave of frame t through LDS with a turn counter.
+//     t-1 to the wave of frame t through LDS with a turn counter.  (The 1024-point batch form with both analysers gives every
+//     wave a contiguous run of frames and a flux image of its own instead, and hands the state over once per run: fx_flux_runs.h.)
 //   * FFTs follow the exact rounding DAG of the reference's FFT (JUCE 4.2 kiss-style radix-4/2
 //     decimation in time, table twiddles, no fused multiply-add), executed as three register-resident
 //     passes (radix 16/8/4 first pass on real input, then radix-16 / radix-4 passes) over a padded
@@ -167,7 +168,12 @@ template <int N> hipError_t launch_t(const FrameParams& p, int analysers, hipStr
             return hipErrorInvalidValue;
         }
     }
-    else if (analysers == 3) hipLaunchKernelGGL((fx_frame_kernel<N, true, true>), grid, block, lds, stream, p);
+    else if (analysers == 3) {
+        constexpr bool RUNS = flux_runs_form<N, true, true, false, false>();
+        if (RUNS && !p.flux_park) return hipErrorInvalidValue;     // (a missing scratch is an error, not a slower form)
+        // (that form's layout has no channel image; frame_kernel_lds_bytes, the planner's bound for every form of a size, is not less)
+        hipLaunchKernelGGL((fx_frame_kernel<N, true, true>), grid, block, FrameLds<N>::bytes(p.ch_per_wg, p.waves_per_ch, false, RUNS), stream, p);
+    }
     else if (analysers == 1) hipLaunchKernelGGL((fx_frame_kernel<N, true, false>), grid, block, lds, stream, p);
     else if (analysers == 2) hipLaunchKernelGGL((fx_frame_kernel<N, false, true>), grid, block, lds, stream, p);
     else return hipErrorInvalidValue;

@@ -106,6 +106,7 @@ fx_status plan_call(const fx_context* c, const void* d_in, int T, int sample_for
     fp.gain = c->gain;
     fp.chan = c->d_chan;
     fp.prev_re = c->d_prev;
+    fp.flux_park = c->d_flux_park;
     fp.tw = c->d_tw;
     fp.tw_image = c->d_tw + 2 * (size_t) c->N;
     fp.part = part;
@@ -316,6 +317,17 @@ bool blocks_feed_kernels(const fx_context* c)
            !(c->test_hooks & FX_HOOK_NO_BLOCK_FEED);
 }
 
+// Bytes of FrameParams::flux_park a call of T frames per channel may need: the 1024-point batch kernel with both analysers keeps the flux
+// state by runs (csrc/fx_flux_runs.h), and a wavefront parks its run's first frame there -- a row of N/2 floats per wavefront of every
+// channel, at most as many wavefronts as the call has frames.  0: no kernel of this call parks (whoever plans such a call grows
+// fx_context::d_flux_park to this first; plan_call() itself allocates nothing).
+size_t flux_park_need(const fx_context* c, int T)
+{
+    if (c->N != 1024 || (c->flags & (FX_SPECTRAL_ONLY | FX_HARMONIC_ONLY)) || T < 2 || uses_pairs(c, c->tuning.waves_per_frame)) return 0;
+    const int kcap = fxk::frame_kernel_max_waves(c->N);
+    return sizeof(float) * (size_t) c->C * (size_t) (T < kcap ? T : kcap) * (size_t) (c->N / 2);
+}
+
 // in_kind / out_kind: where the caller's samples and result buffers live (fx_push_samples hands over hops it has assembled in device
 // memory with results that may go to the host)
 fx_status fx_run(fx_context* c, const void* in, int T, int sample_format, int in_kind, int out_kind, int hop_mode,
@@ -338,6 +350,7 @@ fx_status fx_run(fx_context* c, const void* in, int T, int sample_format, int in
     const size_t raw_bytes = out_elems * sizeof(float);
     if ((st = fx_grow(&c->d_raw, &c->raw_cap, raw_bytes)) != FX_OK) return st;
     if ((st = fx_grow(&c->d_part, &c->part_cap, (size_t) c->C * T * sizeof(fxk::FramePart))) != FX_OK) return st;
+    if ((st = fx_grow(&c->d_flux_park, &c->flux_park_cap, flux_park_need(c, T))) != FX_OK) return st;
 
     const void* d_in = in;
     float* d_or = out_raw;

@@ -38,6 +38,7 @@ inline void begin_launches(fx_context* c) { if (c) c->num_launches = 0; }
 // fx_plan.cpp, where each is described
 bool uses_pairs(const fx_context* c, int waves_per_frame);
 bool blocks_feed_kernels(const fx_context* c);
+size_t flux_park_need(const fx_context* c, int T);
 fx_status plan_call(const fx_context* c, const void* d_in, int T, int sample_format, int hop_mode, float* d_or, float* d_os,
                     const BlockFeed* blocks, const fxk::DynParams* dyn, fxk::FramePart* part, float* raw, Route route, Plan* plan);
 void note_planned(fx_context* c, const Launch& l);

@@ -356,7 +356,9 @@ fx_status fx_stream_submit(fx_stream* s)
         const int par = c->cur;
         fill_dyn(c, sl.h_dyn);
         // a graph keeps the addresses it was captured with: a step captured before the per-track table existed is captured once more
-        if (sl.exec[par] && sl.captured[par].launch[0].fp.chan != c->d_chan) {
+        // (likewise the scratch of the batch kernel's flux runs, which follows the largest call the context has seen)
+        if ((st = fx_grow(&c->d_flux_park, &c->flux_park_cap, flux_park_need(c, s->hops))) != FX_OK) return st;
+        if (sl.exec[par] && (sl.captured[par].launch[0].fp.chan != c->d_chan || sl.captured[par].launch[0].fp.flux_park != c->d_flux_park)) {
             const hipGraphExec_t old = sl.exec[par];
             sl.exec[par] = nullptr;
             HIP_TRY(hipGraphExecDestroy(old));
