@@ -145,6 +145,8 @@ def _prototypes():
         ("fx_offline_get_previous_bins", [vp, dp, i], st), ("fx_offline_spectral_slope", [vp, vp, i, vp, i], st),
         ("fx_offline_auto_correlation", [vp, vp, i, vp, vp, i], st),
         ("fx_offline_frames", [vp, vp, i, i, i, vp, vp, i], st), ("fx_offline_analyse", [vp, vp, i, i, i, i, u, vp, vp, vp, vp, i], st),
+        ("fx_offline_analyse_files", [vp, vp, llp, i, i, i, ip, u, vp, vp, vp, vp, i], st),
+        ("fx_offline_set_nyquists", [vp, dp], st), ("fx_offline_get_nyquists", [vp, dp], st),
         ("fx_offline_feature_ranges", [vp, vp, i, i, vp, i], st), ("fx_offline_feature_distribution", [vp, vp, i, i, i, vp, i], st),
         ("fx_offline_smoothing", [vp, i], st), ("fx_offline_smooth_rows", [vp, vp, i, i, i, vp, i], st), ("fx_offline_get_smoothing", [vp, fp, fp], st),
         ("fx_pack_osc12", [fp, fp], None), ("fx_pack_osc10", [fp, fp], None), ("fx_osc_encode", [cp, fp, P(ctypes.c_ubyte), i], st),

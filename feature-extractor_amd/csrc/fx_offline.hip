@@ -11,6 +11,9 @@
 #include <new>
 #include <vector>
 
+#include <stdint.h>
+
+#include "fx_kernels.h"
 #include "fx_context.h"
 #include "fx_offline_frames.h"
 #include "fx_offline_object.h"
@@ -69,55 +72,27 @@ __device__ __forceinline__ float block_max(float v, float* s_wave /* [NT / 64] *
     return m;
 }
 
+// the zero-crossing count of a step and the log attack time of an envelope: stated once, for these kernels and the file kernels
+#include "fx_offline_steps.hip.h"
+
+struct PlainSamples {
+    const float* a;
+    __device__ __forceinline__ float operator()(long long i) const { return a[i]; }
+};
+
 // ---- ref AudioAnalysis.h:517-541 analyseNormalisedZeroCrosses: block = (channel, downsample step) ----
 __global__ void __launch_bounds__(NT) zero_crosses_kernel(const float* audio, int num_samples, int num_downsamples, float* out)
 {
-    __shared__ int s_cnt[NT / 64];
     const int c = blockIdx.x / num_downsamples, i = blockIdx.x % num_downsamples;
     const int step = num_samples / num_downsamples;                        // :521 (int division)
-    const float* a = audio + (size_t) c * num_samples + (size_t) i * step; // :528
-    int n = 0;
-    for (int s = threadIdx.x; s < step - 1; s += NT) {                     // :529
-        const float first = a[s], second = a[s + 1];
-        const float d = first - second;
-        if ((first > 0.0f && d > first) || (first < 0.0f && d < first)) n++;        // :534-535
-    }
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-        for (int w = 0; w < NT / 64; w++) total += s_cnt[w];
-        out[(size_t) c * num_downsamples + i] = (float) total * 2.0f / (float) step;       // :538 (a float count is exact below 2^24)
-    }
+    zero_crosses_block(PlainSamples{audio + (size_t) c * num_samples + (size_t) i * step}, step, out + (size_t) c * num_downsamples + i);      // :528
 }
 
 // ---- ref AudioAnalysis.h:611-622 setLogAttackTime: one block ----
 __global__ void __launch_bounds__(NT) log_attack_time_kernel(const float* env, int n, int num_input_samples, int num_downsamples, int sample_rate, float* out)
 {
-    __shared__ float s_max[NT];
-    __shared__ int s_idx[NT];
-    float m = -__builtin_huge_valf();
-    bool any = false;
-    // findMinMax(...).getEnd(), :615: the maximum starts from env[0] and moves on `>` only, so a NaN anywhere but at 0 is skipped -- here too, or one
-    // early in a thread's stride would hide the maxima behind it (as in auto_correlation_kernel below); a NaN at env[0] is thread 0's business
-    for (int k = threadIdx.x; k < n; k += NT) { const float v = env[k]; if (v == v && (!any || v > m)) { m = v; any = true; } }
-    s_max[threadIdx.x] = any ? m : -__builtin_huge_valf();                 // (-inf never moves the maximum)
-    __syncthreads();
-    if (threadIdx.x == 0) { float mm = env[0]; for (int k = 0; k < NT; k++) if (s_max[k] > mm) mm = s_max[k]; s_max[0] = mm; }      // a NaN at 0 stays: it equals no entry, i = n
-    __syncthreads();
-    const float max_energy = s_max[0];
-    int first = n;                                                         // first index holding the maximum, :616-618
-    for (int k = threadIdx.x; k < n; k += NT) if (env[k] == max_energy) { first = k; break; }
-    s_idx[threadIdx.x] = first;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int i = n;
-        for (int k = 0; k < NT; k++) if (s_idx[k] < i) i = s_idx[k];
-        const double ms_per_sample = 1.0 / (double) (sample_rate / 1000);  // :619 (sampleRate is an int: AudioFeatures.h:303)
-        const int samples_per_step = num_input_samples / num_downsamples;  // :620
-        out[0] = (float) log10((double) (float) (i * samples_per_step) * (float) ms_per_sample);   // :621
-    }
+    const int samples_per_step = num_input_samples / num_downsamples;      // :620
+    log_attack_block(env, n, samples_per_step, sample_rate, out);
 }
 
 // ---- ref AudioAnalysis.h:543-564 calculateFFTLBP: block = channel ----
@@ -168,7 +143,7 @@ __device__ __forceinline__ double harmonic_energy_ratio(const float* mag, int nu
     return score / total;
 }
 
-__global__ void __launch_bounds__(NT) harmonic_characteristics_kernel(const float* mags, int num_bins, double nyquist, double* prev_f0, float* out3)
+__global__ void __launch_bounds__(NT) harmonic_characteristics_kernel(const float* mags, int num_bins, const double* nyquists, double* prev_f0, float* out3)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* mag = reinterpret_cast<float*>(smem);                           // [num_bins]
@@ -181,6 +156,7 @@ __global__ void __launch_bounds__(NT) harmonic_characteristics_kernel(const floa
     __shared__ double s_w[NT / 64], s_fr[NT / 64], s_hr[NT / 64];
     __shared__ int s_k[NT / 64];
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double nyquist = nyquists[c];                                    // this channel's analyser's (fx_offline_set_nyquists)
     for (int i = tid; i < num_bins; i += NT) { mag[i] = mags[(size_t) c * num_bins + i]; cnt[i] = 0; key[i] = 0x7fffffff; }
     __syncthreads();
     if (tid == 0) {                                                        // :264-268: the reference's serial sum (its last bit decides `mag > mean`)
@@ -329,7 +305,7 @@ fx_status check_args(fx_offline* o, const void* in, const void* out, int mem_kin
 // loads ahead of its additions (serial_sum); "not added" became "+ 0.0" (the flux starts at +0.0 and only grows: x + 0.0 == x bit for bit).
 // LDS: a[bins] | b[bins] | m[bins], doubles = 24 bytes per bin (98 KB at 4097 bins).
 constexpr size_t SPECTRAL_LDS_PER_BIN = 3 * sizeof(double);
-__global__ void __launch_bounds__(NT) spectral_characteristics_kernel(const float* mags, int num_bins, double nyquist, double* prev_bins, float* out4)
+__global__ void __launch_bounds__(NT) spectral_characteristics_kernel(const float* mags, int num_bins, const double* nyquists, double* prev_bins, float* out4)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* ta = reinterpret_cast<double*>(smem);                           // per-bin terms, first pass: rectified difference (or 0); second: spread term
@@ -337,6 +313,7 @@ __global__ void __launch_bounds__(NT) spectral_characteristics_kernel(const floa
     double* tm = tb + num_bins;                                             // (double) mag
     __shared__ double s_chain[4];                                           // flux, sum, weighted, product
     const int c = blockIdx.x;
+    const double nyquist = nyquists[c];
     double* gprev = prev_bins + (size_t) c * num_bins;
     const size_t n = (size_t) num_bins;
     const double frpb = nyquist / n;                                        // :466
@@ -439,7 +416,7 @@ __global__ void __launch_bounds__(NT) conjugate_multiplication_kernel(float* dat
 }
 
 // ---- ref AudioAnalysis.h:636-665 analyseAutoCorrelation + getMaxIndex: block = channel; the FIRST bin holding the largest real part ----
-__global__ void __launch_bounds__(NT) auto_correlation_kernel(const float* data, int num_items, double nyquist, int* peak_bin, double* frequency)
+__global__ void __launch_bounds__(NT) auto_correlation_kernel(const float* data, int num_items, const double* nyquists, int* peak_bin, double* frequency)
 {
     __shared__ float s_val[NT / 64];
     __shared__ int s_idx[NT / 64];
@@ -461,7 +438,7 @@ __global__ void __launch_bounds__(NT) auto_correlation_kernel(const float* data,
         int peak = 0; float current = d[0];
         for (int k = 0; k < NT / 64; k++)
             if (s_idx[k] >= 0 && (s_val[k] > current || (s_val[k] == current && s_idx[k] < peak))) { current = s_val[k]; peak = s_idx[k]; }
-        const double frpb = nyquist / (double) num_items;
+        const double frpb = nyquists[c] / (double) num_items;
         peak_bin[c] = peak;
         frequency[c] = (peak * frpb) + (frpb / 2.0);
     }
@@ -486,7 +463,11 @@ fx_status fx_offline_create(fx_offline** out, int device_id, int num_channels, d
     fx_offline* o = new (std::nothrow) fx_offline();
     if (!o) return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
     o->device = device_id; o->C = num_channels; o->nyquist = nyquist;
+    o->h_nyquist.assign((size_t) num_channels, nyquist);
     hipError_t e = hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&o->staged, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void**) &o->d_nyquist, sizeof(double) * (size_t) num_channels);
+    if (e == hipSuccess) e = hipMemcpyAsync(o->d_nyquist, o->h_nyquist.data(), sizeof(double) * (size_t) num_channels, hipMemcpyHostToDevice, o->stream);
     if (e == hipSuccess) e = hipMalloc((void**) &o->d_prev_f0, sizeof(double) * (size_t) num_channels);
     if (e == hipSuccess) e = hipMemsetAsync(o->d_prev_f0, 0, sizeof(double) * (size_t) num_channels, o->stream);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&harmonic_characteristics_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -508,6 +489,9 @@ fx_status fx_offline_destroy(fx_offline* o)
     if (o->stream) (void) hipStreamSynchronize(o->stream);
     if (o->d_prev_f0) (void) hipFree(o->d_prev_f0);
     if (o->d_prev_bins) (void) hipFree(o->d_prev_bins);
+    if (o->d_nyquist) (void) hipFree(o->d_nyquist);
+    if (o->d_files) (void) hipFree(o->d_files);
+    if (o->staged) (void) hipEventDestroy(o->staged);
     if (o->d_in) (void) hipFree(o->d_in);
     if (o->d_out) (void) hipFree(o->d_out);
     for (float* t : o->d_table) if (t) (void) hipFree(t);
@@ -610,7 +594,7 @@ fx_status fx_offline_harmonic_characteristics(fx_offline* o, const float* magnit
     float* d_out = out3;
     if (mem_kind == FX_MEM_HOST) { if ((st = fx_grow(&o->d_out, &o->out_cap, out_bytes)) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
     hipLaunchKernelGGL(harmonic_characteristics_kernel, dim3((unsigned) o->C), dim3(NT), harmonic_lds_bytes(num_bins), o->stream,
-                       static_cast<const float*>(da), num_bins, o->nyquist, o->d_prev_f0, d_out);
+                       static_cast<const float*>(da), num_bins, o->d_nyquist, o->d_prev_f0, d_out);
     HIP_TRY(hipGetLastError());
     if (mem_kind == FX_MEM_HOST) { HIP_TRY(hipMemcpyAsync(out3, d_out, out_bytes, hipMemcpyDeviceToHost, o->stream)); HIP_TRY(hipStreamSynchronize(o->stream)); }
     return FX_OK;
@@ -635,7 +619,7 @@ fx_status fx_offline_spectral_characteristics(fx_offline* o, const float* magnit
     float* d_out = out4;
     if (mem_kind == FX_MEM_HOST) { if ((st = fx_grow(&o->d_out, &o->out_cap, out_bytes)) != FX_OK) return st; d_out = static_cast<float*>(o->d_out); }
     hipLaunchKernelGGL(spectral_characteristics_kernel, dim3((unsigned) o->C), dim3(NT), SPECTRAL_LDS_PER_BIN * (size_t) num_bins, o->stream,
-                       static_cast<const float*>(da), num_bins, o->nyquist, o->d_prev_bins, d_out);
+                       static_cast<const float*>(da), num_bins, o->d_nyquist, o->d_prev_bins, d_out);
     HIP_TRY(hipGetLastError());
     if (mem_kind == FX_MEM_HOST) { HIP_TRY(hipMemcpyAsync(out4, d_out, out_bytes, hipMemcpyDeviceToHost, o->stream)); HIP_TRY(hipStreamSynchronize(o->stream)); }
     return FX_OK;
@@ -685,7 +669,7 @@ fx_status fx_offline_auto_correlation(fx_offline* o, float* data, int num_items,
     const long long items = (long long) o->C * num_items;
     hipLaunchKernelGGL(conjugate_multiplication_kernel, dim3((unsigned) ((items + NT - 1) / NT)), dim3(NT), 0, o->stream, d_data, items);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(auto_correlation_kernel, dim3((unsigned) o->C), dim3(NT), 0, o->stream, d_data, num_items, o->nyquist, d_peak, d_freq);
+    hipLaunchKernelGGL(auto_correlation_kernel, dim3((unsigned) o->C), dim3(NT), 0, o->stream, d_data, num_items, o->d_nyquist, d_peak, d_freq);
     HIP_TRY(hipGetLastError());
     if (mem_kind == FX_MEM_HOST) {
         HIP_TRY(hipMemcpyAsync(data, d_data, in_bytes, hipMemcpyDeviceToHost, o->stream));
@@ -758,22 +742,34 @@ fx_status fx_offline_frames(fx_offline* o, const float* audio, int num_samples, 
     return FX_OK;
 }
 
-fx_status fx_offline_analyse(fx_offline* o, const float* audio, int num_samples, int num_downsamples, int window_size, int sample_rate, unsigned what,
-                             float* features, float* energy, float* log_attack_time, float* magnitudes, int mem_kind)
+namespace {
+
+// what both whole-analysis entries refuse about `what` and the object's state, in fx_offline_analyse's order: before the sample rate(s) ...
+fx_status check_what(unsigned what, const float* log_attack_time)
 {
-    const int S = num_samples, D = num_downsamples, N = window_size, B = N / 2 + 1;
-    fx_status st = check_frames_args(o, audio, features, S, D, N, mem_kind);
-    if (st != FX_OK) return st;
-    const bool spectral = what & FX_OFFLINE_DO_SPECTRAL, harmonic = what & FX_OFFLINE_DO_HARMONIC, log_attack = what & FX_OFFLINE_DO_LOG_ATTACK;
     if ((what & FX_OFFLINE_DO_NORMALISE_AUDIO) && !(what & FX_OFFLINE_DO_AUDIO))
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "what = %u: FX_OFFLINE_DO_NORMALISE_AUDIO needs FX_OFFLINE_DO_AUDIO", what);
-    if (log_attack && !log_attack_time) return fx_fail(FX_ERR_INVALID_ARGUMENT, "FX_OFFLINE_DO_LOG_ATTACK with a null log_attack_time");
-    if (log_attack && sample_rate < 1000)
-        return fx_fail(FX_ERR_INVALID_ARGUMENT, "sample_rate %d: need sample_rate >= 1000 (sampleRate / 1000 is an int division, ref AudioAnalysis.h:619)", sample_rate);
-    if (spectral && o->d_prev_bins && o->prev_bins != B)
+    if ((what & FX_OFFLINE_DO_LOG_ATTACK) && !log_attack_time) return fx_fail(FX_ERR_INVALID_ARGUMENT, "FX_OFFLINE_DO_LOG_ATTACK with a null log_attack_time");
+    return FX_OK;
+}
+// ... and after
+fx_status check_previous_bins(fx_offline* o, unsigned what, int B)
+{
+    if ((what & FX_OFFLINE_DO_SPECTRAL) && o->d_prev_bins && o->prev_bins != B)
         return fx_fail(FX_ERR_INVALID_ARGUMENT, "this analyser's previousBinMagnitudes holds %d bins (fixed by its window size, ref AudioAnalysis.h:120-121); "
                                                 "fx_offline_reset before frames of %d", o->prev_bins, B);
-    HIP_TRY(hipSetDevice(o->device));
+    return FX_OK;
+}
+
+// The whole analysis of fx_offline_analyse and fx_offline_analyse_files, after their refusals: the allocations, the chunks of frames with the
+// per-frame launches between them, the scatter, the rows over the audio, the copies back.  `in` is the caller's input of in_bytes bytes (host
+// or device, by mem_kind); src says what it is -- audio [C][S] or a bank with its records -- and src.samples is set here.
+fx_status run_analysis(fx_offline* o, const void* in, size_t in_bytes, fxo::Source src, int D, int N, unsigned what, float* features, float* energy,
+                       float* log_attack_time, float* magnitudes, int mem_kind)
+{
+    const int B = N / 2 + 1;
+    fx_status st;
+    const bool spectral = what & FX_OFFLINE_DO_SPECTRAL, harmonic = what & FX_OFFLINE_DO_HARMONIC, log_attack = what & FX_OFFLINE_DO_LOG_ATTACK;
     const size_t C = (size_t) o->C, rows = C * D;
     const bool need_energy = energy || log_attack, need_frames = spectral || harmonic || need_energy || magnitudes;
     const size_t feat_floats = (size_t) FX_OFFLINE_FEATURE_ROWS * rows, mag_floats = magnitudes ? (size_t) D * C * B : 0;
@@ -782,8 +778,9 @@ fx_status fx_offline_analyse(fx_offline* o, const float* audio, int num_samples,
     const float* table = nullptr;
     if (need_frames && (st = forward_table_of(o, N, &table)) != FX_OK) return st;
     const void *da, *db;
-    if ((st = stage_in(o, mem_kind, audio, sizeof(float) * C * S, nullptr, 0, &da, &db)) != FX_OK) return st;
-    const float* d_audio = static_cast<const float*>(da);
+    if ((st = stage_in(o, mem_kind, in, in_bytes, nullptr, 0, &da, &db)) != FX_OK) return st;
+    src.samples = da;
+    const float* d_audio = static_cast<const float*>(da);                   // (audio [C][S]: as the launches below take it)
     float* d_feat = features; float* d_env = energy; float* d_lat = log_attack_time; float* d_mags = magnitudes;
     if (mem_kind == FX_MEM_HOST) {                                          // features | energy | log attack time | magnitudes
         if ((st = fx_grow(&o->d_out, &o->out_cap, sizeof(float) * (feat_floats + rows + C + mag_floats))) != FX_OK) return st;
@@ -815,32 +812,42 @@ fx_status fx_offline_analyse(fx_offline* o, const float* audio, int num_samples,
     for (int f0 = 0; need_frames && f0 < D; f0 += chunk) {
         const int frames = D - f0 < chunk ? D - f0 : chunk;
         float* block = d_mags ? d_mags + (size_t) f0 * C * B : static_cast<float*>(o->d_scratch);
-        if ((st = fxo::launch_frames(o->stream, d_audio, o->C, S, D, N, f0, frames, table, block, need_energy ? d_env : nullptr)) != FX_OK) return st;
+        float* env = need_energy ? d_env : nullptr;
+        st = src.files ? fxo::launch_frames_files(o->stream, src.samples, src.files, src.format, o->C, D, N, f0, frames, table, block, env)
+                       : fxo::launch_frames(o->stream, d_audio, o->C, src.S, D, N, f0, frames, table, block, env);
+        if (st != FX_OK) return st;
         for (int f = f0; f < f0 + frames && (spectral || harmonic); f++) {  // the order of ref AudioAnalysis.h:229-246
             const float* m = block + (size_t) (f - f0) * C * B;
             if (spectral) {
                 hipLaunchKernelGGL(spectral_characteristics_kernel, dim3((unsigned) o->C), dim3(NT), SPECTRAL_LDS_PER_BIN * (size_t) B, o->stream,
-                                   m, B, o->nyquist, o->d_prev_bins, d_out4 + 4 * C * f);
+                                   m, B, o->d_nyquist, o->d_prev_bins, d_out4 + 4 * C * f);
                 hipLaunchKernelGGL(spectral_slope_kernel, dim3((unsigned) o->C), dim3(NT), SLOPE_LDS_PER_BIN * (size_t) B, o->stream, m, B, d_slope + C * f);
             }
             if (harmonic)
                 hipLaunchKernelGGL(harmonic_characteristics_kernel, dim3((unsigned) o->C), dim3(NT), harmonic_lds_bytes(B), o->stream,
-                                   m, B, o->nyquist, o->d_prev_f0, d_out3 + 3 * C * f);
+                                   m, B, o->d_nyquist, o->d_prev_f0, d_out3 + 3 * C * f);
         }
         HIP_TRY(hipGetLastError());
     }
     if (spectral || harmonic)
         if ((st = fxo::launch_scatter_rows(o->stream, spectral ? d_out4 : nullptr, spectral ? d_slope : nullptr, harmonic ? d_out3 : nullptr, o->C, D, d_feat)) != FX_OK) return st;
     if (what & FX_OFFLINE_DO_ZERO_CROSSES) {
-        hipLaunchKernelGGL(zero_crosses_kernel, dim3((unsigned) (o->C * D)), dim3(NT), 0, o->stream, d_audio, S, D, d_feat + (size_t) FX_OFFLINE_ZERO_CROSSES * rows);
+        float* row = d_feat + (size_t) FX_OFFLINE_ZERO_CROSSES * rows;
+        if (src.files) { if ((st = fxo::launch_zero_crosses_files(o->stream, src.samples, src.files, src.format, o->C, D, row)) != FX_OK) return st; }
+        else hipLaunchKernelGGL(zero_crosses_kernel, dim3((unsigned) (o->C * D)), dim3(NT), 0, o->stream, d_audio, src.S, D, row);
         HIP_TRY(hipGetLastError());
     }
     if (what & FX_OFFLINE_DO_AUDIO) {
         float* row = d_feat + (size_t) FX_OFFLINE_AUDIO * rows;
-        if ((st = fxo::launch_rms_row(o->stream, d_audio, o->C, S, D, row)) != FX_OK) return st;
+        st = src.files ? fxo::launch_rms_row_files(o->stream, src.samples, src.files, src.format, o->C, D, row) : fxo::launch_rms_row(o->stream, d_audio, o->C, src.S, D, row);
+        if (st != FX_OK) return st;
         if ((what & FX_OFFLINE_DO_NORMALISE_AUDIO) && (st = fxo::launch_normalise_row(o->stream, row, o->C, D)) != FX_OK) return st;
     }
-    if (log_attack && (st = fxo::launch_log_attack_times(o->stream, d_env, o->C, D, S, sample_rate, d_lat)) != FX_OK) return st;
+    if (log_attack) {
+        st = src.files ? fxo::launch_log_attack_times_files(o->stream, d_env, src.files, o->C, D, d_lat)
+                       : fxo::launch_log_attack_times(o->stream, d_env, o->C, D, src.S, src.sample_rate, d_lat);
+        if (st != FX_OK) return st;
+    }
     if (mem_kind == FX_MEM_HOST) {
         HIP_TRY(hipMemcpyAsync(features, d_feat, sizeof(float) * feat_floats, hipMemcpyDeviceToHost, o->stream));
         if (energy) HIP_TRY(hipMemcpyAsync(energy, d_env, sizeof(float) * rows, hipMemcpyDeviceToHost, o->stream));
@@ -848,6 +855,97 @@ fx_status fx_offline_analyse(fx_offline* o, const float* audio, int num_samples,
         if (magnitudes) HIP_TRY(hipMemcpyAsync(magnitudes, d_mags, sizeof(float) * mag_floats, hipMemcpyDeviceToHost, o->stream));
         HIP_TRY(hipStreamSynchronize(o->stream));
     }
+    return FX_OK;
+}
+
+// A per-channel table goes from its host copy in the object to the device on the object's stream.  The call may return while that copy is
+// queued (a FX_MEM_DEVICE call does not wait), so the host copy stays in the object and is rewritten only behind this wait for the last copy
+// out of it -- never under a copy in flight.
+fx_status wait_staged(fx_offline* o) { HIP_TRY(hipEventSynchronize(o->staged)); return FX_OK; }
+fx_status stage_table(fx_offline* o, void* device, const void* host, size_t bytes)
+{
+    HIP_TRY(hipMemcpyAsync(device, host, bytes, hipMemcpyHostToDevice, o->stream));
+    HIP_TRY(hipEventRecord(o->staged, o->stream));
+    return FX_OK;
+}
+
+} // namespace
+
+fx_status fx_offline_analyse(fx_offline* o, const float* audio, int num_samples, int num_downsamples, int window_size, int sample_rate, unsigned what,
+                             float* features, float* energy, float* log_attack_time, float* magnitudes, int mem_kind)
+{
+    const int S = num_samples, D = num_downsamples, N = window_size;
+    fx_status st = check_frames_args(o, audio, features, S, D, N, mem_kind);
+    if (st != FX_OK) return st;
+    if ((st = check_what(what, log_attack_time)) != FX_OK) return st;
+    if ((what & FX_OFFLINE_DO_LOG_ATTACK) && sample_rate < 1000)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "sample_rate %d: need sample_rate >= 1000 (sampleRate / 1000 is an int division, ref AudioAnalysis.h:619)", sample_rate);
+    if ((st = check_previous_bins(o, what, N / 2 + 1)) != FX_OK) return st;
+    HIP_TRY(hipSetDevice(o->device));
+    return run_analysis(o, audio, sizeof(float) * (size_t) o->C * S, fxo::Source{nullptr, S, sample_rate, nullptr, FX_SAMPLE_F32}, D, N, what,
+                        features, energy, log_attack_time, magnitudes, mem_kind);
+}
+
+fx_status fx_offline_analyse_files(fx_offline* o, const void* samples, const long long* lengths, int sample_format, int num_downsamples, int window_size,
+                                   const int* sample_rates, unsigned what, float* features, float* energy, float* log_attack_time, float* magnitudes,
+                                   int mem_kind)
+{
+    const int D = num_downsamples, N = window_size;
+    if (!o || !samples || !features || !lengths) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null argument");
+    if (D < 1) return fx_fail(FX_ERR_INVALID_ARGUMENT, "num_downsamples %d: need at least 1", D);
+    if (!fxo::known_window(N)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "window_size %d is not one of 256, 512, 1024, 2048, 4096", N);
+    if (sample_format != FX_SAMPLE_F32 && sample_format != FX_SAMPLE_F16 && sample_format != FX_SAMPLE_S16 && sample_format != FX_SAMPLE_S24)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown sample format %d", sample_format);
+    if (mem_kind != FX_MEM_HOST && mem_kind != FX_MEM_DEVICE) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown memory kind %d", mem_kind);
+    if (mem_kind == FX_MEM_DEVICE && (reinterpret_cast<uintptr_t>(samples) & 3))
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "a device bank starts at a 4-byte boundary, not at %p", samples);
+    for (int c = 0; c < o->C; c++) {
+        const long long S = lengths[c];
+        if (S < 1 || S > 2147483647LL) return fx_fail(FX_ERR_INVALID_ARGUMENT, "file %d: num_samples %lld: need 1 .. 2^31 - 1", c, S);
+        if (D > S) return fx_fail(FX_ERR_INVALID_ARGUMENT, "file %d: num_downsamples %d > num_samples %lld (stepSize > 0, ref AudioAnalysis.h:139)", c, D, S);
+        if (D == 1 && N > S)
+            return fx_fail(FX_ERR_INVALID_ARGUMENT, "file %d: one frame of window_size %d needs as many samples, not %lld (ref AudioAnalysis.h:157)", c, N, S);
+    }
+    fx_status st = check_what(what, log_attack_time);
+    if (st != FX_OK) return st;
+    const bool log_attack = what & FX_OFFLINE_DO_LOG_ATTACK;
+    if (log_attack && !sample_rates) return fx_fail(FX_ERR_INVALID_ARGUMENT, "FX_OFFLINE_DO_LOG_ATTACK with null sample_rates");
+    for (int c = 0; log_attack && c < o->C; c++)
+        if (sample_rates[c] < 1000)
+            return fx_fail(FX_ERR_INVALID_ARGUMENT, "file %d: sample_rate %d: need sample_rate >= 1000 (sampleRate / 1000 is an int division, ref AudioAnalysis.h:619)",
+                           c, sample_rates[c]);
+    if ((st = check_previous_bins(o, what, N / 2 + 1)) != FX_OK) return st;
+    HIP_TRY(hipSetDevice(o->device));
+    if (!o->d_files) HIP_TRY(hipMalloc((void**) &o->d_files, sizeof(fxo::FileRecord) * (size_t) o->C));
+    if ((st = wait_staged(o)) != FX_OK) return st;
+    o->h_files.resize((size_t) o->C);
+    long long first = 0;                                                    // offsets in 64 bits
+    for (int c = 0; c < o->C; c++) {
+        const int S = (int) lengths[c];
+        o->h_files[c] = fxo::FileRecord{first, S, S / D, log_attack ? sample_rates[c] : 0, 0};      // step: ref AudioAnalysis.h:135 (int division)
+        first += S;
+    }
+    if ((st = stage_table(o, o->d_files, o->h_files.data(), sizeof(fxo::FileRecord) * (size_t) o->C)) != FX_OK) return st;
+    return run_analysis(o, samples, (size_t) first * (size_t) fxk::sample_bytes(sample_format), fxo::Source{nullptr, 0, 0, o->d_files, sample_format}, D, N, what,
+                        features, energy, log_attack_time, magnitudes, mem_kind);
+}
+
+fx_status fx_offline_set_nyquists(fx_offline* o, const double* nyquist)
+{
+    if (!o || !nyquist) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null argument");
+    for (int c = 0; c < o->C; c++)
+        if (!(nyquist[c] > 0.0)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "channel %d: nyquist %g must be positive", c, nyquist[c]);
+    HIP_TRY(hipSetDevice(o->device));
+    fx_status st = wait_staged(o);
+    if (st != FX_OK) return st;
+    o->h_nyquist.assign(nyquist, nyquist + o->C);
+    return stage_table(o, o->d_nyquist, o->h_nyquist.data(), sizeof(double) * (size_t) o->C);       // in stream order: frames already enqueued keep the old values
+}
+
+fx_status fx_offline_get_nyquists(fx_offline* o, double* out)
+{
+    if (!o || !out) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null argument");
+    for (int c = 0; c < o->C; c++) out[c] = o->h_nyquist[c];                // the values last set (or the creation value): what frames enqueued from now on read
     return FX_OK;
 }
 

@@ -29,4 +29,28 @@ fx_status launch_log_attack_times(hipStream_t stream, const float* energy, int C
 // of features [10][C][D] (ref AudioFeatures.h:133-140 setFeatureSample)
 fx_status launch_scatter_rows(hipStream_t stream, const float* out4, const float* slope, const float* out3, int C, int D, float* features);
 
+// ---- a bank of files (fx_offline_analyse_files): C files back to back in one FX_SAMPLE_* format, each with a record the host forms -- the
+// device never divides by D.  Defined in fx_offline_files.hip; the arithmetic is the kernels' above (fx_offline_frame_body.hip.h,
+// fx_offline_steps.hip.h), read through fx_samples.hip.h's widening with S_c, step_c and the file's rate in place of S, S div D and sample_rate.
+struct FileRecord {
+    long long first;        // index of the file's first sample in the bank
+    int S;                  // its number of samples
+    int step;               // S div D: the frames' step, the Audio row's spb, the attack time's samples_per_step
+    int rate;               // its sample rate (0 unless the log attack time is asked for)
+    int pad;
+};
+fx_status launch_frames_files(hipStream_t stream, const void* bank, const FileRecord* files, int format, int C, int D, int n, int first_frame,
+                              int num_frames, const float* table, float* mags, float* energy);
+fx_status launch_zero_crosses_files(hipStream_t stream, const void* bank, const FileRecord* files, int format, int C, int D, float* row);
+fx_status launch_rms_row_files(hipStream_t stream, const void* bank, const FileRecord* files, int format, int C, int D, float* row);
+fx_status launch_log_attack_times_files(hipStream_t stream, const float* energy, const FileRecord* files, int C, int D, float* out);
+
+// what the driver analyses: audio [C][S] fp32 of one length and rate (files == null), or a bank of files
+struct Source {
+    const void* samples;            // device memory
+    int S, sample_rate;             // audio [C][S]
+    const FileRecord* files;        // [C], device memory
+    int format;
+};
+
 } // namespace fxo

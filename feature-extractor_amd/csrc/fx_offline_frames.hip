@@ -27,61 +27,35 @@ constexpr int NT = 256;
 // the plan, the complex helpers and plain_transform: the one statement of the reference FFT's DAG
 #include "fx_plain_fft.hip.h"
 
+#include "fx_offline_frame_body.hip.h"
+#include "fx_offline_steps.hip.h"
+
+struct PlainSamples {                                                       // a channel of audio [C][S]
+    const float* a;
+    __device__ __forceinline__ float operator()(long long i) const { return a[i]; }
+};
+
 // block = (frame, channel): blockIdx.x = (f - first_frame) * C + c
 template <int N>
 __global__ void __launch_bounds__(NT) offline_frames_kernel(const float* __restrict__ audio, int C, int S, int D, int first_frame,
                                                             const float* __restrict__ tw, float* __restrict__ mags, float* __restrict__ energy)
 {
     constexpr int H = N / 2, B = N / 2 + 1;
-    __shared__ cpx buf[N];
-    __shared__ float mag[B];
-    using P = PlainPlan<N>;
-    const int tid = threadIdx.x;
     const int fl = blockIdx.x / C, c = blockIdx.x - fl * C, f = first_frame + fl;
     const int step = S / D;                                                 // :135 (int division)
     // :150-161: the window is centred on the downsample -- unless there is one frame only, which starts at sample 0
     const long long start = D == 1 ? 0 : (long long) f * step - H;
-    const float* a = audio + (size_t) c * S;
-    for (int j = tid; j < N; j += NT) {
-        const long long i = start + j;                                      // :167
-        const float v = (i >= 0 && i < S) ? a[i] : 0.0f;                    // :169-177: zero padding for the ends
-        // scaleBufferWithBartlettWindowing (:667-676): two gain ramps, each gain the float sum of the increments 1 / H before it -- exact
-        const float w = j < H ? (float) j * (2.0f / N) : 2.0f - (float) j * (2.0f / N);
-        buf[P::position(j)] = cpx{v * w, 0.0f};                             // (always multiplied: inf * 0 = NaN, as applyGainRamp makes it)
-    }
-    __syncthreads();
-    plain_transform<N, false, NT>(buf, tw);
-    // performFrequencyOnlyForwardTransform, as tools/refdiff/juce_standin.h states it: sqrt (re * re + im * im) in float, bins 0 .. N / 2
-    float* out = mags + ((size_t) fl * C + c) * B;
-    for (int b = tid; b < B; b += NT) {
-        const cpx x = buf[b];
-        const float m = sqrtf(x.r * x.r + x.i * x.i);
-        mag[b] = m;
-        out[b] = m;
-    }
-    if (!energy) return;
-    __syncthreads();
-    if (tid == 0) {                                                         // sumAccrossChannels (:705-716) of one channel: serial, in float
-        float e = 0.0f;
-#pragma unroll 8
-        for (int b = 0; b < B; b++) e += mag[b];
-        energy[(size_t) c * D + f] = e;                                     // :249
-    }
+    frame_body<N>(PlainSamples{audio + (size_t) c * S}, S, start, tw, mags + ((size_t) fl * C + c) * B, energy ? energy + (size_t) c * D + f : nullptr);
 }
 
-// ---- ref AudioFeatures.h:158-184 fillDownsampledRMSAudioChannels: lane = (channel, downsample), walking its step serially (getRMSLevel: float
-// squares, double sum in sample order, sqrt of the double mean) ----
+// ---- ref AudioFeatures.h:158-184 fillDownsampledRMSAudioChannels: lane = (channel, downsample), walking its step serially ----
 __global__ void __launch_bounds__(NT) rms_row_kernel(const float* __restrict__ audio, int C, int S, int D, float* __restrict__ row)
 {
     const long long t = (long long) blockIdx.x * NT + threadIdx.x;
     if (t >= (long long) C * D) return;
     const int c = (int) (t / D), i = (int) (t - (long long) c * D);
     const int spb = S / D;                                                  // :161
-    const float* a = audio + (size_t) c * S + (size_t) i * spb;
-    if (spb == 1) { row[t] = a[0]; return; }                                // :165-172: the first D samples as they are
-    double sum = 0.0;
-    for (int s = 0; s < spb; s++) { const float x = a[s]; sum += (double) (x * x); }
-    row[t] = (float) sqrt(sum / (double) spb);
+    row[t] = rms_of_step(PlainSamples{audio + (size_t) c * S + (size_t) i * spb}, spb);
 }
 
 // ---- ref AudioFeatures.h:186-195 normaliseAudioChannels, one channel's row per block.  findMinMax starts both ends from row[0] and moves on
@@ -107,33 +81,12 @@ __global__ void __launch_bounds__(NT) normalise_row_kernel(float* row, int D)
     for (int i = threadIdx.x; i < D; i += NT) r[i] = r[i] * scale;          // :194
 }
 
-// ---- ref AudioAnalysis.h:611-622 setLogAttackTime, block = channel: fx_offline.hip's log_attack_time_kernel over the rows of energy [C][n] ----
+// ---- ref AudioAnalysis.h:611-622 setLogAttackTime, block = channel, over the rows of energy [C][n] ----
 __global__ void __launch_bounds__(NT) log_attack_times_kernel(const float* __restrict__ energy, int n, int num_input_samples, int num_downsamples,
                                                               int sample_rate, float* __restrict__ out)
 {
-    __shared__ float s_max[NT];
-    __shared__ int s_idx[NT];
-    const float* env = energy + (size_t) blockIdx.x * n;
-    float m = -__builtin_huge_valf();
-    bool any = false;
-    // findMinMax (...).getEnd(), :615: the maximum starts from env[0] and moves on `>` only, so a NaN anywhere but at 0 is skipped
-    for (int k = threadIdx.x; k < n; k += NT) { const float v = env[k]; if (v == v && (!any || v > m)) { m = v; any = true; } }
-    s_max[threadIdx.x] = any ? m : -__builtin_huge_valf();
-    __syncthreads();
-    if (threadIdx.x == 0) { float mm = env[0]; for (int k = 0; k < NT; k++) if (s_max[k] > mm) mm = s_max[k]; s_max[0] = mm; }      // a NaN at 0 stays: it equals no entry, i = n
-    __syncthreads();
-    const float max_energy = s_max[0];
-    int first = n;                                                          // first index holding the maximum, :616-618
-    for (int k = threadIdx.x; k < n; k += NT) if (env[k] == max_energy) { first = k; break; }
-    s_idx[threadIdx.x] = first;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int i = n;
-        for (int k = 0; k < NT; k++) if (s_idx[k] < i) i = s_idx[k];
-        const double ms_per_sample = 1.0 / (double) (sample_rate / 1000);   // :619 (sampleRate is an int: AudioFeatures.h:303)
-        const int samples_per_step = num_input_samples / num_downsamples;   // :620
-        out[blockIdx.x] = (float) log10((double) (float) (i * samples_per_step) * (float) ms_per_sample);   // :621
-    }
+    const int samples_per_step = num_input_samples / num_downsamples;       // :620
+    log_attack_block(energy + (size_t) blockIdx.x * n, n, samples_per_step, sample_rate, out + blockIdx.x);
 }
 
 // ---- ref AudioFeatures.h:133-140 setFeatureSample, for the per-frame results of a whole call: thread = (frame, channel) ----

@@ -161,6 +161,77 @@ class AudioAnalyser:
         features, energy, lat, mags = self._finish(kind, features, energy, lat, mags)
         return ConcatenatedFeatureBuffer(features, energy, lat, mags, D, int(sample_rate), analyser=self)
 
+    # ---- a library of files of different lengths in one call (fx_offline_analyse_files) ----
+    _FORMAT_OF = {"float32": capi.SAMPLE_F32, "float16": capi.SAMPLE_F16, "int16": capi.SAMPLE_S16, "uint8": capi.SAMPLE_S24}
+
+    def _format(self, dtype_name, sample_format):
+        """the FX_SAMPLE_* of a dtype, or None: sample_format, when given, must name it, and bytes are samples only when it says so"""
+        fmt = self._FORMAT_OF.get(dtype_name)
+        if (sample_format is None and fmt == capi.SAMPLE_S24) or (sample_format is not None and int(sample_format) != fmt):
+            return None
+        return fmt
+
+    def _bank(self, files, sample_format):
+        """files: a list of 1-D numpy arrays of one dtype (float32, float16, int16, or uint8 bytes with sample_format=SAMPLE_S24), or a pair
+        (flat CUDA tensor, lengths) -> (what to keep alive, address, lengths [C] int64, sample format, memory kind, an allocator)"""
+        if isinstance(files, tuple) and len(files) == 2 and _is_device_tensor(files[0]):
+            import torch
+            bank, lengths = files
+            fmt = self._format(str(bank.dtype).split(".")[-1], sample_format)
+            if fmt is None or bank.dim() != 1:
+                raise ValueError("expected a flat float32 / float16 / int16 tensor, or uint8 bytes with sample_format=SAMPLE_S24")
+            bank = bank.contiguous()
+            lengths = np.ascontiguousarray(lengths, np.int64)
+            if lengths.shape != (self.num_channels,) or int(lengths.sum()) * (3 if fmt == capi.SAMPLE_S24 else 1) != bank.numel():
+                raise ValueError("expected %d lengths that add up to the bank" % self.num_channels)
+            torch.cuda.current_stream(bank.device).synchronize()         # the library reads it on a stream of its own
+            return bank, bank.data_ptr(), lengths, fmt, capi.MEM_DEVICE, lambda *shape: torch.empty(shape, dtype=torch.float32, device=bank.device)
+        files = [np.ascontiguousarray(f) for f in files]
+        if len(files) != self.num_channels or any(f.ndim != 1 or f.dtype != files[0].dtype for f in files):
+            raise ValueError("expected %d one-dimensional arrays of one dtype" % self.num_channels)
+        fmt = self._format(files[0].dtype.name, sample_format)
+        if fmt is None or (fmt == capi.SAMPLE_S24 and any(f.size % 3 for f in files)):
+            raise ValueError("expected float32 / float16 / int16 arrays, or uint8 bytes (three a sample) with sample_format=SAMPLE_S24")
+        lengths = np.array([f.size // (3 if fmt == capi.SAMPLE_S24 else 1) for f in files], np.int64)
+        bank = np.concatenate(files) if files else np.empty(0, np.float32)
+        return bank, bank.ctypes.data, lengths, fmt, capi.MEM_HOST, lambda *shape: np.empty(shape, np.float32)
+
+    def perform_spectral_analysis_files(self, files, num_downsamples, window_size, sample_rates, spectral=True, harmonic=True, zero_crosses=True,
+                                        audio_rms=True, normalise=True, log_attack=True, keep_fft=False, sample_format=None):
+        """perform_spectral_analysis of C files of different lengths (and rates) in one call: every channel's results are what that file alone
+        gives.  sample_rates: one int or C ints; each analyser's nyquist is set_nyquists' business -- nothing is resampled.
+        -> ConcatenatedFeatureBuffer with num_samples [C] and sample_rate [C]."""
+        keep, address, lengths, fmt, kind, new = self._bank(files, sample_format)
+        D, N, C = int(num_downsamples), int(window_size), self.num_channels
+        if D < 1 or N not in capi.OFFLINE_WINDOWS:
+            raise capi.FxError(capi.FX_ERR_INVALID_ARGUMENT, "num_downsamples %d, window_size %d" % (D, N))
+        rates = np.ascontiguousarray(np.broadcast_to(np.asarray(sample_rates, np.int32), (C,)))
+        what = ((capi.OFFLINE_DO_SPECTRAL if spectral else 0) | (capi.OFFLINE_DO_HARMONIC if harmonic else 0)
+                | (capi.OFFLINE_DO_ZERO_CROSSES if zero_crosses else 0) | (capi.OFFLINE_DO_AUDIO if audio_rms else 0)
+                | (capi.OFFLINE_DO_NORMALISE_AUDIO if normalise else 0) | (capi.OFFLINE_DO_LOG_ATTACK if log_attack else 0))
+        features, energy = new(capi.OFFLINE_FEATURE_ROWS, C, D), new(C, D)
+        lat = new(C) if log_attack else None
+        mags = new(D, C, N // 2 + 1) if keep_fft else None
+        capi.check(self._lib.fx_offline_analyse_files(self._h, address, lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), fmt, D, N,
+                                                      rates.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), what, _address(features), _address(energy),
+                                                      _address(lat), _address(mags), kind))
+        if spectral:
+            self._bins = N // 2 + 1
+        features, energy, lat, mags = self._finish(kind, features, energy, lat, mags)
+        return ConcatenatedFeatureBuffer(features, energy, lat, mags, D, rates.copy(), analyser=self, num_samples=lengths)
+
+    def set_nyquists(self, values):                                                          # ref AudioAnalysis.h:107, one per channel's analyser
+        values = np.ascontiguousarray(values, np.float64)
+        if values.shape != (self.num_channels,):
+            raise ValueError("expected %d values" % self.num_channels)
+        capi.check(self._lib.fx_offline_set_nyquists(self._h, values.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+
+    @property
+    def nyquists(self):
+        out = np.empty(self.num_channels, np.float64)
+        capi.check(self._lib.fx_offline_get_nyquists(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return out
+
     # ---- what the reference derives from a feature buffer (fx_offline_feature_ranges / _distribution / _smooth_rows) ----
     def _feature_rows(self, rows, least=1):
         """rows [R][C][D] (numpy: through host memory; a CUDA torch tensor: used where it lies) -> (the array or tensor to keep alive, its
@@ -231,14 +302,16 @@ class ConcatenatedFeatureBuffer:
     """The results of AudioAnalyser.perform_spectral_analysis under the reference's names (ref AudioFeatures.h:14-314), on the host.
     `feature` arguments are the FX_OFFLINE_* row numbers (capi.OFFLINE_CENTROID .. capi.OFFLINE_AUDIO)."""
 
-    def __init__(self, feature_buffer, energy_envelope, estimated_log_attack_time, magnitudes, num_downsamples, sample_rate, analyser=None):
+    def __init__(self, feature_buffer, energy_envelope, estimated_log_attack_time, magnitudes, num_downsamples, sample_rate, analyser=None, num_samples=None):
         self._analyser = analyser                                       # the AudioAnalyser whose GPU derives ranges and distributions
         self.feature_buffer = feature_buffer                            # [10][C][D]: featureBuffer, less its FFT part
         self.energy_envelope = energy_envelope                          # [C][D]
         self.estimated_log_attack_time = estimated_log_attack_time      # [C], or None if not analysed
         self.magnitudes = magnitudes                                    # [D][C][bins], or None unless keep_fft
         self.num_downsamples = int(num_downsamples)
-        self.sample_rate = int(sample_rate)                             # (an int: ref :301)
+        # (an int: ref :301) -- or, from perform_spectral_analysis_files, one int per file [C], beside each file's own number of samples [C]
+        self.sample_rate = int(sample_rate) if np.ndim(sample_rate) == 0 else np.asarray(sample_rate, np.int32)
+        self.num_samples = None if num_samples is None else np.asarray(num_samples, np.int64)
         self.num_feature_channels = feature_buffer.shape[1]
 
     def get_feature_buffer(self, feature):                                                  # ref :242-254

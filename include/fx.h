@@ -872,6 +872,38 @@ fx_status fx_offline_analyse(fx_offline* o, const float* audio, int num_samples,
                              unsigned what, float* features /* [10][C][D] */, float* energy /* [C][D] or NULL */,
                              float* log_attack_time /* [C] or NULL */, float* magnitudes /* [D][C][N/2+1] or NULL */, int mem_kind);
 
+/* A LIBRARY of files in one call: C = num_channels files of DIFFERENT lengths (and sample rates), as the reference gives every file its own
+ * ConcatenatedFeatureBuffer with its own number of samples, step and rate.  samples is a bank exactly as fx_create_clips takes it: the files
+ * back to back, file c being S_c = lengths[c] samples of sample_format (FX_SAMPLE_F32 / F16 / S16 / packed S24) starting at sample index
+ * sum (lengths[0 .. c)), formed in 64 bits.  mem_kind covers samples and the results; a host bank is staged in its wire format and widened by
+ * the kernels.  A device bank starts at a 4-byte boundary; the files inside it start wherever they fall (any 2-byte boundary for the 16-bit
+ * formats, any byte for S24), and no load touches a byte outside the bank.  lengths and sample_rates are host memory, read before the call
+ * returns; sample_rates is needed only with DO_LOG_ATTACK.
+ * With a_c[i] the widening (csrc/fx_samples.hip.h: the one statement of it) of sample i of file c, every output of channel c is what
+ * fx_offline_analyse specifies for that channel with S_c in place of S wherever S occurs -- the frame indexing and zero padding, step, the
+ * D == 1 form, spb of the Audio row, the zero crossings, num_input_samples of the log attack time -- and sample_rates[c] in place of
+ * sample_rate.  The same as there: the frame order, the state carried in and out, the chunking through the object's scratch, "rows not asked
+ * for are +0", the output layouts ([10][C][D], [C][D], [C], [D][C][B]: one num_downsamples for every file).  what == 0 with magnitudes != NULL
+ * is the frame stage alone.  Each analyser's nyquist is the object's (fx_offline_set_nyquists below): a library with files at different rates
+ * sets them and passes sample_rates; nothing is resampled.
+ * Refused (FX_ERR_INVALID_ARGUMENT; fx_last_error names the value and, where there is one, the file; before any launch, copy or state
+ * change): what fx_offline_analyse refuses that still applies; a null lengths; lengths[c] < 1 or > 2^31 - 1; num_downsamples > S_c for some c
+ * (that file's step would be 0); num_downsamples == 1 with window_size > S_c; an unknown sample_format; a device bank off a 4-byte boundary;
+ * DO_LOG_ATTACK with null sample_rates or a rate below 1000.
+ * Not tested on a device: a bank of more than 2^31 samples (the offsets are 64-bit throughout; a bank that large is not analysed in the
+ * seconds a test has) -- as for the clips' 64-bit sample counter above. */
+fx_status fx_offline_analyse_files(fx_offline* o, const void* samples, const long long* lengths /* [C], host */, int sample_format,
+                                   int num_downsamples, int window_size, const int* sample_rates /* [C], host, or NULL */, unsigned what,
+                                   float* features /* [10][C][D] */, float* energy /* [C][D] or NULL */, float* log_attack_time /* [C] or NULL */,
+                                   float* magnitudes /* [D][C][N/2+1] or NULL */, int mem_kind);
+/* Each channel's analyser has a nyquistFrequency of its own (AudioAnalysis.h:107): files of one library come at 44.1 and 48 kHz.  The setter
+ * takes [C] host values, refuses per entry what fx_offline_create refuses for its one value (naming the channel, changing nothing), and
+ * takes effect in stream order: fx_offline_spectral_characteristics, fx_offline_harmonic_characteristics, fx_offline_auto_correlation and
+ * the two whole-analysis entries read the channel's value from then on.  previousF0 and previousBinMagnitudes are left alone.  An object
+ * never set reads the creation value in every channel, which is what the getter returns until the first set. */
+fx_status fx_offline_set_nyquists(fx_offline* o, const double* nyquist /* [C], host */);
+fx_status fx_offline_get_nyquists(fx_offline* o, double* out /* [C], host */);
+
 /* ---- what the reference derives from a feature buffer: ranges, discrete distributions, smoothed features (AudioFeatures.h:208-240,
  * :356-421) ----
  * rows is [R][C][D] fp32, any R = num_rows rows of a feature buffer: rows[(r * C + c) * D + i] is the reference's arrayStartIndex with
