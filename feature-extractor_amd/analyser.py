@@ -274,7 +274,7 @@ class BatchAnalyser:
     def last_launches(self):
         """fx_last_launches_internal (csrc/fx_kernels.h, tests only): the launches the last analysis call made, in order, one dict each
         (capi.LAUNCH_FIELDS; 'kind' as a name: frame, frame_tail, hop, hop_pair, pair, epilogue, reblock, osc, taps, deinterleave, onset_events, osc_table,
-        osc_bundle, display, sources, resample, monitor, listen)."""
+        osc_bundle, display, sources, resample, monitor, listen, rtp)."""
         cap = capi.LAUNCH_RECORD_CAP
         buf = (ctypes.c_int * (cap * len(capi.LAUNCH_FIELDS)))()
         n = self._lib.fx_last_launches_internal(self._h, buf, cap)
@@ -518,6 +518,132 @@ class BatchAnalyser:
         n, K = interleaved_dims(tuple(keep.shape), count * (3 if fmt == capi.SAMPLE_S24 else 1), fmt, num_source_channels)
         frames = (self.pending_samples() + n) // (self.window_size // 2)
         return self._analyse("fx_push_interleaved", d, (n, K), frames, want_raw, want_smoothed, block=True)
+
+    # ---- RTP audio in: a tick's L16 / L24 datagrams unpacked on the GPU (include/fx.h, fx_rtp_configure .. fx_push_rtp) ----
+    def rtp_configure(self, payload_format, channels_per_stream):
+        """S streams of channels_per_stream[s] channels each, all "l16" or "l24" (capi.RTP_L16 / RTP_L24); every stream not running,
+        every track's source none, the statistics zero.  No streams frees the unit."""
+        fmt = capi.RTP_FORMATS.get(payload_format, payload_format) if isinstance(payload_format, str) else payload_format
+        if isinstance(fmt, str):
+            raise ValueError("a payload format is one of %s" % ", ".join(sorted(capi.RTP_FORMATS)))
+        ch = np.ascontiguousarray(np.asarray(channels_per_stream, dtype=np.int32).ravel())
+        capi.check(self._lib.fx_rtp_configure(self._h, int(fmt), int(ch.size), ch.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if ch.size else None))
+        self._rtp = (int(ch.size), 2 if int(fmt) == capi.RTP_L16 else 3) if ch.size else None
+
+    def set_rtp_sources(self, tracks, stream, channel=0):
+        """Track tracks[i] hears channel channel[i] of stream stream[i] (one value for all is fine; stream -1 or None: none, the track
+        hears zeros).  Of a track listed twice the last entry wins; the listed tracks' pending samples become zeros."""
+        a, ptr = self._track_list(tracks)
+        streams = list(stream) if isinstance(stream, (list, tuple, np.ndarray)) else [stream]
+        s, sp = self._per_entry([-1 if x is None else x for x in streams], int(a.size))
+        c, cp = self._per_entry(channel, int(a.size))
+        capi.check(self._lib.fx_rtp_set_track_sources(self._h, ptr, int(a.size), sp, cp))
+
+    def rtp_sources(self):
+        """The track table: dict of stream (int32 [C], -1: none) and channel (int32 [C])."""
+        out = {"stream": np.empty(self.num_channels, np.int32), "channel": np.empty(self.num_channels, np.int32)}
+        ip = ctypes.POINTER(ctypes.c_int)
+        capi.check(self._lib.fx_rtp_get_track_sources(self._h, out["stream"].ctypes.data_as(ip), out["channel"].ctypes.data_as(ip)))
+        return out
+
+    def set_rtp_timestamps(self, streams, timestamps):
+        """Stream streams[i] runs from the next tick on, whose first sample time has the RTP timestamp timestamps[i] (mod 2^32)."""
+        s = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).ravel())
+        t = np.ascontiguousarray((np.asarray(timestamps, dtype=np.int64).ravel() & 0xFFFFFFFF).astype(np.uint32))
+        if t.size == 1 and s.size != 1:
+            t = np.full(s.size, t[0], np.uint32)
+        if t.size != s.size:
+            raise ValueError("one timestamp per listed stream (%d), not %d" % (s.size, t.size))
+        capi.check(self._lib.fx_rtp_set_cursors(self._h, s.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(s.size), t.ctypes.data_as(ctypes.POINTER(ctypes.c_uint))))
+
+    def _rtp_streams(self):
+        if getattr(self, "_rtp", None) is None:
+            raise ValueError("RTP input is not configured (rtp_configure)")
+        return self._rtp
+
+    def rtp_timestamps(self):
+        """The cursors: (timestamp uint32 [S], running int32 [S]); the host's copy, no device use."""
+        S, _ = self._rtp_streams()
+        t, r = np.empty(S, np.uint32), np.empty(S, np.int32)
+        capi.check(self._lib.fx_rtp_get_cursors(self._h, t.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), r.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return t, r
+
+    def push_rtp(self, slots, lengths, stream_of, num_samples, want_raw=True, want_smoothed=True, want_disposition=True):
+        """One tick of num_samples samples per track from the datagrams in `slots` (uint8 [P][stride]: numpy, or a torch CUDA tensor
+        from a 4-byte boundary), datagram i the first lengths[i] bytes of slot i, from stream stream_of[i] (host arrays)
+        -> (raw, smoothed, disposition): the results as push_samples returns them for the unpacked block, and one byte of
+        capi.RTP_* bits per packet (None if not wanted).  P == 0 is a tick of pure loss."""
+        n = int(num_samples)
+        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32).ravel())
+        so = np.ascontiguousarray(np.asarray(stream_of, dtype=np.int32).ravel())
+        torch_input = _is_torch(slots)
+        if torch_input:
+            if not slots.is_cuda or not slots.is_contiguous() or str(slots.dtype) != "torch.uint8" or slots.dim() != 2:
+                raise ValueError("device slots are a contiguous uint8 CUDA tensor [P][stride]")
+            if slots.device.index != self.device:
+                raise ValueError("the slots live on %s, the analyser on cuda:%d" % (slots.device, self.device))
+            if slots.data_ptr() % 4:
+                raise ValueError("device slots must start on a 4-byte boundary")
+            P, stride, ptr, where = int(slots.shape[0]), int(slots.shape[1]), ctypes.c_void_p(slots.data_ptr()), slots.device
+        else:
+            slots = np.ascontiguousarray(slots, np.uint8)
+            if slots.ndim != 2:
+                raise ValueError("slots are uint8 [P][stride]")
+            P, stride, ptr, where = int(slots.shape[0]), int(slots.shape[1]), slots.ctypes.data_as(ctypes.c_void_p), None
+        if ln.size != P or so.size != P:
+            raise ValueError("one length and one stream per slot (%d), not %d and %d" % (P, ln.size, so.size))
+        frames = (self.pending_samples() + n) // (self.window_size // 2) if n > 0 else 0
+        shape = (self.num_channels, frames, 12)
+        if torch_input:
+            import torch
+            raw = torch.empty(shape, dtype=torch.float32, device=where) if want_raw else None
+            sm = torch.empty(shape, dtype=torch.float32, device=where) if want_smoothed else None
+            disp = torch.zeros(P, dtype=torch.uint8, device=where) if want_disposition else None
+            pointers = [ctypes.c_void_p(r.data_ptr()) if r is not None and r.numel() else None for r in (raw, sm, disp)]
+        else:
+            raw = np.empty(shape, np.float32) if want_raw else None
+            sm = np.empty(shape, np.float32) if want_smoothed else None
+            disp = np.zeros(P, np.uint8) if want_disposition else None
+            pointers = [r.ctypes.data_as(ctypes.c_void_p) if r is not None and r.size else None for r in (raw, sm, disp)]
+        frames_out = ctypes.c_int(0)
+        ip = ctypes.POINTER(ctypes.c_int)
+        args = (self._h, ptr if P else None, ln.ctypes.data_as(ip) if P else None, so.ctypes.data_as(ip) if P else None, P, stride if P else 12, n,
+                capi.MEM_DEVICE if torch_input else capi.MEM_HOST, pointers[0], pointers[1], ctypes.byref(frames_out), pointers[2])
+        if torch_input:
+            self._ordered(where, self._lib.fx_push_rtp, *args)
+        else:
+            capi.check(self._lib.fx_push_rtp(*args))
+        assert frames_out.value == frames
+        return raw, sm, disp
+
+    def rtp_block(self, device=False):
+        """The last tick's planar block as push_samples would take it: int16 [C][n] for L16, uint8 [C][3n] for L24 (numpy, or a CUDA
+        torch tensor written asynchronously on the library's stream); n == 0 before the first tick."""
+        _, B = self._rtp_streams()
+        n, fmt, probe = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        # (no room at all: refused while a block is held, and the refusal still reports its length)
+        status = self._lib.fx_rtp_get_block(self._h, ctypes.byref(probe), 0, ctypes.byref(n), ctypes.byref(fmt), capi.MEM_HOST)
+        if status != capi.FX_OK and n.value == 0:
+            capi.check(status)
+        shape = (self.num_channels, n.value) if B == 2 else (self.num_channels, 3 * n.value)
+        nbytes = self.num_channels * n.value * B
+        if device:
+            import torch
+            out = torch.empty(shape, dtype=torch.int16 if B == 2 else torch.uint8, device=torch.device("cuda", self.device))
+            if nbytes:
+                self._ordered(out.device, self._lib.fx_rtp_get_block, self._h, ctypes.c_void_p(out.data_ptr()), nbytes, ctypes.byref(n), ctypes.byref(fmt), capi.MEM_DEVICE)
+        else:
+            out = np.empty(shape, np.int16 if B == 2 else np.uint8)
+            if nbytes:
+                capi.check(self._lib.fx_rtp_get_block(self._h, out.ctypes.data_as(ctypes.c_void_p), nbytes, ctypes.byref(n), ctypes.byref(fmt), capi.MEM_HOST))
+        return out
+
+    def rtp_stats(self):
+        """Per stream, summed since rtp_configure: dict of int64 [S] arrays, capi.RTP_STATS_FIELDS."""
+        S, _ = self._rtp_streams()
+        out = np.empty((S, len(capi.RTP_STATS_FIELDS)), np.int64)
+        capi.check(self._lib.fx_rtp_get_stats(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return {name: out[:, k].copy() for k, name in enumerate(capi.RTP_STATS_FIELDS)}
 
     # ---- file sources: tracks play device-resident clips (include/fx.h, fx_create_clips .. fx_push_sources; AudioFilePlayer.h:41-67) ----
     def create_clips(self, samples, lengths=None, sample_format=None, borrow=False, sample_rates=None):

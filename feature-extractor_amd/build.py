@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libfx_hip.so")
 # the shim's host units: no kernel, nothing of the units that attach through fx_context.h's hooks.  The fake-HIP test builds
 # (tests/cpp/fake_hip) compile exactly these.
 HOST_SOURCES = ["fx_capi.cpp", "fx_plan.cpp", "fx_stream.cpp", "fx_comm.cpp", "fx_osc_sender.cpp"]
-SOURCES = ["fx_kernels.hip", "fx_offline.hip", "fx_offline_frames.hip", "fx_offline_files.hip", "fx_offline_stats.hip", "fx_reblock.hip", "fx_osc.hip", "fx_taps.hip", "fx_interleave.hip", "fx_events.hip", "fx_tracks.hip", "fx_osc_table.hip", "fx_osc_bundle.hip", "fx_track_state.hip", "fx_display.hip", "fx_clips.hip", "fx_monitor.hip"] + HOST_SOURCES
+SOURCES = ["fx_kernels.hip", "fx_offline.hip", "fx_offline_frames.hip", "fx_offline_files.hip", "fx_offline_stats.hip", "fx_reblock.hip", "fx_osc.hip", "fx_taps.hip", "fx_interleave.hip", "fx_events.hip", "fx_tracks.hip", "fx_osc_table.hip", "fx_osc_bundle.hip", "fx_track_state.hip", "fx_display.hip", "fx_clips.hip", "fx_monitor.hip", "fx_rtp.hip"] + HOST_SOURCES
 # fx_kernels.hip is compiled twice: frame kernels up to 1024 points (+ tail kernels + host helpers) with the scheduler's
 # alternative register-pressure tracker (+3.5 % at 1024 points), the 2048- / 4096-point frame kernels without (-7 % at 4096)
 UNITS = [("fx_kernels.hip", "fx_kernels_small.o", ["-DFX_PART=1", "-mllvm", "-amdgpu-use-amdgpu-trackers=1"]),
@@ -34,8 +34,9 @@ UNITS = [("fx_kernels.hip", "fx_kernels_small.o", ["-DFX_PART=1", "-mllvm", "-am
          ("fx_track_state.hip", "fx_track_state.o", []),
          ("fx_display.hip", "fx_display.o", []),
          ("fx_clips.hip", "fx_clips.o", []),
-         ("fx_monitor.hip", "fx_monitor.o", [])] + [(s, s.replace(".cpp", ".o"), []) for s in HOST_SOURCES]
-HEADERS = ["fx_kernels.h", "fx_context.h", "fx_offline_frames.h", "fx_offline_object.h", "fx_plan.h", "fx_osc_words.h", "fx_wave.hip.h", "fx_lane_exchange.h", "fx_lane_consts.hip.h", "fx_flux_runs.h", "fx_fft.hip.h", "fx_plain_fft.hip.h", "fx_offline_frame_body.hip.h", "fx_offline_steps.hip.h", "fx_samples.hip.h", "fx_blocks.hip.h", "fx_frame_kernel.hip.h", "fx_pair_kernel.hip.h", "fx_tail_kernels.hip.h", "fx_hop_kernel.hip.h",
+         ("fx_monitor.hip", "fx_monitor.o", []),
+         ("fx_rtp.hip", "fx_rtp.o", [])] + [(s, s.replace(".cpp", ".o"), []) for s in HOST_SOURCES]
+HEADERS = ["fx_kernels.h", "fx_context.h", "fx_offline_frames.h", "fx_offline_object.h", "fx_plan.h", "fx_osc_words.h", "fx_wave.hip.h", "fx_lane_exchange.h", "fx_lane_consts.hip.h", "fx_flux_runs.h", "fx_fft.hip.h", "fx_plain_fft.hip.h", "fx_offline_frame_body.hip.h", "fx_offline_steps.hip.h", "fx_samples.hip.h", "fx_blocks.hip.h", "fx_rtp_packet.h", "fx_frame_kernel.hip.h", "fx_pair_kernel.hip.h", "fx_tail_kernels.hip.h", "fx_hop_kernel.hip.h",
            os.path.join("..", "..", "include", "fx.h")]
 
 # -ffp-contract=off : the reference FFT never fuses a*b+c; spectra must be bit-identical.

@@ -25,13 +25,18 @@ LAUNCH_FIELDS = ["kind", "window", "analysers", "T", "direct_state", "block_mode
                  "ep_T", "out_stride", "ep_form", "reblock"]
 LAUNCH_KINDS = {1: "frame", 2: "frame_tail", 3: "hop", 4: "hop_pair", 5: "pair", 6: "epilogue", 7: "reblock", 8: "osc", 9: "taps",
                 10: "deinterleave", 11: "onset_events", 12: "osc_table", 13: "osc_bundle", 14: "display", 15: "sources", 16: "resample", 17: "monitor",
-                18: "listen"}
+                18: "listen", 19: "rtp"}
 # file sources (include/fx.h): FX_SOURCE_*, FX_TRANSPORT_*, the fx_transport commands FX_PLAY .. FX_RESTART, FX_CLIP_BORROW
 SOURCE_INPUT, SOURCE_FILE = 0, 1
 TRANSPORT_NO_FILE, TRANSPORT_PLAYING, TRANSPORT_PAUSED, TRANSPORT_STOPPED, TRANSPORT_FINISHED = range(5)
 PLAY, PAUSE, STOP, RESTART = range(4)
 TRANSPORT_COMMANDS = {"play": PLAY, "pause": PAUSE, "stop": STOP, "restart": RESTART}
 CLIP_BORROW = 1
+# RTP input (include/fx.h): FX_RTP_L16 / FX_RTP_L24, the disposition bits FX_RTP_*, struct fx_rtp_stats' fields in order
+RTP_L16, RTP_L24 = 0, 1
+RTP_FORMATS = {"l16": RTP_L16, "l24": RTP_L24}
+RTP_PLACED, RTP_LATE, RTP_EARLY, RTP_MALFORMED, RTP_IGNORED = 1, 2, 4, 8, 16
+RTP_STATS_FIELDS = ["packets", "malformed", "late_packets", "early_packets", "samples_placed", "samples_missing"]
 MONITOR_GROUP = 64                  # FX_MONITOR_GROUP: the tracks whose sends are summed in a row before the groups are
 LISTEN_SELF, LISTEN_LEFT, LISTEN_RIGHT = 0, 1, 2       # FX_LISTEN_*: what a track's analysers hear (fx_set_channel_listen)
 LISTENS = {"self": LISTEN_SELF, "left": LISTEN_LEFT, "right": LISTEN_RIGHT}
@@ -115,6 +120,10 @@ def _prototypes():
         ("fx_push_hops", [vp, vp, i, i, i, vp, vp], st), ("fx_push_samples", [vp, vp, i, i, i, vp, vp, ip], st),
         ("fx_set_channel_map", [vp, ip], st), ("fx_push_interleaved", [vp, vp, i, i, i, i, vp, vp, ip], st),
         ("fx_pending_samples", [vp], st), ("fx_clear_pending", [vp], st),
+        ("fx_rtp_configure", [vp, i, i, ip], st), ("fx_rtp_set_track_sources", [vp, ip, i, ip, ip], st), ("fx_rtp_get_track_sources", [vp, ip, ip], st),
+        ("fx_rtp_set_cursors", [vp, ip, i, P(u)], st), ("fx_rtp_get_cursors", [vp, P(u), ip], st),
+        ("fx_push_rtp", [vp, vp, ip, ip, i, i, i, i, vp, vp, ip, vp], st), ("fx_rtp_get_block", [vp, vp, ctypes.c_size_t, ip, ip, i], st),
+        ("fx_rtp_get_stats", [vp, vp], st),
         ("fx_create_clips", [vp, vp, llp, i, i, i, u, ip], st), ("fx_destroy_clips", [vp, i], st), ("fx_set_channel_clips", [vp, ip, i, ip, ip], st),
         ("fx_set_clip_rates", [vp, ip, i, dp], st), ("fx_get_resampler_table", [fp, i, ip, ip], st),
         ("fx_set_channel_sources", [vp, ip, i, ip], st), ("fx_transport", [vp, ip, i, i], st), ("fx_get_transport", [vp, ip, ip, llp, llp], st),

@@ -434,6 +434,7 @@ fx_status fx_destroy(fx_context* c)
     if (c->display_release) c->display_release(c);
     if (c->clips_release) c->clips_release(c);
     if (c->monitor_release) c->monitor_release(c);
+    if (c->rtp_release) c->rtp_release(c);
     fx_free_device({c->d_tw, c->d_prev, c->d_tail[0], c->d_tail[1], c->d_hist, c->d_latest,
                     c->d_raw, c->d_part, c->d_in, c->d_out_raw, c->d_queue, c->d_carry[0], c->d_carry[1], c->d_hops, c->d_osc, c->d_chan, c->d_flux_park});
     if (c->h_err) (void) hipHostFree(c->h_err);

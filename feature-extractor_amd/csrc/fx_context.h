@@ -1,6 +1,6 @@
 // fx_context.h -- the context behind the C ABI (include/fx.h), shared by the shim's host units (fx_capi.cpp, fx_plan.cpp, fx_stream.cpp,
 // fx_comm.cpp) and the units that attach through its hooks (fx_taps.hip, fx_interleave.hip, fx_events.hip, fx_tracks.hip,
-// fx_osc_table.hip, fx_osc_bundle.hip, fx_track_state.hip, fx_display.hip, fx_clips.hip, fx_monitor.hip).  Internal.
+// fx_osc_table.hip, fx_osc_bundle.hip, fx_track_state.hip, fx_display.hip, fx_clips.hip, fx_monitor.hip, fx_rtp.hip).  Internal.
 //
 // What a new attached unit uses instead of copying its neighbour: a list of tracks is judged by fx_check_channel_list and
 // fx_check_channel_entries (the call's own values between the two), a memory kind by fx_check_memory_kind (or fx_check_call, with a
@@ -100,6 +100,7 @@ struct fx_track_state;  // fx_track_state.hip
 struct fx_display;      // fx_display.hip
 struct fx_clips;        // fx_clips.hip
 struct fx_monitor;      // fx_monitor.hip
+struct fx_rtp;          // fx_rtp.hip
 // The OSC address table in force (fx_osc_table.hip makes and frees it; fx_osc_bundle.hip reads it): one device allocation, [C][128]
 // bytes of rows, then int len[C]; the messages' lengths on the host.
 struct fx_osc_table {
@@ -252,6 +253,12 @@ struct fx_context {
     fx_status (*monitor_prepare)(fx_context*, int num_samples, int sample_format) = nullptr;
     fx_status (*monitor_launch)(fx_context*, void* planar, int num_samples, int sample_format) = nullptr;
     void      (*monitor_release)(fx_context*) = nullptr;
+
+    // RTP input (fx_rtp.hip): the stream and track tables, the statistics and the scratch of fx_push_rtp; null until fx_rtp_configure,
+    // which installs the hook fx_destroy calls (and frees the unit again when it is given no streams).  The slot's state, not the
+    // analysers': no reset touches it.
+    fx_rtp* rtp = nullptr;
+    void (*rtp_release)(fx_context*) = nullptr;
 };
 
 // The per-track rows (fx_capi.cpp), for the units that change them.  fx_channel_rows: what every track runs with now -- the table's rows,

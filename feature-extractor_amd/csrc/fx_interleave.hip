@@ -27,6 +27,8 @@ namespace {
 // 16-byte chunks back (ds_read_b128) and writes them to 16-byte aligned addresses (global_store_dwordx4), consecutive lanes along a
 // row and on into the next one.  Only the first and last chunk of a row's segment are partial: they are written byte by byte, each
 // byte once, whatever the row pitch n * B makes of the alignment.
+// TWIN: fx_rtp.hip's gather restates this tile (tile_at, store_sample, pick, the store stage below as tile_to_rows): a change to the
+// layout or the drain here belongs there too.
 constexpr int DI_FRAMES = 64, DI_TRACKS = 64, DI_THREADS = 256;
 static_assert(DI_THREADS == 4 * 64 && DI_TRACKS == 64, "lane = track, four wavefronts step through the frames");
 

@@ -443,6 +443,10 @@ constexpr int FX_LAUNCH_MONITOR = 17;
 // fx_push_sources while a track listens to a monitor output (fx_set_channel_listen): one launch of fx_monitor_listen_kernel, the entry
 // directly after the monitor's; T = the samples per track.  A context in which no track listens records no entry of this kind.
 constexpr int FX_LAUNCH_LISTEN = 18;
+// fx_push_rtp (fx_rtp.hip): the unpack of a tick's datagrams, the FIRST entry of the call's record; ONE entry for its launches (the
+// owner table's fill, fx_rtp_parse_kernel where the tick has packets, fx_rtp_gather_kernel, fx_rtp_count_kernel); T = the samples per
+// track the call forms.  The entries after it are those of fx_push_samples on the planar block it made.
+constexpr int FX_LAUNCH_RTP = 19;
 struct fx_launch_record {
     int kind;               // FX_LAUNCH_*
     int window, analysers;  // window size, analysers mask (bit 0 spectral, bit 1 harmonic)

@@ -1,0 +1,581 @@
+// fx_rtp.hip -- RTP audio in: a tick's L16 / L24 datagrams unpacked to the planar block on the GPU (include/fx.h, fx_rtp_configure /
+// fx_push_rtp).
+//
+// Audio in the numbers this library is built for arrives over the network (AES67, ST 2110-30, Ravenna): RTP datagrams whose payload
+// is big-endian signed PCM, a few channels interleaved per stream, a few dozen sample times per packet.  A receiver collects a tick's
+// datagrams in slots of one stride and says which stream each came from; this unit does the rest on the device, as a pure function
+// of what it was given: fx_rtp_parse_kernel judges every header (fx_rtp_packet.h), places the packet against its stream's cursor and
+// claims the tick positions it covers in an owner table [S][n] (integer atomicMax: the packet of the greatest index wins, whatever
+// order the wavefronts run in); fx_rtp_gather_kernel forms the planar block [C][n] that fx_push_samples takes -- track c's row is
+// channel j of stream s, byte-reversed to little endian, zeros where no packet owns the position -- and fx_rtp_count_kernel adds the
+// tick's owned and missing positions to the per-stream statistics.  fx_push_block (fx_capi.cpp) does the rest: the same launches, the
+// same bits as fx_push_samples of that planar block.  Integer atomics only: every result is the same at every run.
+//
+// Nothing in the shim's host units (build.py, HOST_SOURCES) refers to this unit: fx_rtp_configure installs the context's release hook.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <new>
+#include <vector>
+
+#include "fx_kernels.h"
+#include "fx_context.h"
+#include "fx_rtp_packet.h"
+
+namespace fxk {
+
+struct RtpStream {          // a row of the stream table
+    int      channels;      // 1 .. 64
+    unsigned origin;        // running: the cursor of a tick is origin + RtpTick::advanced (mod 2^32)
+    int      running;
+};
+struct RtpTrack {           // a row of the track table: what track c hears
+    int stream;             // -1: none, the track hears zeros
+    int channel;
+};
+struct RtpRecord {          // what the parse leaves of packet i for the gather; read only where the owner table names i
+    int payload;            // the payload's offset in the slot
+    int d0;                 // the tick position of its first sample time
+};
+static_assert(sizeof(fx_rtp_stats) == 6 * sizeof(long long), "the statistics are six counters per stream, accumulated as such");
+enum { ST_PACKETS = 0, ST_MALFORMED, ST_LATE, ST_EARLY, ST_PLACED, ST_MISSING, ST_FIELDS };
+
+struct RtpTick {
+    const unsigned char* slots;     // [P][stride], 4-byte aligned
+    const int*           lengths;   // [P], 0 .. stride
+    const int*           stream_of; // [P], 0 .. S - 1
+    const RtpStream*     streams;   // [S]
+    const RtpTrack*      tracks;    // [C]
+    RtpRecord*           records;   // [P]
+    int*                 owner;     // [S][n]: -1, or the greatest index of a packet that covers the position
+    unsigned char*       disposition;   // [P] or null
+    unsigned long long*  stats;     // [S][ST_FIELDS]
+    unsigned char*       out;       // [C][n] samples of B bytes, 16-byte aligned
+    int                  P, stride, S, C, n;
+    int                  B;         // bytes per sample: 2 (L16) or 3 (L24)
+    unsigned             advanced;  // samples per stream of the ticks before this one (mod 2^32)
+};
+
+struct SlotBytes {
+    const unsigned char* at;
+    __device__ unsigned operator()(int k) const { return at[k]; }
+};
+
+// One wavefront per packet.  Every lane forms the same few values from the same header bytes (uniform loads); the lanes then spread
+// along the positions the packet covers.  Lane 0 leaves the record, the disposition and the packet's counts.
+__global__ void __launch_bounds__(256)
+fx_rtp_parse_kernel(const RtpTick p)
+{
+    const int lane = threadIdx.x & 63, i = (int) blockIdx.x * 4 + (int) (threadIdx.x >> 6);
+    if (i >= p.P) return;
+    const int s = p.stream_of[i], len = p.lengths[i];
+    const RtpStream st = p.streams[s];
+    unsigned long long* stats = p.stats + (size_t) s * ST_FIELDS;
+    fx_rtp_parsed h;
+    unsigned bits;
+    if (!fx_rtp_parse(SlotBytes{p.slots + (size_t) i * (size_t) p.stride}, len, st.channels * p.B, &h)) {
+        bits = FX_RTP_BIT_MALFORMED;
+        if (lane == 0) atomicAdd(&stats[ST_MALFORMED], 1ull);
+    } else if (!st.running) {
+        bits = FX_RTP_BIT_IGNORED;
+        if (lane == 0) atomicAdd(&stats[ST_PACKETS], 1ull);
+    } else {
+        const fx_rtp_placement at = fx_rtp_place(h.timestamp, st.origin + p.advanced, h.sample_times, p.n);
+        bits = at.bits;
+        int* owner = p.owner + (size_t) s * (size_t) p.n;
+        for (int q = at.lo + lane; q < at.hi; q += 64) atomicMax(&owner[q], i);
+        if (lane == 0) {
+            p.records[i] = RtpRecord{h.payload, at.d0};
+            atomicAdd(&stats[ST_PACKETS], 1ull);
+            if (!(bits & FX_RTP_BIT_PLACED) && (bits & FX_RTP_BIT_LATE)) atomicAdd(&stats[ST_LATE], 1ull);
+            if (!(bits & FX_RTP_BIT_PLACED) && (bits & FX_RTP_BIT_EARLY)) atomicAdd(&stats[ST_EARLY], 1ull);
+        }
+    }
+    if (lane == 0 && p.disposition) p.disposition[i] = (unsigned char) bits;
+}
+
+// The B bytes of a big-endian sample at byte `at` of the slots, as the little-endian sample in the low bytes.  The sample lies inside
+// its packet and a slot starts and ends on a dword boundary, so the one or two aligned dwords around it lie inside the slot: no wide
+// load that could cross the end of the slots' memory.
+template <int B> __device__ __forceinline__ unsigned load_reversed(const unsigned char* slots, long long at)
+{
+    const unsigned sh = (unsigned) at & 3u;
+    const unsigned* w = reinterpret_cast<const unsigned*>(slots + (at - sh));
+    const unsigned lo = w[0], hi = sh + B > 4 ? w[1] : 0u;
+    const unsigned v = __builtin_amdgcn_alignbyte(hi, lo, sh);         // the sample's bytes from bit 0 up, first byte lowest
+    return __builtin_bswap32(v) >> (32 - 8 * B);                        // (one v_perm_b32 and a shift)
+}
+
+// ---- the tile: PT_TRACKS planar rows on their way to memory through LDS ----
+// TWIN: tile_at, store_sample, pick and tile_to_rows restate the tile of fx_deinterleave_kernel (fx_interleave.hip: tile_at,
+// store_sample, pick and the kernel's store stage) for 2- and 3-byte samples.  A change to the layout or the drain of one belongs in
+// the other too.  (They are two copies because that kernel's machine code moves when its tile comes from a shared header.)
+// The load stage puts sample f of tile row r at byte m + f * B of the row, m the byte the row's segment has in the planar block
+// modulo 16.  The store stage reads whole 16-byte chunks back (ds_read_b128) and writes them to 16-byte aligned addresses
+// (global_store_dwordx4), consecutive lanes along a row and on into the next one.  Only the first and last chunk of a row's segment
+// are partial: they are written byte by byte, each byte once, whatever the row pitch n * B makes of the alignment.
+constexpr int PT_FRAMES = 64, PT_TRACKS = 64, PT_THREADS = 256, PT_GROUP = 8;
+static_assert(PT_THREADS == 4 * 64 && PT_TRACKS == 64 && (PT_FRAMES / 4) % PT_GROUP == 0, "lane = track, four wavefronts step through the positions, PT_GROUP at a time");
+// a row's segment of PT_FRAMES * B bytes, placed at its offset modulo 16
+template <int B> constexpr int pt_chunks() { return PT_FRAMES * B / 16 + 1; }
+template <int B> constexpr int pt_row() { return 16 * pt_chunks<B>(); }
+
+// Byte `col` of tile row r: chunks of 16 bytes in order, the four dwords of a chunk rotated by (r / 8) % 4.  A row is 9 (L16) or 13
+// (L24) chunks, 36 or 52 dwords: on the 32 banks a store sees, row r starts at bank 4 r or 20 r modulo 32, eight distinct multiples
+// of 4 for r = 0 .. 7 and the same again for r + 8; the rotation moves those apart, so the load stage's stores (a group of 32 lanes =
+// 32 rows at one sample) fall on 32 distinct banks where the rows' offsets modulo 16 agree, and on at most two lanes a bank where
+// they do not.  The store stage's reads of whole chunks are not affected.
+__device__ __forceinline__ int tile_at(int r, int row_bytes, int col)
+{
+    return r * row_bytes + (col & ~15) + ((((col >> 2) + (r >> 3)) & 3) << 2) + (col & 3);
+}
+
+// (a row's offset modulo 16 is even for 2-byte samples: those never straddle a dword of the tile)
+template <int B> __device__ __forceinline__ void store_sample(unsigned char* tile, int r, int row_bytes, int col, unsigned v)
+{
+    if constexpr (B == 2) *reinterpret_cast<unsigned short*>(tile + tile_at(r, row_bytes, col)) = (unsigned short) v;
+    else {
+#pragma unroll
+        for (int i = 0; i < 3; i++) tile[tile_at(r, row_bytes, col + i)] = (unsigned char) (v >> (8 * i));
+    }
+}
+
+__device__ __forceinline__ unsigned pick(const uint4& q, int j)
+{
+    j &= 3;
+    return j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w;
+}
+
+// The tile's rows to out [C][n] samples of B bytes (16-byte aligned): tracks c0 .. of the block's C, positions q0 .. q0 + nq of n.
+// All PT_THREADS threads of the workgroup, after the barrier that ends the load stage.
+template <int B>
+__device__ __forceinline__ void tile_to_rows(const unsigned char* tile, unsigned char* out, int c0, int C, int q0, int nq, int n)
+{
+    constexpr int CHUNKS = pt_chunks<B>(), ROW = pt_row<B>();
+    for (int i = threadIdx.x; i < PT_TRACKS * CHUNKS; i += PT_THREADS) {
+        const int r = i / CHUNKS, k = i - r * CHUNKS, c = c0 + r;
+        if (c >= C) break;                                  // (r only grows with i)
+        const long long seg = ((long long) c * n + q0) * B;
+        const int m = (int) (seg & 15);
+        const int lo = m > 16 * k ? m : 16 * k, hi = m + nq * B < 16 * k + 16 ? m + nq * B : 16 * k + 16;
+        if (lo >= hi) continue;
+        const uint4 s = *reinterpret_cast<const uint4*>(tile + r * ROW + 16 * k);
+        const int rot = r >> 3;
+        const uint4 q{pick(s, rot), pick(s, rot + 1), pick(s, rot + 2), pick(s, rot + 3)};
+        unsigned char* dst = out + (seg - m) + 16 * k;
+        if (hi - lo == 16) {
+            *reinterpret_cast<uint4*>(dst) = q;
+        } else {
+            for (int b = lo - 16 * k; b < hi - 16 * k; b++) dst[b] = (unsigned char) (pick(q, b >> 2) >> (8 * (b & 3)));
+        }
+    }
+}
+
+// A workgroup takes PT_FRAMES positions of PT_TRACKS consecutive tracks.  Load: lane = track, wavefront = position, so a wavefront
+// reads, of every stream its tracks hear, one sample time of one packet: F contiguous bytes where consecutive tracks hear consecutive
+// channels, and the sample time after it four steps later.  The owner and the record are the same address for all lanes of a stream
+// (one request).  The samples go to the tile above and from there to the planar rows.
+template <int B>
+__global__ void __launch_bounds__(PT_THREADS)
+fx_rtp_gather_kernel(const RtpTick p)
+{
+    constexpr int ROW = pt_row<B>();
+    __shared__ __attribute__((aligned(16))) unsigned char tile[PT_TRACKS * ROW];
+    const int q0 = (int) blockIdx.x * PT_FRAMES;
+    const int c0 = (int) blockIdx.y * PT_TRACKS;
+    const int nq = p.n - q0 < PT_FRAMES ? p.n - q0 : PT_FRAMES;
+
+    {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = c0 + lane;
+        if (c < p.C) {
+            const int m = (int) (((long long) c * p.n * B + (long long) q0 * B) & 15);
+            const RtpTrack t = p.tracks[c];
+            const int F = t.stream >= 0 ? p.streams[t.stream].channels * B : 0;
+            const int* owner = p.owner + (size_t) (t.stream >= 0 ? t.stream : 0) * (size_t) p.n + q0;
+            const bool heard = t.stream >= 0;
+            // PT_GROUP positions at a time, each of the three dependent loads (owner, record, sample) for all of them before the next
+#pragma unroll 1
+            for (int j0 = 0; j0 < PT_FRAMES / 4; j0 += PT_GROUP) {
+                int own[PT_GROUP];
+                RtpRecord rec[PT_GROUP];
+                unsigned v[PT_GROUP];
+#pragma unroll
+                for (int g = 0; g < PT_GROUP; g++) {
+                    const int f = wave + 4 * (j0 + g);
+                    own[g] = heard && f < nq ? owner[f] : -1;
+                }
+#pragma unroll
+                for (int g = 0; g < PT_GROUP; g++) rec[g] = own[g] >= 0 ? p.records[own[g]] : RtpRecord{0, 0};
+#pragma unroll
+                for (int g = 0; g < PT_GROUP; g++) {
+                    const int f = wave + 4 * (j0 + g);
+                    v[g] = own[g] >= 0 ? load_reversed<B>(p.slots, (long long) own[g] * p.stride + rec[g].payload + (long long) (q0 + f - rec[g].d0) * F + t.channel * B) : 0u;
+                }
+#pragma unroll
+                for (int g = 0; g < PT_GROUP; g++) {
+                    const int f = wave + 4 * (j0 + g);
+                    if (f < nq) store_sample<B>(tile, lane, ROW, m + f * B, v[g]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    tile_to_rows<B>(tile, p.out, c0, p.C, q0, nq, p.n);
+}
+
+// Owned and missing positions of the tick, per running stream: workgroup (s, y) steps through the stream's row of the owner table,
+// every wavefront counts by ballot and adds its two sums once.
+__global__ void __launch_bounds__(256)
+fx_rtp_count_kernel(const RtpTick p)
+{
+    const int s = (int) blockIdx.x;
+    if (!p.streams[s].running) return;
+    const int* owner = p.owner + (size_t) s * (size_t) p.n;
+    int owned = 0, seen = 0;
+    for (int q0 = (int) blockIdx.y * 256; q0 < p.n; q0 += 256 * (int) gridDim.y) {
+        const int q = q0 + (int) threadIdx.x;
+        const bool in = q < p.n;
+        seen += __popcll(__ballot(in));
+        owned += __popcll(__ballot(in && owner[q] >= 0));
+    }
+    if ((threadIdx.x & 63) == 0 && seen) {
+        unsigned long long* stats = p.stats + (size_t) s * ST_FIELDS;
+        atomicAdd(&stats[ST_PLACED], (unsigned long long) owned);
+        atomicAdd(&stats[ST_MISSING], (unsigned long long) (seen - owned));
+    }
+}
+
+hipError_t launch_rtp_kernels(const RtpTick& p, hipStream_t stream)
+{
+    const long long gx = ((long long) p.n + PT_FRAMES - 1) / PT_FRAMES, gy = ((long long) p.C + PT_TRACKS - 1) / PT_TRACKS;
+    if (gy > 65535) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(p.owner, 0xff, sizeof(int) * (size_t) p.S * (size_t) p.n, stream);
+    if (e != hipSuccess) return e;
+    const dim3 parse((unsigned) ((p.P + 3) / 4)), gather((unsigned) gx, (unsigned) gy);
+    const dim3 count((unsigned) p.S, (unsigned) (gx < 16 ? (gx + 3) / 4 : 4));
+    if (p.P > 0) hipLaunchKernelGGL(fx_rtp_parse_kernel, parse, dim3(256), 0, stream, p);
+    if (p.B == 2) hipLaunchKernelGGL(fx_rtp_gather_kernel<2>, gather, dim3(PT_THREADS), 0, stream, p);
+    else hipLaunchKernelGGL(fx_rtp_gather_kernel<3>, gather, dim3(PT_THREADS), 0, stream, p);
+    hipLaunchKernelGGL(fx_rtp_count_kernel, count, dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+} // namespace fxk
+
+struct fx_rtp {
+    int format = FX_RTP_L16;                    // FX_RTP_L16 / FX_RTP_L24
+    std::vector<fxk::RtpStream> streams;        // [S]: the host's copy of the stream table
+    std::vector<fxk::RtpTrack>  tracks;         // [C]
+    unsigned advanced = 0;                      // samples per stream of all ticks so far (mod 2^32)
+    int      last_n = 0;                        // the last tick's samples per track: what fx_rtp_get_block copies
+    fxk::RtpStream* d_streams = nullptr;
+    fxk::RtpTrack*  d_tracks = nullptr;
+    unsigned long long* d_stats = nullptr;      // [S][6]
+    // a tick's lengths and stream numbers, [2][P] ints: two lists in turn, each with the event of its last upload, so that a tick
+    // fills one while the upload of the tick before may still read the other
+    fx_staged_list meta[2];
+    hipEvent_t     meta_done[2] = {nullptr, nullptr};
+    int            meta_cur = 0;
+    unsigned char* d_slots = nullptr;           // a host tick's datagrams
+    unsigned char* d_disposition = nullptr;     // a host tick's disposition bytes before they go to the caller
+    fxk::RtpRecord* d_records = nullptr;
+    int*           d_owner = nullptr;
+    unsigned char* d_planar = nullptr;          // the planar block handed to fx_push_block
+    size_t slots_cap = 0, disposition_cap = 0, records_cap = 0, owner_cap = 0, planar_cap = 0;
+
+    int bytes() const { return format == FX_RTP_L16 ? 2 : 3; }
+    int sample_format() const { return format == FX_RTP_L16 ? FX_SAMPLE_S16 : FX_SAMPLE_S24; }
+};
+
+namespace {
+
+void rtp_release(fx_context* c)
+{
+    fx_rtp* s = c->rtp;
+    if (!s) return;
+    fx_free_device({s->d_streams, s->d_tracks, s->d_stats, s->d_slots, s->d_disposition, s->d_records, s->d_owner, s->d_planar});
+    for (int k = 0; k < 2; k++) {
+        fx_release_list(&s->meta[k]);
+        if (s->meta_done[k]) (void) hipEventDestroy(s->meta_done[k]);
+    }
+    delete s;
+    c->rtp = nullptr;
+}
+
+fx_status rtp_configured(const fx_context* c, fx_rtp** out)
+{
+    if (!c->rtp) return fx_fail(FX_ERR_INVALID_ARGUMENT, "RTP input is not configured on this context (fx_rtp_configure)");
+    *out = c->rtp;
+    return FX_OK;
+}
+
+// the host's stream table to the device; the stream is idle
+fx_status upload_streams(fx_rtp* s)
+{
+    HIP_TRY(hipMemcpy(s->d_streams, s->streams.data(), s->streams.size() * sizeof(fxk::RtpStream), hipMemcpyHostToDevice));
+    return FX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+fx_status fx_rtp_configure(fx_context* c, int payload_format, int num_streams, const int* channels)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    if (payload_format != FX_RTP_L16 && payload_format != FX_RTP_L24) return fx_fail(FX_ERR_INVALID_ARGUMENT, "unknown payload format %d", payload_format);
+    if (num_streams < 0 || num_streams > FX_RTP_MAX_STREAMS)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d streams: a context takes 0 (none) to %d", num_streams, FX_RTP_MAX_STREAMS);
+    if (num_streams > 0 && !channels) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null channel counts with %d streams", num_streams);
+    for (int k = 0; k < num_streams; k++)
+        if (channels[k] < 1 || channels[k] > FX_RTP_MAX_CHANNELS)
+            return fx_fail(FX_ERR_INVALID_ARGUMENT, "channels[%d] = %d: a stream carries 1 to %d channels", k, channels[k], FX_RTP_MAX_CHANNELS);
+    if (num_streams == 0 && !c->rtp) return FX_OK;
+    { const fx_status ds = fx_require_device(); if (ds != FX_OK) return ds; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));           // ticks in flight read the tables
+    if (num_streams == 0) {
+        rtp_release(c);
+        return FX_OK;
+    }
+    // the new unit whole, then the old one goes: a failure leaves the context as it was
+    fx_rtp* s = new (std::nothrow) fx_rtp();
+    if (!s) return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    fx_rtp* const old = c->rtp;
+    c->rtp = s;                                         // (rtp_release frees what c->rtp names)
+    const auto give_up = [&](fx_status st) { rtp_release(c); c->rtp = old; return st; };
+    try {
+        s->streams.resize((size_t) num_streams);
+        s->tracks.assign((size_t) c->C, fxk::RtpTrack{-1, 0});
+    } catch (const std::bad_alloc&) {
+        return give_up(fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed"));
+    }
+    for (int k = 0; k < num_streams; k++) s->streams[(size_t) k] = fxk::RtpStream{channels[k], 0u, 0};
+    s->format = payload_format;
+    const size_t stream_bytes = sizeof(fxk::RtpStream) * (size_t) num_streams, track_bytes = sizeof(fxk::RtpTrack) * (size_t) c->C;
+    const size_t stats_bytes = sizeof(fx_rtp_stats) * (size_t) num_streams;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->d_streams), stream_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_tracks), track_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_stats), stats_bytes);
+    for (int k = 0; k < 2 && e == hipSuccess; k++) e = hipEventCreateWithFlags(&s->meta_done[k], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemcpy(s->d_streams, s->streams.data(), stream_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(s->d_tracks, s->tracks.data(), track_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(s->d_stats, 0, stats_bytes);
+    if (e != hipSuccess) return give_up(fx_fail(fx_hip_status(e), "allocating the RTP tables failed: %s", hipGetErrorString(e)));
+    c->rtp = old;
+    rtp_release(c);
+    c->rtp = s;
+    c->rtp_release = rtp_release;
+    return FX_OK;
+}
+
+fx_status fx_rtp_set_track_sources(fx_context* c, const int* tracks, int num_tracks, const int* stream, const int* channel)
+{
+    fx_status st = fx_check_channel_list(c, tracks, num_tracks);
+    if (st != FX_OK || num_tracks == 0) return st;
+    if (!stream || !channel) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null source list with %d entries", num_tracks);
+    fx_rtp* s = nullptr;
+    if ((st = rtp_configured(c, &s)) != FX_OK) return st;
+    for (int i = 0; i < num_tracks; i++) {
+        if (stream[i] == -1) continue;
+        if (stream[i] < 0 || stream[i] >= (int) s->streams.size())
+            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: stream %d out of range [0,%d) (-1: none)", i, stream[i], (int) s->streams.size());
+        if (channel[i] < 0 || channel[i] >= s->streams[(size_t) stream[i]].channels)
+            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: channel %d of stream %d, which carries %d", i, channel[i], stream[i], s->streams[(size_t) stream[i]].channels);
+    }
+    if ((st = fx_check_channel_entries(c, tracks, num_tracks)) != FX_OK) return st;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<fxk::RtpTrack> next;
+    try {
+        next = s->tracks;
+    } catch (const std::bad_alloc&) {
+        return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    }
+    for (int i = 0; i < num_tracks; i++) next[(size_t) tracks[i]] = fxk::RtpTrack{stream[i], stream[i] == -1 ? 0 : channel[i]};
+    // ticks already pushed read the old table on the device: they finish before it is replaced
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(s->d_tracks, next.data(), next.size() * sizeof(fxk::RtpTrack), hipMemcpyHostToDevice));
+    s->tracks.swap(next);
+    return fx_clear_pending_channels(c, tracks, num_tracks);
+}
+
+fx_status fx_rtp_get_track_sources(fx_context* c, int* stream, int* channel)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    fx_rtp* s = nullptr;
+    { const fx_status st = rtp_configured(c, &s); if (st != FX_OK) return st; }
+    for (int t = 0; t < c->C; t++) {
+        if (stream) stream[t] = s->tracks[(size_t) t].stream;
+        if (channel) channel[t] = s->tracks[(size_t) t].channel;
+    }
+    return FX_OK;
+}
+
+fx_status fx_rtp_set_cursors(fx_context* c, const int* streams, int num, const unsigned* timestamp)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    if (num < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative stream count %d", num);
+    if (num == 0) return FX_OK;
+    if (!streams || !timestamp) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null stream or timestamp list with %d entries", num);
+    fx_rtp* s = nullptr;
+    { const fx_status st = rtp_configured(c, &s); if (st != FX_OK) return st; }
+    for (int i = 0; i < num; i++)
+        if (streams[i] < 0 || streams[i] >= (int) s->streams.size())
+            return fx_fail(FX_ERR_INVALID_ARGUMENT, "entry %d: stream %d out of range [0,%d)", i, streams[i], (int) s->streams.size());
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < num; i++) {
+        fxk::RtpStream& r = s->streams[(size_t) streams[i]];
+        r.origin = timestamp[i] - s->advanced;
+        r.running = 1;
+    }
+    return upload_streams(s);
+}
+
+fx_status fx_rtp_get_cursors(fx_context* c, unsigned* timestamp, int* running)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    fx_rtp* s = nullptr;
+    { const fx_status st = rtp_configured(c, &s); if (st != FX_OK) return st; }
+    for (size_t k = 0; k < s->streams.size(); k++) {
+        if (timestamp) timestamp[k] = s->streams[k].running ? s->streams[k].origin + s->advanced : 0u;
+        if (running) running[k] = s->streams[k].running;
+    }
+    return FX_OK;
+}
+
+fx_status fx_push_rtp(fx_context* c, const void* packets, const int* lengths, const int* stream_of, int num_packets, int slot_stride,
+                      int num_samples, int mem_kind, float* out_raw, float* out_smoothed, int* frames_out, unsigned char* disposition)
+{
+    if (frames_out) *frames_out = 0;
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    c->num_launches = 0;
+    if (num_samples < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative sample count");
+    if (num_packets < 0) return fx_fail(FX_ERR_INVALID_ARGUMENT, "negative packet count %d", num_packets);
+    { const fx_status ks = fx_check_memory_kind(mem_kind); if (ks != FX_OK) return ks; }
+    if (slot_stride < 12 || slot_stride > FX_RTP_MAX_SLOT_STRIDE || slot_stride % 4 != 0)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "slot stride %d: a multiple of 4 in [12, %d]", slot_stride, FX_RTP_MAX_SLOT_STRIDE);
+    if (num_samples == 0) return FX_OK;
+    if (num_packets > 0 && (!packets || !lengths || !stream_of)) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null packets, lengths or stream list with %d packets", num_packets);
+    if (num_packets > 0 && mem_kind == FX_MEM_DEVICE && reinterpret_cast<uintptr_t>(packets) % 4 != 0)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "device packets must be 4-byte aligned");
+    fx_rtp* s = nullptr;
+    fx_status st;
+    if ((st = rtp_configured(c, &s)) != FX_OK) return st;
+    const int S = (int) s->streams.size();
+    for (int i = 0; i < num_packets; i++) {
+        if (lengths[i] < 0 || lengths[i] > slot_stride) return fx_fail(FX_ERR_INVALID_ARGUMENT, "lengths[%d] = %d: a datagram holds 0 to %d (the slot stride) bytes", i, lengths[i], slot_stride);
+        if (stream_of[i] < 0 || stream_of[i] >= S) return fx_fail(FX_ERR_INVALID_ARGUMENT, "stream_of[%d] = %d out of range [0,%d)", i, stream_of[i], S);
+    }
+    // fx_push_block's own refusals, before anything is launched: a refused call changes nothing
+    const int format = s->sample_format(), B = s->bytes();
+    { const fx_status rs = fx_block_refusal(c, num_samples, format); if (rs != FX_OK) return rs; }
+
+    HIP_TRY(hipSetDevice(c->device));
+    { const fx_status es = fx_check_device_error(c); if (es != FX_OK) return es; }
+    // everything that can fail for want of memory before the first launch.  Growing a buffer drops what it held, so the block of the
+    // tick before is gone from here on, also where one of these refuses the call.
+    s->last_n = 0;
+    const size_t P = (size_t) num_packets, slot_bytes = P * (size_t) slot_stride;
+    const size_t planar_bytes = (size_t) c->C * (size_t) num_samples * (size_t) B;
+    fx_staged_list& meta = s->meta[s->meta_cur];
+    if ((st = fx_reserve_list(c, &meta, 2 * P > 0 ? 2 * P : 1, sizeof(int))) != FX_OK) return st;
+    if ((st = fx_grow(&s->d_records, &s->records_cap, (P > 0 ? P : 1) * sizeof(fxk::RtpRecord))) != FX_OK) return st;
+    if ((st = fx_grow(&s->d_owner, &s->owner_cap, sizeof(int) * (size_t) S * (size_t) num_samples)) != FX_OK) return st;
+    if ((st = fx_grow(&s->d_planar, &s->planar_cap, (planar_bytes + 15) & ~(size_t) 15)) != FX_OK) return st;
+    if (mem_kind == FX_MEM_HOST && P > 0) {
+        if ((st = fx_grow(&s->d_slots, &s->slots_cap, slot_bytes)) != FX_OK) return st;
+        if (disposition && (st = fx_grow(&s->d_disposition, &s->disposition_cap, P)) != FX_OK) return st;
+    }
+
+    const unsigned char* d_slots = static_cast<const unsigned char*>(packets);
+    unsigned char* d_disposition = disposition;
+    if (P > 0) {
+        HIP_TRY(hipEventSynchronize(s->meta_done[s->meta_cur]));        // the upload that last read this list has finished
+        int* pinned = static_cast<int*>(meta.pinned);
+        memcpy(pinned, lengths, P * sizeof(int));
+        memcpy(pinned + P, stream_of, P * sizeof(int));
+        HIP_TRY(hipMemcpyAsync(meta.device, meta.pinned, 2 * P * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(s->meta_done[s->meta_cur], c->stream));
+        s->meta_cur ^= 1;
+        if (mem_kind == FX_MEM_HOST) {
+            HIP_TRY(hipMemcpyAsync(s->d_slots, packets, slot_bytes, hipMemcpyHostToDevice, c->stream));
+            d_slots = s->d_slots;
+            if (disposition) d_disposition = s->d_disposition;
+        }
+    }
+    fxk::RtpTick p;
+    p.slots = d_slots;
+    p.lengths = static_cast<const int*>(meta.device);
+    p.stream_of = p.lengths + P;
+    p.streams = s->d_streams;
+    p.tracks = s->d_tracks;
+    p.records = s->d_records;
+    p.owner = s->d_owner;
+    p.disposition = d_disposition;
+    p.stats = s->d_stats;
+    p.out = s->d_planar;
+    p.P = num_packets;
+    p.stride = slot_stride;
+    p.S = S;
+    p.C = c->C;
+    p.n = num_samples;
+    p.B = B;
+    p.advanced = s->advanced;
+    if (fx_launch_record* r = note_launch(c, FX_LAUNCH_RTP, 0)) r->T = num_samples;
+    HIP_TRY(fxk::launch_rtp_kernels(p, c->stream));
+    s->advanced += (unsigned) num_samples;              // every running stream's cursor
+    s->last_n = num_samples;
+    if (P > 0 && mem_kind == FX_MEM_HOST && disposition)
+        HIP_TRY(hipMemcpyAsync(disposition, s->d_disposition, P, hipMemcpyDeviceToHost, c->stream));
+    int frames = 0;
+    st = fx_push_block(c, s->d_planar, num_samples, format, FX_MEM_DEVICE, mem_kind, out_raw, out_smoothed, &frames, true);
+    if (st != FX_OK) {
+        // the copies of the caller's host arrays are enqueued: they end before the caller has them back, whatever failed
+        if (mem_kind == FX_MEM_HOST) (void) hipStreamSynchronize(c->stream);
+        return st;
+    }
+    // the caller may reuse host packets, and read the disposition, on return
+    if (mem_kind == FX_MEM_HOST) HIP_TRY(hipStreamSynchronize(c->stream));
+    if (frames_out) *frames_out = frames;
+    return FX_OK;
+}
+
+fx_status fx_rtp_get_block(fx_context* c, void* out, size_t capacity_bytes, int* num_samples, int* sample_format, int mem_kind)
+{
+    if (num_samples) *num_samples = 0;
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    if (!out) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null output pointer");
+    { const fx_status st = fx_check_memory_kind(mem_kind); if (st != FX_OK) return st; }
+    fx_rtp* s = nullptr;
+    { const fx_status st = rtp_configured(c, &s); if (st != FX_OK) return st; }
+    if (num_samples) *num_samples = s->last_n;          // (also where the room is refused: a host learns what to bring)
+    if (sample_format) *sample_format = s->sample_format();
+    const size_t bytes = (size_t) c->C * (size_t) s->last_n * (size_t) s->bytes();
+    if (capacity_bytes < bytes)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "capacity %zu bytes: the last tick's block holds %d samples per track, %zu bytes", capacity_bytes, s->last_n, bytes);
+    if (bytes == 0) return FX_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, s->d_planar, bytes, mem_kind == FX_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    if (mem_kind == FX_MEM_HOST) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return fx_check_device_error(c);
+    }
+    return FX_OK;
+}
+
+fx_status fx_rtp_get_stats(fx_context* c, fx_rtp_stats* out)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    if (!out) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null output pointer");
+    fx_rtp* s = nullptr;
+    { const fx_status st = rtp_configured(c, &s); if (st != FX_OK) return st; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out, s->d_stats, sizeof(fx_rtp_stats) * s->streams.size(), hipMemcpyDeviceToHost));
+    return fx_check_device_error(c);
+}
+
+} // extern "C"

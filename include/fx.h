@@ -269,6 +269,81 @@ int fx_pending_samples(fx_context* ctx);
  * the pending samples become zeros; their count, like the ring's indices, stays. */
 fx_status fx_clear_pending(fx_context* ctx);
 
+/* ---- RTP audio in: a tick's L16 / L24 datagrams unpacked to tracks on the GPU ----
+ * Audio in the numbers this library is built for arrives over the network (AES67, ST 2110-30, Dante in AES67 mode, Ravenna), and
+ * all of these are one wire format: RTP datagrams (RFC 3550) whose payload is L16 or L24 (RFC 3551 4.5.11, RFC 3190), big-endian
+ * signed PCM, a stream's channels interleaved per sample time.  A receiver collects the datagrams of one tick in slots of one
+ * stride and says which stream each came from; fx_push_rtp parses the headers, places the payloads by their RTP time, fills what is
+ * lost with zeros, reverses the bytes and analyses the planar block as fx_push_samples would -- all of it on the device, and the
+ * result a pure function of the arguments and the cursors.
+ *
+ *   fx_rtp_configure   S streams (1 .. FX_RTP_MAX_STREAMS), stream s of channels[s] (1 .. FX_RTP_MAX_CHANNELS) channels, all in one
+ *                      payload format (a planar block has one sample format).  Every stream starts not running, every track's
+ *                      source is none, the statistics are zero -- also when a configured context is configured again.
+ *                      num_streams == 0 frees the unit.  Synchronises the context's stream.
+ *   fx_rtp_set_track_sources  a track list under fx_reset_channels' rules (host memory, duplicates allowed and the last entry
+ *                      wins, 0 entries a no-op, every entry checked before anything changes): track tracks[i] hears channel
+ *                      channel[i] of stream stream[i]; stream[i] == -1: none, the track hears zeros.  The listed tracks' pending
+ *                      samples become zeros, also where nothing changes (as fx_set_channel_sources: toggleCollectInput,
+ *                      AudioDataCollector.h:119).  Takes effect for the ticks pushed after it; synchronises the stream.
+ *   fx_rtp_set_cursors stream streams[i] becomes running with cursor rtp_time[i]: the RTP time (the header's 32-bit sample clock,
+ *                      RFC 3550 5.1) of the first sample time of the next tick.  (A receiver takes it from a stream's first
+ *                      packet, less its latency; that policy is the caller's.)  Every tick moves every running stream's cursor
+ *                      on by its num_samples, modulo 2^32; the host keeps the cursors, so fx_rtp_get_cursors uses no device
+ *                      (0 for a stream that is not running).
+ *
+ * fx_push_rtp -- one tick.  `packets` holds num_packets slots of slot_stride bytes (a multiple of 4 in [12, FX_RTP_MAX_SLOT_STRIDE])
+ * in mem_kind memory, device memory 4-byte aligned; datagram i is the first lengths[i] (0 .. slot_stride) bytes of slot i and came
+ * from stream stream_of[i].  lengths and stream_of are host arrays and are judged before anything is launched, as are
+ * fx_push_samples' own refusals (the block's format is FX_SAMPLE_S16 for L16, FX_SAMPLE_S24 for L24): a refused call names the
+ * entry and changes nothing.  num_packets == 0 is a tick of pure loss; num_samples == 0 is a no-op.  mem_kind covers the packets,
+ * the results and `disposition` (optional: one byte of FX_RTP_* bits per packet, any alignment).  The caller may reuse host
+ * arrays on return.  With n = num_samples:
+ *   1. Packet i of length len, bytes b, is MALFORMED if len < 12 or b[0] >> 6 != 2.  P = bit 5 of b[0], X = bit 4, CC = b[0] & 15,
+ *      T = the big-endian 32 bits b[4..8); marker, payload type, sequence number and SSRC are not interpreted.  h = 12 + 4 CC; if X:
+ *      malformed if h + 4 > len, else h += 4 + 4 * (big-endian 16 bits b[h+2..h+4)).  Malformed if h > len.  pad = P ? b[len-1] : 0;
+ *      malformed if P and (pad == 0 or h + pad > len).  With F = channels[s] * B (B = 2 or 3 bytes) and payload = len - h - pad:
+ *      malformed unless payload is a positive multiple of F; m = payload / F sample times.  No byte at or beyond len is read.
+ *   2. A valid packet of a stream that is not running is IGNORED.  Otherwise d0 = (int32) (T - cursor), a wrapping subtraction
+ *      read as signed (a stream may sit anywhere within 2^31 of its cursor and cross 2^32), and the packet covers the positions
+ *      d0 .. d0 + m - 1: LATE if d0 < 0, EARLY if d0 + m > n (the caller submits such a packet again with the next tick, where its
+ *      part before the new cursor is ignored), PLACED if any position lies in [0, n).
+ *   3. Position q of stream s belongs to the valid, placed packet of the GREATEST index i that covers it; with none, it is missing.
+ *   4. The block [C][n], rows back to back, samples of B bytes: for a track with source (s, j), s running and q owned by packet i,
+ *      the B bytes at payload offset (q - d0_i) * F + j * B in reversed order (big to little endian); otherwise B zero bytes.
+ *   5. Every result, the pending samples and the launch sequence after the unpack's entry are those of fx_push_samples on that
+ *      block, bit for bit -- taps, onset events and the display included; a failure after samples have moved on leaves the stream
+ *      as fx_push_samples describes.
+ *
+ * fx_rtp_get_block copies the last tick's block [C][n] (as fx_get_monitor the mix: *num_samples = n also where the capacity is
+ * refused; host memory synchronous, device memory asynchronous on the context's stream).  fx_rtp_get_stats: per stream, summed
+ * over the ticks since fx_rtp_configure with integer atomics on the device (synchronises): valid packets (ignored ones included),
+ * malformed packets (of the stream stream_of names), valid packets entirely before / entirely after their tick, positions owned
+ * and positions missing (running streams only).
+ *
+ * The unit is the slot's, not the analysers': fx_reset_state and fx_reset_channels do not touch it, fx_export_channels /
+ * fx_import_channels do not carry it.  fx_push_samples, fx_push_interleaved, fx_push_sources, the fx_stream_* ring and the monitor do
+ * not consult it, and a context that never calls fx_rtp_configure makes the launches it always made.
+ * Not here: sockets and the jitter-buffer policy (recvmmsg into pinned slots, multicast joins: the receiver this unit is fed by),
+ * RTCP, SDP, filtering by SSRC or payload type, mixed formats in one context, AM824 / L32, and a fx_stream_* ring form. */
+enum { FX_RTP_L16 = 0, FX_RTP_L24 = 1 };
+enum { FX_RTP_PLACED = 1, FX_RTP_LATE = 2, FX_RTP_EARLY = 4, FX_RTP_MALFORMED = 8, FX_RTP_IGNORED = 16 };
+#define FX_RTP_MAX_STREAMS 65536
+#define FX_RTP_MAX_CHANNELS 64
+#define FX_RTP_MAX_SLOT_STRIDE 65536
+typedef struct fx_rtp_stats {
+    long long packets, malformed, late_packets, early_packets, samples_placed, samples_missing;
+} fx_rtp_stats;
+fx_status fx_rtp_configure(fx_context* ctx, int payload_format, int num_streams, const int* channels /*[num_streams]*/);
+fx_status fx_rtp_set_track_sources(fx_context* ctx, const int* tracks, int num_tracks, const int* stream, const int* channel);
+fx_status fx_rtp_get_track_sources(fx_context* ctx, int* stream /*[num_channels]*/, int* channel /*[num_channels]*/);
+fx_status fx_rtp_set_cursors(fx_context* ctx, const int* streams, int num, const unsigned* rtp_time);
+fx_status fx_rtp_get_cursors(fx_context* ctx, unsigned* rtp_time /*[num_streams]*/, int* running /*[num_streams]*/);
+fx_status fx_push_rtp(fx_context* ctx, const void* packets, const int* lengths, const int* stream_of, int num_packets, int slot_stride,
+                      int num_samples, int mem_kind, float* out_raw, float* out_smoothed, int* frames_out, unsigned char* disposition);
+fx_status fx_rtp_get_block(fx_context* ctx, void* out, size_t capacity_bytes, int* num_samples, int* sample_format, int mem_kind);
+fx_status fx_rtp_get_stats(fx_context* ctx, fx_rtp_stats* out /*[num_streams]*/);
+
 /* ---- file sources: tracks play device-resident clips, transport on the GPU ----
  * In the reference every track listens either to the audio device or to its own AudioFilePlayer, a looping file behind play / pause /
  * stop / restart buttons (AudioFilePlayer.h:41-67, AnalyserTrackController.h:92-138, AudioFileTransportComponent.h:133-179).  Here a

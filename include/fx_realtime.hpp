@@ -209,6 +209,63 @@ public:
     const std::vector<int>& getChannelMap() const { return channelMap; }
     int getHighestSourceChannel() const           { return highestSource; }      // the highest source channel the map reads
 
+    // RTP audio in (fx.h, "RTP audio in"): a tick's L16 / L24 datagrams, as a receiver collected them in slots of one stride, unpacked
+    // to the tracks and analysed on the GPU.  Thin forms of fx_rtp_configure .. fx_rtp_get_stats, host memory; the socket side (which
+    // fills the slots and chooses the streams' first timestamps) is the caller's.
+    void rtpConfigure (int payloadFormat, const std::vector<int>& channelsPerStream)
+    {
+        check (fx_rtp_configure (ctx, payloadFormat, (int) channelsPerStream.size(), channelsPerStream.empty() ? nullptr : channelsPerStream.data()));
+        rtpStreams = (int) channelsPerStream.size();
+    }
+    void setRtpSources (const std::vector<int>& tracks, const std::vector<int>& stream, const std::vector<int>& channel)
+    {
+        if (stream.size() != tracks.size() || channel.size() != tracks.size()) throw Error (FX_ERR_INVALID_ARGUMENT, "one stream and one channel per listed track");
+        check (fx_rtp_set_track_sources (ctx, tracks.data(), (int) tracks.size(), stream.data(), channel.data()));
+    }
+    void rtpSources (std::vector<int>& stream, std::vector<int>& channel) const
+    {
+        stream.resize ((std::size_t) channels); channel.resize ((std::size_t) channels);
+        check (fx_rtp_get_track_sources (ctx, stream.data(), channel.data()));
+    }
+    void setRtpTimestamps (const std::vector<int>& streams, const std::vector<unsigned>& timestamps)
+    {
+        if (timestamps.size() != streams.size()) throw Error (FX_ERR_INVALID_ARGUMENT, "one timestamp per listed stream");
+        check (fx_rtp_set_cursors (ctx, streams.data(), (int) streams.size(), timestamps.data()));
+    }
+    void rtpTimestamps (std::vector<unsigned>& timestamps, std::vector<int>& running) const
+    {
+        timestamps.resize ((std::size_t) rtpStreams); running.resize ((std::size_t) rtpStreams);
+        check (fx_rtp_get_cursors (ctx, timestamps.data(), running.data()));
+    }
+    // one tick of numSamples per track -> the frames analysed; raw / smoothed [channels][frames][12] (null: not wanted), disposition one
+    // byte of FX_RTP_* bits per packet (null: not wanted)
+    int pushRtp (const void* slots, const int* lengths, const int* streamOf, int numPackets, int slotStride, int numSamples,
+                 float* raw, float* smoothed, unsigned char* disposition = nullptr)
+    {
+        int frames = 0;
+        check (fx_push_rtp (ctx, slots, lengths, streamOf, numPackets, slotStride, numSamples, FX_MEM_HOST, raw, smoothed, &frames, disposition));
+        return frames;
+    }
+    // the last tick's planar block [channels][n] as fx_push_samples takes it (FX_SAMPLE_S16 / FX_SAMPLE_S24 bytes) -> n
+    int rtpBlock (std::vector<unsigned char>& block, int* sampleFormat = nullptr)
+    {
+        int n = 0, format = 0;
+        unsigned char none = 0;
+        const fx_status probe = fx_rtp_get_block (ctx, &none, 0, &n, &format, FX_MEM_HOST);      // (no room: refused, the count reported)
+        if (probe != FX_OK && n == 0) check (probe);
+        block.resize ((std::size_t) channels * (std::size_t) n * (format == FX_SAMPLE_S16 ? 2u : 3u));
+        if (n > 0) check (fx_rtp_get_block (ctx, block.data(), block.size(), &n, &format, FX_MEM_HOST));
+        if (sampleFormat != nullptr) *sampleFormat = format;
+        return n;
+    }
+    std::vector<fx_rtp_stats> rtpStats() const
+    {
+        std::vector<fx_rtp_stats> stats ((std::size_t) rtpStreams);       // (not configured: no streams, and the entry says so)
+        if (rtpStreams == 0) throw Error (FX_ERR_INVALID_ARGUMENT, "RTP input is not configured (rtpConfigure)");
+        check (fx_rtp_get_stats (ctx, stats.data()));
+        return stats;
+    }
+
     // The analysers' display buffers (fx_request_taps / fx_get_taps): what RealTimeAudioDataOverlapper, both FFTAnalysers and the
     // PitchAnalyser hand out after their enable...NeedsUpdating flags (RealTimeAudioAnalysis.h:221-232,268-283, PitchAnalyser.h:30-72).
     // requestDisplayBuffers arms every flag of these channels; the next analysis call that analyses a frame captures its first frame.
@@ -335,6 +392,7 @@ private:
     std::vector<int> channelMap;             // [track]: what fx_set_channel_map was last given (the identity by default)
     int highestSource = channels - 1;
     int displayLength = 0;                   // levels per track of the audio display (0: not enabled)
+    int rtpStreams = 0;                      // streams of the RTP unit (0: not configured)
     std::vector<float> latest;
 };
 

@@ -125,11 +125,11 @@ def table(kernels):
     return "\n".join(lines) + "\n"
 
 
-# the kernels DESIGN.md section 3.8 tabulates (the analysis kernels, the onset event list's, the per-track ones and the listeners' copy; the offline analyser's and the byte mover are in the full dump)
+# the kernels DESIGN.md section 3.8 tabulates (the analysis kernels, the onset event list's, the per-track ones, the listeners' copy and the RTP unit's; the offline analyser's and the byte mover are in the full dump)
 DESIGN_PREFIXES = ("fxk::fx_frame_kernel<", "fxk::fx_frame_tail_kernel<", "fxk::fx_pair_kernel<", "fxk::fx_hop_kernel<", "fxk::fx_hop_pair_kernel<",
                    "fxk::fx_finalise_kernel", "fxk::fx_epilogue_kernel", "fxk::fx_history_kernel", "fxk::fx_tail_fused_kernel",
                    "fxk::fx_onset_events_kernel", "fxk::fx_osc_table_kernel", "fxk::fx_osc_bundle_kernel", "fxk::fx_reset_channels_kernel",
-                   "fxk::fx_pack_tracks_kernel", "fxk::fx_unpack_tracks_kernel", "fxk::fx_monitor_listen_kernel")
+                   "fxk::fx_pack_tracks_kernel", "fxk::fx_unpack_tracks_kernel", "fxk::fx_monitor_listen_kernel", "fxk::fx_rtp_")
 
 
 def markdown(kernels):
