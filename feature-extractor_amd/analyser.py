@@ -645,6 +645,20 @@ class BatchAnalyser:
         capi.check(self._lib.fx_rtp_get_stats(self._h, out.ctypes.data_as(ctypes.c_void_p)))
         return {name: out[:, k].copy() for k, name in enumerate(capi.RTP_STATS_FIELDS)}
 
+    def rtp_set_window(self, window):
+        """The reorder window, 0 .. capi.RTP_MAX_WINDOW sample times: what a tick's packets own up to `window` sample times beyond
+        the tick is held on the device for the tick that covers it.  Discards everything held; 0 (where rtp_configure starts): none."""
+        capi.check(self._lib.fx_rtp_set_window(self._h, int(window)))
+
+    def rtp_window(self):
+        """{"window": W, "held": int64 [S], the owned positions each stream holds now, "recovered": int64 [S], the block positions
+        since rtp_configure / rtp_set_window that were owned only through the held state}"""
+        S, _ = self._rtp_streams()
+        w = ctypes.c_int(0)
+        out = np.zeros((S, len(capi.RTP_WINDOW_STATS_FIELDS)), np.int64)
+        capi.check(self._lib.fx_rtp_get_window(self._h, ctypes.byref(w), out.ctypes.data_as(ctypes.c_void_p)))
+        return dict({"window": w.value}, **{name: out[:, k].copy() for k, name in enumerate(capi.RTP_WINDOW_STATS_FIELDS)})
+
     # ---- file sources: tracks play device-resident clips (include/fx.h, fx_create_clips .. fx_push_sources; AudioFilePlayer.h:41-67) ----
     def create_clips(self, samples, lengths=None, sample_format=None, borrow=False, sample_rates=None):
         """A bank of clips in device memory -> the first clip's id (the clips get consecutive ids).  `samples`: the clips back to back

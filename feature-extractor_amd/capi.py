@@ -37,6 +37,10 @@ RTP_L16, RTP_L24 = 0, 1
 RTP_FORMATS = {"l16": RTP_L16, "l24": RTP_L24}
 RTP_PLACED, RTP_LATE, RTP_EARLY, RTP_MALFORMED, RTP_IGNORED = 1, 2, 4, 8, 16
 RTP_STATS_FIELDS = ["packets", "malformed", "late_packets", "early_packets", "samples_placed", "samples_missing"]
+# the reorder window: FX_RTP_HELD, FX_RTP_MAX_WINDOW, struct fx_rtp_window_stats' fields in order
+RTP_HELD = 32
+RTP_MAX_WINDOW = 65536
+RTP_WINDOW_STATS_FIELDS = ["held", "recovered"]
 MONITOR_GROUP = 64                  # FX_MONITOR_GROUP: the tracks whose sends are summed in a row before the groups are
 LISTEN_SELF, LISTEN_LEFT, LISTEN_RIGHT = 0, 1, 2       # FX_LISTEN_*: what a track's analysers hear (fx_set_channel_listen)
 LISTENS = {"self": LISTEN_SELF, "left": LISTEN_LEFT, "right": LISTEN_RIGHT}
@@ -123,7 +127,7 @@ def _prototypes():
         ("fx_rtp_configure", [vp, i, i, ip], st), ("fx_rtp_set_track_sources", [vp, ip, i, ip, ip], st), ("fx_rtp_get_track_sources", [vp, ip, ip], st),
         ("fx_rtp_set_cursors", [vp, ip, i, P(u)], st), ("fx_rtp_get_cursors", [vp, P(u), ip], st),
         ("fx_push_rtp", [vp, vp, ip, ip, i, i, i, i, vp, vp, ip, vp], st), ("fx_rtp_get_block", [vp, vp, ctypes.c_size_t, ip, ip, i], st),
-        ("fx_rtp_get_stats", [vp, vp], st),
+        ("fx_rtp_get_stats", [vp, vp], st), ("fx_rtp_set_window", [vp, i], st), ("fx_rtp_get_window", [vp, ip, vp], st),
         ("fx_create_clips", [vp, vp, llp, i, i, i, u, ip], st), ("fx_destroy_clips", [vp, i], st), ("fx_set_channel_clips", [vp, ip, i, ip, ip], st),
         ("fx_set_clip_rates", [vp, ip, i, dp], st), ("fx_get_resampler_table", [fp, i, ip, ip], st),
         ("fx_set_channel_sources", [vp, ip, i, ip], st), ("fx_transport", [vp, ip, i, i], st), ("fx_get_transport", [vp, ip, ip, llp, llp], st),

@@ -403,6 +403,7 @@ hipError_t launch_hop_kernel(int window_size, const FrameParams& p, const Epilog
 //      calls that complete several hops do
 //   5  a call of two hops per channel runs the batch kernels' two-frame form instead of two one-frame launches
 //   6  fx_export_channels / fx_import_channels move a HOST buffer's records through the device scratch two at a time (default: 32 MB a chunk)
+//   7  the RTP reorder window's tick numbers (fx_rtp.hip: the stamps' upper half) start over after 3 (default: after 2^32 - 1)
 // None changes a result bit (bit 0 makes the call fail, as it must).
 #define FX_HOOK_NO_HANDOVER      1u
 #define FX_HOOK_NO_QUARTER_TURN  2u
@@ -411,6 +412,7 @@ hipError_t launch_hop_kernel(int window_size, const FrameParams& p, const Epilog
 #define FX_HOOK_NO_BLOCK_FEED    16u
 #define FX_HOOK_NO_TWO_LAUNCHES  32u
 #define FX_HOOK_SMALL_TRACK_CHUNKS 64u
+#define FX_HOOK_RTP_FEW_TICK_NUMBERS 128u
 extern "C" fx_status fx_set_tuning_internal(fx_context* ctx, unsigned test_hooks);
 
 // Launch record, NOT part of the public ABI (tests only): the launches the context's last call made -- fx_push_hops, fx_process_frames,

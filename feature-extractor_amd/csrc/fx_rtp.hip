@@ -11,12 +11,29 @@
 // tick's owned and missing positions to the per-stream statistics.  fx_push_block (fx_capi.cpp) does the rest: the same launches, the
 // same bits as fx_push_samples of that planar block.  Integer atomics only: every result is the same at every run.
 //
+// The reorder window (fx_rtp_set_window, W > 0 sample times): a tick works on a span of n + W positions, and what its packets own
+// beyond the tick stays on the device until the tick that covers it.  Per stream the held state is a ring of W sample times of WIRE
+// bytes (stream-interleaved, big-endian, as they arrived: the gather reads a held sample with the load_reversed it uses on a slot) and
+// a 64-bit stamp per ring position: 0 = empty, else (tick number << 32) | (packet index + 1), claimed with atomicMax, so the most
+// recently submitted packet owns a position whatever order the wavefronts run in.  Span position q lives in ring slot
+// (head + q) % W, head moving on by n per tick.  The far end of the span, positions [max(n, W), n + W), has the ring slots of the
+// positions [.., n) this tick consumes: those claims go to a per-tick table behind the owner table (`far`, min(n, W) entries a
+// stream, filled with it), and the order of the launches does the rest --
+//   fill, fx_rtp_parse_span_kernel   claims: [0, n) in the owner table, [n, W) in the stamps, the far end in `far`
+//   fx_rtp_gather_span_kernel        reads the slots and, where no packet of the tick owns a position, the ring
+//   fx_rtp_count_span_kernel         counts, and one thread per consumed ring slot replaces its stamp by the far claim (or 0)
+//   fx_rtp_deposit_kernel            writes the bytes of the held positions the tick's packets own into the ring
+// -- so the gather has read a slot's bytes and the count its stamp before either is overwritten: the ring needs no spare capacity,
+// for any n (n > W: everything held is consumed and the whole carry is new).  With W == 0 a tick takes the path above, unchanged.
+//
 // Nothing in the shim's host units (build.py, HOST_SOURCES) refers to this unit: fx_rtp_configure installs the context's release hook.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "fx_kernels.h"
@@ -57,6 +74,27 @@ struct RtpTick {
     unsigned             advanced;  // samples per stream of the ticks before this one (mod 2^32)
 };
 
+struct RtpHeldRange {       // packet i's span positions beyond the tick, [lo, hi); empty: none (not HELD, or no valid packet of a running stream)
+    int lo, hi;
+};
+enum { WS_HELD = 0, WS_RECOVERED, WS_FIELDS };
+
+struct RtpSpan {            // a tick with a reorder window
+    RtpTick              t;         // t.owner: [S][n], the tick's own positions
+    int*                 far;       // [S][E], E = min(n, W): as owner, for the span positions [max(n, W), n + W)
+    RtpHeldRange*        held;      // [P]
+    unsigned char*       ring;      // the streams' rings of wire bytes
+    const long long*     ring_base; // [S]: the byte at which stream s's ring of W * F bytes starts, a multiple of 4
+    unsigned long long*  stamps;    // [S][W]
+    unsigned long long*  wstats;    // [WS_FIELDS][S]
+    int                  W, E;
+    int                  head;      // span position q has ring slot (head + q) % W
+    unsigned             tick;      // this tick's number, from 1
+};
+
+__device__ __forceinline__ unsigned long long span_stamp(unsigned tick, int i) { return ((unsigned long long) tick << 32) | (unsigned) (i + 1); }
+__device__ __forceinline__ int span_slot(const RtpSpan& p, int q) { return (int) (((unsigned) p.head + (unsigned) q) % (unsigned) p.W); }
+
 struct SlotBytes {
     const unsigned char* at;
     __device__ unsigned operator()(int k) const { return at[k]; }
@@ -93,6 +131,60 @@ fx_rtp_parse_kernel(const RtpTick p)
         }
     }
     if (lane == 0 && p.disposition) p.disposition[i] = (unsigned char) bits;
+}
+
+// The same with a reorder window: the packet is placed in the span of n + W positions and claims each covered position where that
+// part of the span keeps its owners (the unit's header comment).  A position of [n, W) whose stamp was 0 is newly held: counted here;
+// the far end's and the consumed positions' share of `held` is fx_rtp_count_span_kernel's.
+__global__ void __launch_bounds__(256)
+fx_rtp_parse_span_kernel(const RtpSpan w)
+{
+    const RtpTick& p = w.t;
+    const int lane = threadIdx.x & 63, i = (int) blockIdx.x * 4 + (int) (threadIdx.x >> 6);
+    if (i >= p.P) return;
+    const int s = p.stream_of[i], len = p.lengths[i];
+    const RtpStream st = p.streams[s];
+    unsigned long long* stats = p.stats + (size_t) s * ST_FIELDS;
+    fx_rtp_parsed h;
+    unsigned bits;
+    RtpHeldRange keep{0, 0};
+    if (!fx_rtp_parse(SlotBytes{p.slots + (size_t) i * (size_t) p.stride}, len, st.channels * p.B, &h)) {
+        bits = FX_RTP_BIT_MALFORMED;
+        if (lane == 0) atomicAdd(&stats[ST_MALFORMED], 1ull);
+    } else if (!st.running) {
+        bits = FX_RTP_BIT_IGNORED;
+        if (lane == 0) atomicAdd(&stats[ST_PACKETS], 1ull);
+    } else {
+        const fx_rtp_span_placement at = fx_rtp_place_span(h.timestamp, st.origin + p.advanced, h.sample_times, p.n, w.W);
+        bits = at.bits;
+        const int lo = (int) at.lo, hi = (int) at.hi, far0 = p.n > w.W ? p.n : w.W;       // (n + W fits an int: the host saw to it)
+        int* owner = p.owner + (size_t) s * (size_t) p.n;
+        int* far = w.far + (size_t) s * (size_t) w.E;
+        unsigned long long* stamps = w.stamps + (size_t) s * (size_t) w.W;
+        const unsigned long long mine = span_stamp(w.tick, i);
+        int fresh = 0;
+        for (int q = lo + lane; q < hi; q += 64) {
+            if (q < p.n) atomicMax(&owner[q], i);
+            else if (q >= far0) atomicMax(&far[q - far0], i);
+            else fresh += atomicMax(&stamps[span_slot(w, q)], mine) == 0ull;
+        }
+        if (bits & FX_RTP_BIT_HELD) keep = RtpHeldRange{lo > p.n ? lo : p.n, hi};
+        if (p.n < w.W) {                                    // (uniform: only then is there a part [n, W))
+            for (int d = 32; d > 0; d >>= 1) fresh += __shfl_xor(fresh, d);
+            if (lane == 0 && fresh) atomicAdd(&w.wstats[(size_t) WS_HELD * p.S + s], (unsigned long long) fresh);
+        }
+        if (lane == 0) {
+            p.records[i] = RtpRecord{h.payload, at.d0};
+            atomicAdd(&stats[ST_PACKETS], 1ull);
+            const bool in_span = bits & (FX_RTP_BIT_PLACED | FX_RTP_BIT_HELD);
+            if (!in_span && (bits & FX_RTP_BIT_LATE)) atomicAdd(&stats[ST_LATE], 1ull);
+            if (!in_span && (bits & FX_RTP_BIT_EARLY)) atomicAdd(&stats[ST_EARLY], 1ull);
+        }
+    }
+    if (lane == 0) {
+        w.held[i] = keep;
+        if (p.disposition) p.disposition[i] = (unsigned char) bits;
+    }
 }
 
 // The B bytes of a big-endian sample at byte `at` of the slots, as the little-endian sample in the low bytes.  The sample lies inside
@@ -176,11 +268,13 @@ __device__ __forceinline__ void tile_to_rows(const unsigned char* tile, unsigned
 // reads, of every stream its tracks hear, one sample time of one packet: F contiguous bytes where consecutive tracks hear consecutive
 // channels, and the sample time after it four steps later.  The owner and the record are the same address for all lanes of a stream
 // (one request).  The samples go to the tile above and from there to the planar rows.
-template <int B>
-__global__ void __launch_bounds__(PT_THREADS)
-fx_rtp_gather_kernel(const RtpTick p)
+// (One body for both forms of the tick: Span = const RtpSpan* with a reorder window -- a position no packet of the tick owns is then
+// read from the stream's ring where its stamp says it is held -- and nullptr_t without, which is the kernel as it was.)
+template <int B, typename Span>
+__device__ __forceinline__ void rtp_gather(const RtpTick& p, Span w)
 {
     constexpr int ROW = pt_row<B>();
+    constexpr bool WINDOW = !std::is_same<Span, std::nullptr_t>::value;
     __shared__ __attribute__((aligned(16))) unsigned char tile[PT_TRACKS * ROW];
     const int q0 = (int) blockIdx.x * PT_FRAMES;
     const int c0 = (int) blockIdx.y * PT_TRACKS;
@@ -194,6 +288,14 @@ fx_rtp_gather_kernel(const RtpTick p)
             const int F = t.stream >= 0 ? p.streams[t.stream].channels * B : 0;
             const int* owner = p.owner + (size_t) (t.stream >= 0 ? t.stream : 0) * (size_t) p.n + q0;
             const bool heard = t.stream >= 0;
+            [[maybe_unused]] const unsigned long long* stamps = nullptr;     // the stream's stamps and its ring (a 4-byte aligned base)
+            [[maybe_unused]] const unsigned char* ring = nullptr;
+            if constexpr (WINDOW) {
+                if (heard) {
+                    stamps = w->stamps + (size_t) t.stream * (size_t) w->W;
+                    ring = w->ring + w->ring_base[t.stream];
+                }
+            }
             // PT_GROUP positions at a time, each of the three dependent loads (owner, record, sample) for all of them before the next
 #pragma unroll 1
             for (int j0 = 0; j0 < PT_FRAMES / 4; j0 += PT_GROUP) {
@@ -205,12 +307,28 @@ fx_rtp_gather_kernel(const RtpTick p)
                     const int f = wave + 4 * (j0 + g);
                     own[g] = heard && f < nq ? owner[f] : -1;
                 }
+                // (the stamps beside the owners, not behind them: a position's stamp is asked for whether or not a packet owns it)
+                [[maybe_unused]] int slot[PT_GROUP];
+                if constexpr (WINDOW) {
+                    unsigned long long stamp[PT_GROUP];
+#pragma unroll
+                    for (int g = 0; g < PT_GROUP; g++) {
+                        const int f = wave + 4 * (j0 + g);
+                        slot[g] = heard && f < nq && q0 + f < w->W ? span_slot(*w, q0 + f) : -1;
+                        stamp[g] = slot[g] >= 0 ? stamps[slot[g]] : 0ull;
+                    }
+#pragma unroll
+                    for (int g = 0; g < PT_GROUP; g++)
+                        if (own[g] >= 0 || stamp[g] == 0ull) slot[g] = -1;
+                }
 #pragma unroll
                 for (int g = 0; g < PT_GROUP; g++) rec[g] = own[g] >= 0 ? p.records[own[g]] : RtpRecord{0, 0};
 #pragma unroll
                 for (int g = 0; g < PT_GROUP; g++) {
                     const int f = wave + 4 * (j0 + g);
                     v[g] = own[g] >= 0 ? load_reversed<B>(p.slots, (long long) own[g] * p.stride + rec[g].payload + (long long) (q0 + f - rec[g].d0) * F + t.channel * B) : 0u;
+                    if constexpr (WINDOW)
+                        if (slot[g] >= 0) v[g] = load_reversed<B>(ring, (long long) slot[g] * F + t.channel * B);
                 }
 #pragma unroll
                 for (int g = 0; g < PT_GROUP; g++) {
@@ -223,6 +341,20 @@ fx_rtp_gather_kernel(const RtpTick p)
     __syncthreads();
 
     tile_to_rows<B>(tile, p.out, c0, p.C, q0, nq, p.n);
+}
+
+template <int B>
+__global__ void __launch_bounds__(PT_THREADS)
+fx_rtp_gather_kernel(const RtpTick p)
+{
+    rtp_gather<B>(p, nullptr);
+}
+
+template <int B>
+__global__ void __launch_bounds__(PT_THREADS)
+fx_rtp_gather_span_kernel(const RtpSpan w)
+{
+    rtp_gather<B>(w.t, &w);
 }
 
 // Owned and missing positions of the tick, per running stream: workgroup (s, y) steps through the stream's row of the owner table,
@@ -245,6 +377,130 @@ fx_rtp_count_kernel(const RtpTick p)
         atomicAdd(&stats[ST_PLACED], (unsigned long long) owned);
         atomicAdd(&stats[ST_MISSING], (unsigned long long) (seen - owned));
     }
+}
+
+// The count with a reorder window: a position of the tick is owned through a packet of the tick or, failing that, through the held
+// state (recovered).  The thread of a position q < E = min(n, W) is also the only one that touches ring slot (head + q) % W in this
+// launch: it has read the stamp of the position the tick consumes, and leaves the stamp of the far-end position that takes the
+// slot over -- Q = q + W for n < W, else the one Q of [n, n + W) with Q = q modulo W -- or 0.  `held` moves by the difference.
+__global__ void __launch_bounds__(256)
+fx_rtp_count_span_kernel(const RtpSpan w)
+{
+    const RtpTick& p = w.t;
+    const int s = (int) blockIdx.x;
+    if (!p.streams[s].running) return;
+    const int* owner = p.owner + (size_t) s * (size_t) p.n;
+    const int* far = w.far + (size_t) s * (size_t) w.E;
+    unsigned long long* stamps = w.stamps + (size_t) s * (size_t) w.W;
+    int owned = 0, seen = 0, recovered = 0, gained = 0, lost = 0;
+    for (int q0 = (int) blockIdx.y * 256; q0 < p.n; q0 += 256 * (int) gridDim.y) {
+        const int q = q0 + (int) threadIdx.x;
+        const bool in = q < p.n;
+        const bool own = in && owner[q] >= 0;
+        bool was = false, next = false;
+        if (in && q < w.E) {
+            const int at = span_slot(w, q);
+            was = stamps[at] != 0ull;
+            int k = q;
+            if (p.n >= w.W) { k = (q - p.n) % w.W; if (k < 0) k += w.W; }
+            const int i = far[k];
+            next = i >= 0;
+            stamps[at] = next ? span_stamp(w.tick, i) : 0ull;
+        }
+        seen += __popcll(__ballot(in));
+        owned += __popcll(__ballot(own || was));
+        recovered += __popcll(__ballot(was && !own));
+        gained += __popcll(__ballot(next));
+        lost += __popcll(__ballot(was));
+    }
+    if ((threadIdx.x & 63) == 0 && seen) {
+        unsigned long long* stats = p.stats + (size_t) s * ST_FIELDS;
+        atomicAdd(&stats[ST_PLACED], (unsigned long long) owned);
+        atomicAdd(&stats[ST_MISSING], (unsigned long long) (seen - owned));
+        if (recovered) atomicAdd(&w.wstats[(size_t) WS_RECOVERED * p.S + s], (unsigned long long) recovered);
+        if (gained != lost) atomicAdd(&w.wstats[(size_t) WS_HELD * p.S + s], (unsigned long long) (long long) (gained - lost));   // (wraps to the sum)
+    }
+}
+
+// The 4 bytes at byte `at` of the slots (all inside one datagram, so the aligned dwords around them lie inside its slot), first lowest.
+__device__ __forceinline__ unsigned load_shifted(const unsigned char* slots, long long at)
+{
+    const unsigned sh = (unsigned) at & 3u;
+    const unsigned* w = reinterpret_cast<const unsigned*>(slots + (at - sh));
+    const unsigned lo = w[0], hi = sh ? w[1] : 0u;
+    return __builtin_amdgcn_alignbyte(hi, lo, sh);
+}
+
+// Bytes [r0, r1) of stream s's ring (ring slots [r0 / F, r1 / F), which hold the span positions from qa on) from byte `src` of the
+// slots on, by one wavefront; position q's bytes only where packet i owns q.  Lane by lane one aligned dword of the ring: written
+// whole, from the shifted read, where all four bytes lie in the run and packet i owns the (one or two: F >= 2) positions they belong
+// to, else byte by byte -- a neighbouring position may be another packet's, whose wavefront writes its bytes of the same dword.
+__device__ __forceinline__ void deposit_run(const RtpSpan& w, int s, int i, int F, int lane, int r0, int r1, int qa, long long src)
+{
+    const RtpTick& p = w.t;
+    unsigned char* ring = w.ring + w.ring_base[s];
+    const int far0 = p.n > w.W ? p.n : w.W;
+    const unsigned long long mine = span_stamp(w.tick, i);
+    const auto owns = [&](int q) {
+        return q >= far0 ? w.far[(size_t) s * (size_t) w.E + (q - far0)] == i : w.stamps[(size_t) s * (size_t) w.W + span_slot(w, q)] == mine;
+    };
+    const int slot0 = r0 / F;
+    for (int a = (r0 & ~3) + 4 * lane; a < r1; a += 4 * 64) {
+        const int b0 = a > r0 ? a : r0, b1 = a + 4 < r1 ? a + 4 : r1;
+        const int first = b0 / F, last = (b1 - 1) / F;
+        const bool own_first = owns(qa + (first - slot0)), own_last = last == first ? own_first : owns(qa + (last - slot0));
+        if (b1 - b0 == 4 && own_first && own_last) {
+            *reinterpret_cast<unsigned*>(ring + a) = load_shifted(p.slots, src + (a - r0));
+        } else {
+            for (int b = b0; b < b1; b++)
+                if (b / F == first ? own_first : own_last) ring[b] = p.slots[src + (b - r0)];
+        }
+    }
+}
+
+// One wavefront per packet: the span positions beyond the tick that the packet covers are one run of bytes in its slot and one or two
+// in the ring, which wraps at W.  After the gather and the count of the same tick (the unit's header comment).
+__global__ void __launch_bounds__(256)
+fx_rtp_deposit_kernel(const RtpSpan w)
+{
+    const RtpTick& p = w.t;
+    const int lane = threadIdx.x & 63, i = (int) blockIdx.x * 4 + (int) (threadIdx.x >> 6);
+    if (i >= p.P) return;
+    const RtpHeldRange keep = w.held[i];
+    if (keep.lo >= keep.hi) return;
+    const int s = p.stream_of[i], F = p.streams[s].channels * p.B;
+    const RtpRecord rec = p.records[i];
+    const long long src = (long long) i * p.stride + rec.payload + (long long) (keep.lo - rec.d0) * F;
+    const int at = span_slot(w, keep.lo), count = keep.hi - keep.lo;                // count <= W
+    const int head = count < w.W - at ? count : w.W - at;
+    deposit_run(w, s, i, F, lane, at * F, (at + head) * F, keep.lo, src);
+    if (head < count) deposit_run(w, s, i, F, lane, 0, (count - head) * F, keep.lo + head, src + (long long) head * F);
+}
+
+hipError_t launch_rtp_span_kernels(const RtpSpan& w, hipStream_t stream)
+{
+    const RtpTick& p = w.t;
+    const long long gx = ((long long) p.n + PT_FRAMES - 1) / PT_FRAMES, gy = ((long long) p.C + PT_TRACKS - 1) / PT_TRACKS;
+    if (gy > 65535) return hipErrorInvalidValue;
+    // (owner and far are one allocation, [S][n] then [S][E])
+    hipError_t e = hipMemsetAsync(p.owner, 0xff, sizeof(int) * (size_t) p.S * ((size_t) p.n + (size_t) w.E), stream);
+    if (e != hipSuccess) return e;
+    const dim3 packets((unsigned) ((p.P + 3) / 4)), gather((unsigned) gx, (unsigned) gy);
+    const dim3 count((unsigned) p.S, (unsigned) (gx < 16 ? (gx + 3) / 4 : 4));
+    if (p.P > 0) hipLaunchKernelGGL(fx_rtp_parse_span_kernel, packets, dim3(256), 0, stream, w);
+    if (p.B == 2) hipLaunchKernelGGL(fx_rtp_gather_span_kernel<2>, gather, dim3(PT_THREADS), 0, stream, w);
+    else hipLaunchKernelGGL(fx_rtp_gather_span_kernel<3>, gather, dim3(PT_THREADS), 0, stream, w);
+    hipLaunchKernelGGL(fx_rtp_count_span_kernel, count, dim3(256), 0, stream, w);
+    if (p.P > 0) hipLaunchKernelGGL(fx_rtp_deposit_kernel, packets, dim3(256), 0, stream, w);
+    return hipGetLastError();
+}
+
+// Before the tick number would wrap: every held position's stamp becomes the least one, which any later claim beats.
+__global__ void __launch_bounds__(256)
+fx_rtp_rebase_stamps_kernel(unsigned long long* stamps, long long count)
+{
+    const long long k = (long long) blockIdx.x * 256 + threadIdx.x;
+    if (k < count && stamps[k] != 0ull) stamps[k] = 1ull;
 }
 
 hipError_t launch_rtp_kernels(const RtpTick& p, hipStream_t stream)
@@ -284,6 +540,17 @@ struct fx_rtp {
     int*           d_owner = nullptr;
     unsigned char* d_planar = nullptr;          // the planar block handed to fx_push_block
     size_t slots_cap = 0, disposition_cap = 0, records_cap = 0, owner_cap = 0, planar_cap = 0;
+    // the reorder window (fx_rtp_set_window): nothing of it exists while window == 0.  The ring, the stamps and the counters are
+    // allocated there and never by a tick, so no tick's growing buffer can drop what is held.
+    int      window = 0;                        // W
+    int      head = 0;                          // the ring slot of the next tick's position 0
+    unsigned tick_no = 1;                       // the next tick's number in the stamps
+    unsigned char*      d_ring = nullptr;       // every stream's ring: W * channels * B bytes from a 4-byte boundary, 4 bytes of slack behind
+    long long*          d_ring_base = nullptr;  // [S]
+    unsigned long long* d_stamps = nullptr;     // [S][W]
+    unsigned long long* d_wstats = nullptr;     // [2][S]: held, recovered
+    fxk::RtpHeldRange*  d_held = nullptr;       // [P], a tick's scratch
+    size_t held_cap = 0;
 
     int bytes() const { return format == FX_RTP_L16 ? 2 : 3; }
     int sample_format() const { return format == FX_RTP_L16 ? FX_SAMPLE_S16 : FX_SAMPLE_S24; }
@@ -295,7 +562,8 @@ void rtp_release(fx_context* c)
 {
     fx_rtp* s = c->rtp;
     if (!s) return;
-    fx_free_device({s->d_streams, s->d_tracks, s->d_stats, s->d_slots, s->d_disposition, s->d_records, s->d_owner, s->d_planar});
+    fx_free_device({s->d_streams, s->d_tracks, s->d_stats, s->d_slots, s->d_disposition, s->d_records, s->d_owner, s->d_planar,
+                    s->d_ring, s->d_ring_base, s->d_stamps, s->d_wstats, s->d_held});
     for (int k = 0; k < 2; k++) {
         fx_release_list(&s->meta[k]);
         if (s->meta_done[k]) (void) hipEventDestroy(s->meta_done[k]);
@@ -431,6 +699,24 @@ fx_status fx_rtp_set_cursors(fx_context* c, const int* streams, int num, const u
         r.origin = timestamp[i] - s->advanced;
         r.running = 1;
     }
+    if (s->window > 0) {
+        // the listed streams' time base has moved: what they hold goes, run of consecutive streams by run
+        std::vector<int> listed;
+        try {
+            listed.assign(streams, streams + num);
+        } catch (const std::bad_alloc&) {
+            return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
+        }
+        std::sort(listed.begin(), listed.end());
+        for (size_t a = 0; a < listed.size();) {
+            size_t b = a + 1;
+            while (b < listed.size() && listed[b] <= listed[b - 1] + 1) b++;
+            const size_t first = (size_t) listed[a], rows = (size_t) (listed[b - 1] - listed[a] + 1);
+            HIP_TRY(hipMemset(s->d_stamps + first * (size_t) s->window, 0, rows * (size_t) s->window * sizeof(unsigned long long)));
+            HIP_TRY(hipMemset(s->d_wstats + (size_t) fxk::WS_HELD * s->streams.size() + first, 0, rows * sizeof(unsigned long long)));
+            a = b;
+        }
+    }
     return upload_streams(s);
 }
 
@@ -472,6 +758,8 @@ fx_status fx_push_rtp(fx_context* c, const void* packets, const int* lengths, co
     // fx_push_block's own refusals, before anything is launched: a refused call changes nothing
     const int format = s->sample_format(), B = s->bytes();
     { const fx_status rs = fx_block_refusal(c, num_samples, format); if (rs != FX_OK) return rs; }
+    const int W = s->window, E = num_samples < W ? num_samples : W;     // (E: the far end's claims, fxk::RtpSpan)
+    if (W > 0 && num_samples > INT32_MAX - W) return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d samples and a window of %d: the span is too long for one call", num_samples, W);
 
     HIP_TRY(hipSetDevice(c->device));
     { const fx_status es = fx_check_device_error(c); if (es != FX_OK) return es; }
@@ -483,7 +771,8 @@ fx_status fx_push_rtp(fx_context* c, const void* packets, const int* lengths, co
     fx_staged_list& meta = s->meta[s->meta_cur];
     if ((st = fx_reserve_list(c, &meta, 2 * P > 0 ? 2 * P : 1, sizeof(int))) != FX_OK) return st;
     if ((st = fx_grow(&s->d_records, &s->records_cap, (P > 0 ? P : 1) * sizeof(fxk::RtpRecord))) != FX_OK) return st;
-    if ((st = fx_grow(&s->d_owner, &s->owner_cap, sizeof(int) * (size_t) S * (size_t) num_samples)) != FX_OK) return st;
+    if ((st = fx_grow(&s->d_owner, &s->owner_cap, sizeof(int) * (size_t) S * ((size_t) num_samples + (size_t) E))) != FX_OK) return st;
+    if (W > 0 && (st = fx_grow(&s->d_held, &s->held_cap, (P > 0 ? P : 1) * sizeof(fxk::RtpHeldRange))) != FX_OK) return st;
     if ((st = fx_grow(&s->d_planar, &s->planar_cap, (planar_bytes + 15) & ~(size_t) 15)) != FX_OK) return st;
     if (mem_kind == FX_MEM_HOST && P > 0) {
         if ((st = fx_grow(&s->d_slots, &s->slots_cap, slot_bytes)) != FX_OK) return st;
@@ -525,7 +814,32 @@ fx_status fx_push_rtp(fx_context* c, const void* packets, const int* lengths, co
     p.B = B;
     p.advanced = s->advanced;
     if (fx_launch_record* r = note_launch(c, FX_LAUNCH_RTP, 0)) r->T = num_samples;
-    HIP_TRY(fxk::launch_rtp_kernels(p, c->stream));
+    if (W == 0) {
+        HIP_TRY(fxk::launch_rtp_kernels(p, c->stream));
+    } else {
+        // the stamps' tick numbers start over below every later one before they would wrap (FX_HOOK_RTP_FEW_TICK_NUMBERS, tests: after 3)
+        if (s->tick_no >= ((c->test_hooks & FX_HOOK_RTP_FEW_TICK_NUMBERS) ? 4u : UINT32_MAX)) {
+            const long long count = (long long) S * W;
+            hipLaunchKernelGGL(fxk::fx_rtp_rebase_stamps_kernel, dim3((unsigned) ((count + 255) / 256)), dim3(256), 0, c->stream, s->d_stamps, count);
+            HIP_TRY(hipGetLastError());
+            s->tick_no = 1;
+        }
+        fxk::RtpSpan w;
+        w.t = p;
+        w.far = s->d_owner + (size_t) S * (size_t) num_samples;
+        w.held = s->d_held;
+        w.ring = s->d_ring;
+        w.ring_base = s->d_ring_base;
+        w.stamps = s->d_stamps;
+        w.wstats = s->d_wstats;
+        w.W = W;
+        w.E = E;
+        w.head = s->head;
+        w.tick = s->tick_no;
+        HIP_TRY(fxk::launch_rtp_span_kernels(w, c->stream));
+        s->head = (int) (((long long) s->head + num_samples) % W);
+        s->tick_no++;
+    }
     s->advanced += (unsigned) num_samples;              // every running stream's cursor
     s->last_n = num_samples;
     if (P > 0 && mem_kind == FX_MEM_HOST && disposition)
@@ -575,6 +889,82 @@ fx_status fx_rtp_get_stats(fx_context* c, fx_rtp_stats* out)
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out, s->d_stats, sizeof(fx_rtp_stats) * s->streams.size(), hipMemcpyDeviceToHost));
+    return fx_check_device_error(c);
+}
+
+fx_status fx_rtp_set_window(fx_context* c, int window)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    if (window < 0 || window > FX_RTP_MAX_WINDOW)
+        return fx_fail(FX_ERR_INVALID_ARGUMENT, "window %d: a reorder window is 0 (none) to %d sample times", window, FX_RTP_MAX_WINDOW);
+    fx_rtp* s = nullptr;
+    { const fx_status st = rtp_configured(c, &s); if (st != FX_OK) return st; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));           // ticks in flight read and write the held state
+    // the new window's state whole, then the old one goes: a failure leaves the unit as it was
+    unsigned char* ring = nullptr;
+    long long* ring_base = nullptr;
+    unsigned long long *stamps = nullptr, *wstats = nullptr;
+    if (window > 0) {
+        const size_t S = s->streams.size();
+        std::vector<long long> base;
+        try {
+            base.resize(S);
+        } catch (const std::bad_alloc&) {
+            return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
+        }
+        long long ring_bytes = 0;
+        for (size_t k = 0; k < S; k++) {                // each ring from a dword boundary, a dword of slack behind it
+            base[k] = ring_bytes;
+            ring_bytes += (((long long) window * s->streams[k].channels * s->bytes() + 3) & ~3ll) + 4;
+        }
+        const size_t stamp_bytes = sizeof(unsigned long long) * S * (size_t) window, wstats_bytes = sizeof(unsigned long long) * fxk::WS_FIELDS * S;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ring), (size_t) ring_bytes);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ring_base), sizeof(long long) * S);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&stamps), stamp_bytes);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&wstats), wstats_bytes);
+        if (e == hipSuccess) e = hipMemset(ring, 0, (size_t) ring_bytes);
+        if (e == hipSuccess) e = hipMemset(stamps, 0, stamp_bytes);
+        if (e == hipSuccess) e = hipMemset(wstats, 0, wstats_bytes);
+        if (e == hipSuccess) e = hipMemcpy(ring_base, base.data(), sizeof(long long) * S, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            fx_free_device({ring, ring_base, stamps, wstats});
+            return fx_fail(fx_hip_status(e), "allocating a reorder window of %d sample times failed: %s", window, hipGetErrorString(e));
+        }
+    }
+    fx_free_device({s->d_ring, s->d_ring_base, s->d_stamps, s->d_wstats});
+    s->d_ring = ring;
+    s->d_ring_base = ring_base;
+    s->d_stamps = stamps;
+    s->d_wstats = wstats;
+    s->window = window;
+    s->head = 0;
+    s->tick_no = 1;
+    return FX_OK;
+}
+
+fx_status fx_rtp_get_window(fx_context* c, int* window, fx_rtp_window_stats* out)
+{
+    if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
+    fx_rtp* s = nullptr;
+    { const fx_status st = rtp_configured(c, &s); if (st != FX_OK) return st; }
+    if (window) *window = s->window;
+    if (!out) return FX_OK;
+    const size_t S = s->streams.size();
+    if (s->window == 0) {
+        for (size_t k = 0; k < S; k++) out[k] = fx_rtp_window_stats{0, 0};
+        return FX_OK;
+    }
+    std::vector<unsigned long long> got;
+    try {
+        got.resize(fxk::WS_FIELDS * S);
+    } catch (const std::bad_alloc&) {
+        return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(got.data(), s->d_wstats, sizeof(unsigned long long) * got.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < S; k++) out[k] = fx_rtp_window_stats{(long long) got[fxk::WS_HELD * S + k], (long long) got[fxk::WS_RECOVERED * S + k]};
     return fx_check_device_error(c);
 }
 

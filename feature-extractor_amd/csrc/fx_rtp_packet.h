@@ -1,7 +1,7 @@
 // fx_rtp_packet.h -- one RTP datagram with an L16 / L24 payload (RFC 3550 5.1, RFC 3551 4.5.11, RFC 3190), stated once: what makes it
 // malformed, where its payload starts and how many sample times it holds, and where those land in a tick (include/fx.h, fx_push_rtp).
 // Plain host/device functions, in the manner of fx_flux_runs.h and fx_osc_words.h: fx_rtp_parse_kernel (fx_rtp.hip), and the
-// stand-alone host program that holds them to the model (tests/cpp/rtp_packet_host.cpp) include this one statement.
+// stand-alone host programs that hold them to the models (tests/cpp/rtp_packet_host.cpp, rtp_window_host.cpp) include this one statement.
 //
 // A packet is read through `byte(k)`, 0 <= k < len: any callable that returns byte k.  fx_rtp_parse asks for no k at or beyond len,
 // whatever the bytes say, so a datagram that lies about its extension or its padding is refused without a read outside it.
@@ -15,7 +15,7 @@
 #endif
 
 // the disposition bits (FX_RTP_* of include/fx.h; this header stands alone)
-enum { FX_RTP_BIT_PLACED = 1, FX_RTP_BIT_LATE = 2, FX_RTP_BIT_EARLY = 4, FX_RTP_BIT_MALFORMED = 8, FX_RTP_BIT_IGNORED = 16 };
+enum { FX_RTP_BIT_PLACED = 1, FX_RTP_BIT_LATE = 2, FX_RTP_BIT_EARLY = 4, FX_RTP_BIT_MALFORMED = 8, FX_RTP_BIT_IGNORED = 16, FX_RTP_BIT_HELD = 32 };
 
 struct fx_rtp_parsed {
     unsigned timestamp;     // T: the RTP timestamp of the first sample time
@@ -65,6 +65,27 @@ FX_RTP_FN fx_rtp_placement fx_rtp_place(unsigned T, unsigned cursor, int m, int 
     p.hi = end < n ? (int) end : n;
     const unsigned late = FX_RTP_BIT_LATE, early = FX_RTP_BIT_EARLY, placed = FX_RTP_BIT_PLACED;
     p.bits = (p.d0 < 0 ? late : 0u) | (end > n ? early : 0u) | (p.lo < p.hi ? placed : 0u);
+    if (p.lo >= p.hi) p.lo = p.hi = 0;
+    return p;
+}
+
+struct fx_rtp_span_placement {
+    int       d0;           // as fx_rtp_placement
+    long long lo, hi;       // the positions it covers inside the span [0, n + W), [lo, hi); empty unless PLACED or HELD
+    unsigned  bits;         // FX_RTP_BIT_PLACED / HELD / LATE / EARLY
+};
+
+// the same packet against a tick with a reorder window of W sample times (include/fx.h, "the reorder window"): the span is the
+// tick's n positions and the W beyond them.  64-bit ends: neither d0 + m nor n + W overflows.  W == 0 gives fx_rtp_place's bits.
+FX_RTP_FN fx_rtp_span_placement fx_rtp_place_span(unsigned T, unsigned cursor, int m, int n, int W)
+{
+    fx_rtp_span_placement p;
+    p.d0 = (int) (T - cursor);
+    const long long end = (long long) p.d0 + m, span = (long long) n + W;
+    p.lo = p.d0 > 0 ? p.d0 : 0;
+    p.hi = end < span ? end : span;
+    const unsigned late = FX_RTP_BIT_LATE, early = FX_RTP_BIT_EARLY, placed = FX_RTP_BIT_PLACED, held = FX_RTP_BIT_HELD;
+    p.bits = (p.d0 < 0 ? late : 0u) | (end > span ? early : 0u) | (p.lo < p.hi && p.lo < n ? placed : 0u) | (p.lo < p.hi && p.hi > n ? held : 0u);
     if (p.lo >= p.hi) p.lo = p.hi = 0;
     return p;
 }

@@ -52,6 +52,35 @@ def packetise(planar_int, channels_per_stream, samples_per_packet, first_timesta
     return slots_of(packets) + (np.asarray(stream_of, np.int32),)
 
 
+def timestamps_of(slots):
+    """slots uint8 [P][stride] of datagrams with a whole fixed header -> their RTP timestamps, int64 [P]"""
+    s = np.asarray(slots, np.uint8)[:, 4:8].astype(np.int64)
+    return (s[:, 0] << 24) | (s[:, 1] << 16) | (s[:, 2] << 8) | s[:, 3]
+
+
+def arrival_ticks(positions, ahead, samples_per_tick):
+    """The tick in which a receiver submits each packet: the packet's first sample time is `positions[i]` sample times after the
+    first tick's cursor, the network delivers it `ahead[i]` sample times before that moment, and ticks are samples_per_tick long
+    -> int64 [P], never below 0.  With a reorder window W (BatchAnalyser.rtp_set_window) a packet of m sample times that arrives
+    0 .. W - m ahead lies whole in the span of its tick."""
+    at = np.asarray(positions, np.int64) - np.asarray(ahead, np.int64)
+    return np.maximum(at, 0) // int(samples_per_tick)
+
+
+def cut_into_ticks(slots, lengths, stream_of, arrival, num_ticks=None):
+    """One list of packets cut into ticks by an arrival schedule: packet i is submitted in tick arrival[i]
+    -> [(slots, lengths, stream_of)] * num_ticks (None: up to the last arrival), each tick's packets in the order of the list.
+    Reorder a tick's packets by indexing the three arrays alike."""
+    arrival = np.asarray(arrival, np.int64).ravel()
+    slots, lengths, stream_of = np.asarray(slots, np.uint8), np.asarray(lengths, np.int32), np.asarray(stream_of, np.int32)
+    if not (arrival.size == slots.shape[0] == lengths.size == stream_of.size):
+        raise ValueError("one arrival, length and stream per slot")
+    if arrival.size and arrival.min() < 0:
+        raise ValueError("a packet arrives in tick 0 or later")
+    count = int(num_ticks) if num_ticks is not None else (int(arrival.max()) + 1 if arrival.size else 0)
+    return [(slots[arrival == k], lengths[arrival == k], stream_of[arrival == k]) for k in range(count)]
+
+
 def slots_of(packets, stride=None):
     """datagrams (bytes each) -> (slots uint8 [P][stride], lengths int32 [P]); stride None: the longest, rounded up to a multiple of 4
     (at least 12)"""

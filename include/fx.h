@@ -324,13 +324,14 @@ fx_status fx_clear_pending(fx_context* ctx);
  * The unit is the slot's, not the analysers': fx_reset_state and fx_reset_channels do not touch it, fx_export_channels /
  * fx_import_channels do not carry it.  fx_push_samples, fx_push_interleaved, fx_push_sources, the fx_stream_* ring and the monitor do
  * not consult it, and a context that never calls fx_rtp_configure makes the launches it always made.
- * Not here: sockets and the jitter-buffer policy (recvmmsg into pinned slots, multicast joins: the receiver this unit is fed by),
- * RTCP, SDP, filtering by SSRC or payload type, mixed formats in one context, AM824 / L32, and a fx_stream_* ring form. */
+ * Not here: sockets (recvmmsg into pinned slots, multicast joins: the receiver this unit is fed by; what arrives early or out of
+ * order it pushes as it comes, the reorder window below holds it), RTCP, SDP, filtering by SSRC or payload type, mixed formats in one context, AM824 / L32, and a fx_stream_* ring form. */
 enum { FX_RTP_L16 = 0, FX_RTP_L24 = 1 };
-enum { FX_RTP_PLACED = 1, FX_RTP_LATE = 2, FX_RTP_EARLY = 4, FX_RTP_MALFORMED = 8, FX_RTP_IGNORED = 16 };
+enum { FX_RTP_PLACED = 1, FX_RTP_LATE = 2, FX_RTP_EARLY = 4, FX_RTP_MALFORMED = 8, FX_RTP_IGNORED = 16, FX_RTP_HELD = 32 };
 #define FX_RTP_MAX_STREAMS 65536
 #define FX_RTP_MAX_CHANNELS 64
 #define FX_RTP_MAX_SLOT_STRIDE 65536
+#define FX_RTP_MAX_WINDOW 65536            /* sample times: 1.37 s at 48 kHz */
 typedef struct fx_rtp_stats {
     long long packets, malformed, late_packets, early_packets, samples_placed, samples_missing;
 } fx_rtp_stats;
@@ -343,6 +344,50 @@ fx_status fx_push_rtp(fx_context* ctx, const void* packets, const int* lengths, 
                       int num_samples, int mem_kind, float* out_raw, float* out_smoothed, int* frames_out, unsigned char* disposition);
 fx_status fx_rtp_get_block(fx_context* ctx, void* out, size_t capacity_bytes, int* num_samples, int* sample_format, int mem_kind);
 fx_status fx_rtp_get_stats(fx_context* ctx, fx_rtp_stats* out /*[num_streams]*/);
+
+/* ---- the RTP reorder window: early packets held on the GPU until their tick ----
+ * On a network packets arrive ahead of the tick they belong to, and out of order.  With a window of W sample times the unit keeps,
+ * per stream and in device memory, what a tick's packets own up to W sample times beyond the tick, and the tick that covers those
+ * positions hears them: a packet is submitted once, when it arrives, in whichever tick and whatever order.  W = 0, where
+ * fx_rtp_configure starts every unit (a re-configured one included, nothing held), is fx_push_rtp exactly as defined above: the same
+ * launches, disposition bytes and statistics.
+ *
+ *   fx_rtp_set_window  window in 0 .. FX_RTP_MAX_WINDOW (judged before any device use), on a configured unit.  Synchronises the
+ *                      context's stream and discards everything held, also when `window` is the current value.  What the new
+ *                      window needs is allocated before the old state goes: a failure (FX_ERR_OUT_OF_MEMORY) leaves the unit as
+ *                      it was.
+ *   fx_rtp_get_window  the window and, where `out` is not NULL, per stream: `held`, the owned positions the stream holds now, and
+ *                      `recovered`, the block positions, summed over the ticks since fx_rtp_configure or fx_rtp_set_window, that
+ *                      were owned only through the held state.  Synchronises, as fx_rtp_get_stats.
+ *
+ * A tick (fx_push_rtp with n = num_samples > 0) of a running stream s works on a SPAN of n + W positions:
+ *   1. Header validity is rule 1 above, unchanged.
+ *   2. Position q of the span has RTP time cursor + q.  Before the tick's packets are looked at, positions [0, W) carry what the
+ *      unit holds for s from earlier ticks, each either owned, with its wire bytes, or empty; positions [W, n + W) are empty.
+ *   3. A valid packet i of a running stream, d0 = (int32) (T - cursor), m sample times, covers d0 .. d0 + m - 1: LATE if d0 < 0,
+ *      EARLY if d0 + m > n + W, PLACED if any covered position lies in [0, n), HELD if any lies in [n, n + W).  (W = 0: rule 2
+ *      above, and HELD never appears.)  MALFORMED and IGNORED are unchanged; packets of a stream that is not running are never held.
+ *   4. A span position covered by one or more of this tick's valid packets belongs to the one of the greatest index, whose bytes
+ *      replace whatever was held there; every other position keeps what 2. gave it.  The most recently submitted packet owns a
+ *      position: a later tick beats an earlier one, within a tick the greater index wins.
+ *   5. The block is rule 4 above over span positions [0, n): an owned position gives its bytes reversed, whether they came from a
+ *      packet of this tick or from the held state, an empty one zeros.  Span positions [n, n + W) become the held positions
+ *      [0, W) of the next tick, and the cursor moves on by n.  (n > W is legal: everything held is consumed.)
+ *   6. Rule 5 above stands: from the unpack's entry on the tick is fx_push_samples of that block, bit for bit.
+ *   7. fx_rtp_stats: packets and malformed as above, each datagram counted once, in the tick that received it; late_packets /
+ *      early_packets count the valid packets of running streams that have no position in [0, n + W) and are LATE / EARLY;
+ *      samples_placed counts, per tick, the owned positions of [0, n), whichever source they came from, samples_missing the empty.
+ *
+ * fx_rtp_set_cursors discards what the LISTED streams hold (their time base has moved); streams not listed keep theirs.  A tick
+ * with num_samples == 0 stays a no-op: its packets are not looked at.  fx_rtp_set_track_sources does not touch the held state (it
+ * is per stream and holds wire bytes: a track that changes source hears the new stream's held samples from its next tick on), nor
+ * do fx_reset_state, fx_reset_channels, export / import or the other push calls.  A refused tick changes nothing, the held state
+ * included; a failure after samples have moved on leaves the stream as fx_push_samples describes.
+ * So: if no two packets of a stream overlap, and every packet is submitted in some tick whose span covers it whole, the blocks and
+ * all analysis results do not depend on which tick each packet was submitted in, or on the order within a tick. */
+typedef struct fx_rtp_window_stats { long long held, recovered; } fx_rtp_window_stats;
+fx_status fx_rtp_set_window(fx_context* ctx, int window /* 0 .. FX_RTP_MAX_WINDOW sample times */);
+fx_status fx_rtp_get_window(fx_context* ctx, int* window, fx_rtp_window_stats* out /*[num_streams], may be NULL*/);
 
 /* ---- file sources: tracks play device-resident clips, transport on the GPU ----
  * In the reference every track listens either to the audio device or to its own AudioFilePlayer, a looping file behind play / pause /

@@ -265,6 +265,17 @@ public:
         check (fx_rtp_get_stats (ctx, stats.data()));
         return stats;
     }
+    // the reorder window (fx.h, "the RTP reorder window"): what a tick's packets own up to `window` sample times beyond the tick is
+    // held on the device for the tick that covers it, so a packet is pushed once, when it arrives.  Discards everything held; 0: none.
+    void setRtpWindow (int window) { check (fx_rtp_set_window (ctx, window)); }
+    // -> the window; stats (optional): per stream, the positions held now and the block positions recovered from the held state
+    int rtpWindow (std::vector<fx_rtp_window_stats>* stats = nullptr) const
+    {
+        int window = 0;
+        if (stats != nullptr) stats->resize ((std::size_t) rtpStreams);
+        check (fx_rtp_get_window (ctx, &window, stats != nullptr && rtpStreams > 0 ? stats->data() : nullptr));
+        return window;
+    }
 
     // The analysers' display buffers (fx_request_taps / fx_get_taps): what RealTimeAudioDataOverlapper, both FFTAnalysers and the
     // PitchAnalyser hand out after their enable...NeedsUpdating flags (RealTimeAudioAnalysis.h:221-232,268-283, PitchAnalyser.h:30-72).

@@ -1,4 +1,4 @@
-"""What fx_push_rtp costs on one MI355X (writes profiles/rtp_ingest_bench.txt).
+"""What fx_push_rtp costs on one MI355X (writes profiles/rtp_ingest_bench.txt; with --window or --parent, profiles/rtp_window_bench.txt).
 
 Shape: 8192 tracks = 1024 streams x 8 channels, L24, 48-sample packets, ticks of n = 480: 10 240 datagrams of 1164 bytes a tick,
 11.8 MB of payload in and 11.8 MB of planar samples out.  Three calls are timed the same way -- 16 ticks back to back on the
@@ -12,11 +12,22 @@ of the same analysis): differences of whole calls, host side included, not kerne
 
     python tools/rtp_ingest.py [--passes 15] [--out profiles/rtp_ingest_bench.txt]
 
-The difference of two whole calls is not the time of the unpack's launches themselves.  Those come from a kernel trace, in a run of
-its own (the trace slows the host side), read back by --kernels:
+The reorder window (fx_rtp_set_window).  --window W[,W..] adds, per W, the call
+  rtp_wW       fx_push_rtp with a window of W sample times: the same datagrams, each delivered 0 .. W - 48 sample times ahead of its
+               own sample time by a seeded draw (feature-extractor_amd/rtp.py, arrival_ticks / cut_into_ticks), so a tick's slots hold
+               what arrived during it, part of it for later ticks; the pass's last block must be the planar block, nothing missing
+and --parent FILE adds
+  rtp_parent   the `rtp` call on the library FILE, a build of the parent commit, loaded beside this one: the W = 0 tick must lie
+               inside that call's own spread (the window adds one host test to it and no launch)
+to the alternated passes (`interleaved` is left out).
 
-    rocprofv3 --kernel-trace -d DIR -o rtp -- python tools/rtp_ingest.py --passes 3 --out /dev/null
-    python tools/rtp_ingest.py --kernels DIR/rtp_results.db        (appends to --out)
+    python tools/rtp_ingest.py --window 480,4800 --parent PARENT/libfx_hip.so [--out profiles/rtp_window_bench.txt]
+
+The difference of two whole calls is not the time of the unpack's launches themselves.  Those come from a kernel trace, in a run of
+its own (the trace slows the host side), read back by --kernels; --only NAME runs that one call alone:
+
+    rocprofv3 --kernel-trace -d DIR -o rtp -- python tools/rtp_ingest.py --passes 3 --out /dev/null [--window 480 --only rtp_w480]
+    python tools/rtp_ingest.py --kernels DIR/rtp_results.db [--label TEXT]       (appends to --out)
 """
 import argparse
 import ctypes
@@ -34,7 +45,7 @@ sys.path.insert(0, ROOT)
 STREAMS, PER, N_TICK, PACKET, WINDOW, TICKS = 1024, 8, 480, 48, 1024, 16
 
 
-def kernels(db_path, out):
+def kernels(db_path, out, label):
     """per-kernel medians of a traced run (rocprofv3's results database), and the span of a tick's unpack on the device"""
     import sqlite3
     rows = sqlite3.connect(db_path).execute("select name, start, end from kernels order by start").fetchall()
@@ -42,31 +53,50 @@ def kernels(db_path, out):
     by_name, spans = {}, []
     for i, (name, a, b) in enumerate(rows):
         by_name.setdefault(short(name), []).append((b - a) / 1000.0)
-        if "fx_rtp_parse_kernel" in name:                 # a tick's unpack: from the owner table's fill to the end of the count
-            k = next(j for j in range(i, len(rows)) if "fx_rtp_count_kernel" in rows[j][0])
+        if "fx_rtp_parse" in name:                        # a tick's unpack: from the owner table's fill to the end of its last launch
+            last = "fx_rtp_deposit_kernel" if "span" in name else "fx_rtp_count_kernel"
+            k = next(j for j in range(i, len(rows)) if last in rows[j][0])
             fills = [(rows[i - 1][2] - rows[i - 1][1]) / 1000.0]
             by_name.setdefault("owner table fill (the fill before each parse)", []).extend(fills)
             spans.append((rows[k][2] - rows[i - 1][1]) / 1000.0)
-    lines = ["", "kernel trace of the same shape (python tools/rtp_ingest.py --kernels): us, median (min - max) of n dispatches"]
+    lines = ["", "kernel trace of %s (python tools/rtp_ingest.py --kernels): us, median (min - max) of n dispatches" % (label or "the same shape")]
     for name in sorted(by_name):
         if "rtp" in name or "deinterleave" in name or "owner table" in name:
             v = by_name[name]
             lines.append("  %-50s %7.1f (%.1f - %.1f) of %d" % (name, statistics.median(v), min(v), max(v), len(v)))
-    lines.append("  %-50s %7.1f (%.1f - %.1f) of %d" % ("a tick's unpack, fill start to count end", statistics.median(spans), min(spans), max(spans), len(spans)))
+    lines.append("  %-50s %7.1f (%.1f - %.1f) of %d" % ("a tick's unpack, fill start to last launch's end", statistics.median(spans), min(spans), max(spans), len(spans)))
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     with open(out, "a") as f:
         f.write(text)
 
 
+def other_library(capi, path):
+    """a second build of the library beside the package's own, with the prototypes of the entries it has"""
+    lib = ctypes.CDLL(path)
+    for name, argtypes, restype in capi.PROTOTYPES + capi.INTERNAL_PROTOTYPES:
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, restype
+    return lib
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--passes", type=int, default=15)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rtp_ingest_bench.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--kernels", default=None, help="a traced run's rocprofv3 results database: append its kernel times to --out")
+    ap.add_argument("--label", default=None, help="with --kernels: what the traced run was")
+    ap.add_argument("--window", default="", help="reorder windows to time, sample times, comma-separated")
+    ap.add_argument("--parent", default=None, help="a build of the parent commit's library: its rtp call joins the alternated passes")
+    ap.add_argument("--only", default=None, help="run this one call alone (a traced run)")
+    ap.add_argument("--seed", type=int, default=0, help="of the arrival schedule's draw")
     args = ap.parse_args()
+    windows = [int(w) for w in args.window.split(",") if w]
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "rtp_window_bench.txt" if windows or args.parent else "rtp_ingest_bench.txt")
     if args.kernels:
-        kernels(args.kernels, args.out)
+        kernels(args.kernels, args.out, args.label)
         return
     import torch
     fx = importlib.import_module("feature-extractor_amd")
@@ -77,77 +107,128 @@ def main():
     slots, lengths, stream_of = fx.rtp.packetise(x, [PER] * STREAMS, PACKET, 0)
     P, stride = slots.shape
     # the same datagrams for every tick of a pass, their timestamps moved on by n per tick
-    stamps = np.array([int.from_bytes(bytes(slots[i, 4:8]), "big") for i in range(P)], np.int64)
-    ticks = []
-    for k in range(TICKS):
-        s = slots.copy()
-        s[:, 4:8] = np.frombuffer((stamps + k * N_TICK).astype(">u4").tobytes(), np.uint8).reshape(P, 4)
-        ticks.append(torch.from_numpy(s).cuda())
+    stamps = fx.rtp.timestamps_of(slots)
+    restamped = lambda k: np.frombuffer((stamps + k * N_TICK).astype(">u4").tobytes(), np.uint8).reshape(P, 4)
+    ip = ctypes.POINTER(ctypes.c_int)
+    names = ["rtp"] + (["rtp_parent"] if args.parent else []) + ["planar"] + ([] if windows or args.parent else ["interleaved"]) + ["rtp_w%d" % w for w in windows]
+    if args.only:
+        if args.only not in names:
+            raise SystemExit("--only: one of %s" % ", ".join(names))
+        names = [args.only]
+    ticks = {}                                            # per call: [(slots on the device, lengths, stream_of, P)] * TICKS
+    if any(n in names for n in ("rtp", "rtp_parent")):
+        on_time = []
+        for k in range(TICKS):
+            s = slots.copy()
+            s[:, 4:8] = restamped(k)
+            on_time.append((torch.from_numpy(s).cuda(), lengths, stream_of, P))
+        ticks["rtp"] = ticks["rtp_parent"] = on_time
+    for w in windows:
+        if "rtp_w%d" % w not in names:
+            continue
+        # a pass's datagrams as one list, in time order, each submitted in the tick during which it arrives
+        everything = np.concatenate([slots] * TICKS)
+        everything[:, 4:8] = np.concatenate([restamped(k) for k in range(TICKS)])
+        position = np.concatenate([stamps + k * N_TICK for k in range(TICKS)])
+        ahead = np.random.default_rng(args.seed).integers(0, max(w - PACKET, 0) + 1, position.size)
+        arrival = fx.rtp.arrival_ticks(position, ahead, N_TICK)
+        cut = fx.rtp.cut_into_ticks(everything, np.tile(lengths, TICKS), np.tile(stream_of, TICKS), arrival, TICKS)
+        ticks["rtp_w%d" % w] = [(torch.from_numpy(np.ascontiguousarray(s)).cuda(), np.ascontiguousarray(l), np.ascontiguousarray(o), len(l)) for s, l, o in cut]
+        del everything
     planar = torch.from_numpy(np.ascontiguousarray(fx.rtp.big_endian_bytes(x, 3)[:, :, ::-1]).reshape(C, 3 * N_TICK)).cuda()
     inter = torch.from_numpy(np.ascontiguousarray(fx.rtp.big_endian_bytes(x, 3)[:, :, ::-1].transpose(1, 0, 2)).reshape(N_TICK, 3 * C)).cuda()
     raw = torch.empty((C, 2, 12), dtype=torch.float32, device="cuda")
     sm = torch.empty((C, 2, 12), dtype=torch.float32, device="cuda")
-    ip = ctypes.POINTER(ctypes.c_int)
-    ln, so = lengths.ctypes.data_as(ip), stream_of.ctypes.data_as(ip)
     vp = lambda t: ctypes.c_void_p(t.data_ptr())
     frames = ctypes.c_int(0)
 
-    def analyser(rtp):
-        an = fx.BatchAnalyser(C, WINDOW)
-        if rtp:
+    def analyser(name):
+        """(the analyser, the library its calls go to)"""
+        its = other_library(capi, args.parent) if name == "rtp_parent" else lib
+        kept, capi._lib = capi._lib, its                  # (a BatchAnalyser keeps the library it was made with)
+        try:
+            an = fx.BatchAnalyser(C, WINDOW)
+        finally:
+            capi._lib = kept
+        if name.startswith("rtp"):
             an.rtp_configure("l24", [PER] * STREAMS)
             an.set_rtp_sources(np.arange(C), np.arange(C) // PER, np.arange(C) % PER)
-        return an
+            if name.startswith("rtp_w"):
+                an.rtp_set_window(int(name[5:]))
+        return an, its
 
-    ans = {"rtp": analyser(True), "planar": analyser(False), "interleaved": analyser(False)}
+    ans = {name: analyser(name) for name in names}
 
     def one_pass(name):
-        an = ans[name]
+        an, its = ans[name]
         an.reset_state()
-        if name == "rtp":
+        if name.startswith("rtp"):
             an.set_rtp_timestamps(np.arange(STREAMS), 0)
         an.sync()
         t0 = time.perf_counter()
         for k in range(TICKS):
-            if name == "rtp":
-                st = lib.fx_push_rtp(an._h, vp(ticks[k]), ln, so, P, stride, N_TICK, capi.MEM_DEVICE, vp(raw), vp(sm), ctypes.byref(frames), None)
+            if name.startswith("rtp"):
+                d, ln, so, count = ticks[name][k]
+                st = its.fx_push_rtp(an._h, vp(d) if count else None, ln.ctypes.data_as(ip), so.ctypes.data_as(ip), count, stride, N_TICK, capi.MEM_DEVICE, vp(raw), vp(sm), ctypes.byref(frames), None)
             elif name == "planar":
-                st = lib.fx_push_samples(an._h, vp(planar), N_TICK, capi.SAMPLE_S24, capi.MEM_DEVICE, vp(raw), vp(sm), ctypes.byref(frames))
+                st = its.fx_push_samples(an._h, vp(planar), N_TICK, capi.SAMPLE_S24, capi.MEM_DEVICE, vp(raw), vp(sm), ctypes.byref(frames))
             else:
-                st = lib.fx_push_interleaved(an._h, vp(inter), N_TICK, C, capi.SAMPLE_S24, capi.MEM_DEVICE, vp(raw), vp(sm), ctypes.byref(frames))
-            capi.check(st)
+                st = its.fx_push_interleaved(an._h, vp(inter), N_TICK, C, capi.SAMPLE_S24, capi.MEM_DEVICE, vp(raw), vp(sm), ctypes.byref(frames))
+            if st != capi.FX_OK:
+                raise capi.FxError(st, its.fx_last_error().decode(errors="replace"))
         an.sync()
         return (time.perf_counter() - t0) / TICKS * 1e6
 
     torch.cuda.synchronize()
-    # the unpack is right before it is timed: the block of the last tick of a pass is the planar block
-    one_pass("rtp")
-    assert ans["rtp"].rtp_block().tobytes() == planar.cpu().numpy().tobytes(), "the unpacked block is not the planar block"
-    stats = ans["rtp"].rtp_stats()
-    assert int(stats["samples_missing"].sum()) == 0 and int(stats["packets"].sum()) == P * TICKS
-    for name in ans:                                    # warm-up
+    # the unpack is right before it is timed: the block of the last tick of a pass is the planar block, and nothing is missing
+    notes = []
+    for name in names:
+        if not name.startswith("rtp"):
+            continue
         one_pass(name)
-    times = {name: [] for name in ans}
+        an = ans[name][0]
+        assert an.rtp_block().tobytes() == planar.cpu().numpy().tobytes(), "%s: the unpacked block is not the planar block" % name
+        stats = an.rtp_stats()
+        assert int(stats["samples_missing"].sum()) == 0 and int(stats["packets"].sum()) == P * TICKS, name
+        if name.startswith("rtp_w"):
+            w = an.rtp_window()
+            counts = [t[3] for t in ticks[name]]
+            assert int(w["held"].sum()) == 0 and int(w["recovered"].sum()) > 0
+            notes.append("  %s: datagrams per tick %d .. %d (first %d, last %d); %.1f %% of a pass's positions came out of the held state"
+                         % (name, min(counts), max(counts), counts[0], counts[-1], 100.0 * int(w["recovered"].sum()) / (STREAMS * N_TICK * TICKS)))
+    for name in names:                                    # warm-up
+        one_pass(name)
+    times = {name: [] for name in names}
     for _ in range(args.passes):
-        for name in ans:                                # alternated
+        for name in names:                                # alternated
             times[name].append(one_pass(name))
     med = {k: statistics.median(v) for k, v in times.items()}
     lines = ["fx_push_rtp on one MI355X (tools/rtp_ingest.py): %d tracks = %d streams x %d channels, L24, %d-sample packets, n = %d:" % (C, STREAMS, PER, PACKET, N_TICK),
              "%d datagrams of %d bytes (slot stride %d) a tick; %d-point context; %d ticks back to back per pass on the library's stream, device" % (P, int(lengths[0]), stride, WINDOW, TICKS),
-             "buffers, one synchronisation per pass, the three calls' passes alternated, %d passes each; us per tick, median (min - max):" % args.passes]
-    for name in ("rtp", "planar", "interleaved"):
+             "buffers, one synchronisation per pass, the calls' passes alternated, %d passes each; us per tick, median (min - max):" % args.passes]
+    for name in names:
         lines.append("  %-12s %8.1f (%.1f - %.1f)" % (name, med[name], min(times[name]), max(times[name])))
-    unpack = [a - b for a, b in zip(times["rtp"], times["planar"])]
-    deint = [a - b for a, b in zip(times["interleaved"], times["planar"])]
-    mu, md = statistics.median(unpack), statistics.median(deint)
-    lines += ["  what the unpack adds (rtp - planar, pass by pass):              %8.1f (%.1f - %.1f)" % (mu, min(unpack), max(unpack)),
-              "  what the de-interleave adds (interleaved - planar, pass by pass): %8.1f (%.1f - %.1f)" % (md, min(deint), max(deint)),
-              "  ratio of the two: %.2f   whole tick rtp / planar: %.3f" % (mu / md if md > 0 else float("nan"), med["rtp"] / med["planar"])]
+    pairs = [("what the unpack adds (rtp - planar, pass by pass):", "rtp", "planar"),
+             ("what the de-interleave adds (interleaved - planar, pass by pass):", "interleaved", "planar"),
+             ("this build less the parent's (rtp - rtp_parent, pass by pass):", "rtp", "rtp_parent")]
+    pairs += [("what a window of %d adds (rtp_w%d - rtp, pass by pass):" % (w, w), "rtp_w%d" % w, "rtp") for w in windows]
+    diff = {}
+    for what, a, b in pairs:
+        if a in times and b in times:
+            d = [u - v for u, v in zip(times[a], times[b])]
+            diff[(a, b)] = statistics.median(d)
+            lines.append("  %-66s %8.1f (%.1f - %.1f)" % (what, diff[(a, b)], min(d), max(d)))
+    if ("interleaved", "planar") in diff and diff[("interleaved", "planar")] > 0:
+        lines.append("  ratio of the two: %.2f   whole tick rtp / planar: %.3f" % (diff[("rtp", "planar")] / diff[("interleaved", "planar")], med["rtp"] / med["planar"]))
+    if "rtp_parent" in times and "rtp" in times:
+        lo, hi = min(times["rtp_parent"]), max(times["rtp_parent"])
+        lines.append("  W = 0 gate: this build's rtp median %.1f %s the parent's own spread %.1f - %.1f" % (med["rtp"], "lies inside" if lo <= med["rtp"] <= hi else "lies OUTSIDE", lo, hi))
+    lines += notes
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     with open(args.out, "w") as f:
         f.write(text)
-    for an in ans.values():
+    for an, _ in ans.values():
         an.close()
 
 
