@@ -36,7 +36,7 @@ UNITS = [("fx_kernels.hip", "fx_kernels_small.o", ["-DFX_PART=1", "-mllvm", "-am
          ("fx_clips.hip", "fx_clips.o", []),
          ("fx_monitor.hip", "fx_monitor.o", []),
          ("fx_rtp.hip", "fx_rtp.o", [])] + [(s, s.replace(".cpp", ".o"), []) for s in HOST_SOURCES]
-HEADERS = ["fx_kernels.h", "fx_context.h", "fx_offline_frames.h", "fx_offline_object.h", "fx_plan.h", "fx_osc_words.h", "fx_wave.hip.h", "fx_lane_exchange.h", "fx_lane_consts.hip.h", "fx_flux_runs.h", "fx_fft.hip.h", "fx_plain_fft.hip.h", "fx_offline_frame_body.hip.h", "fx_offline_steps.hip.h", "fx_samples.hip.h", "fx_blocks.hip.h", "fx_rtp_packet.h", "fx_frame_kernel.hip.h", "fx_pair_kernel.hip.h", "fx_tail_kernels.hip.h", "fx_hop_kernel.hip.h",
+HEADERS = ["fx_kernels.h", "fx_context.h", "fx_offline_frames.h", "fx_offline_object.h", "fx_plan.h", "fx_osc_words.h", "fx_wave.hip.h", "fx_lane_exchange.h", "fx_lane_consts.hip.h", "fx_flux_runs.h", "fx_fft.hip.h", "fx_plain_fft.hip.h", "fx_offline_frame_body.hip.h", "fx_offline_steps.hip.h", "fx_samples.hip.h", "fx_blocks.hip.h", "fx_rtp_packet.h", "fx_planar_tile.hip.h", "fx_frame_kernel.hip.h", "fx_pair_kernel.hip.h", "fx_tail_kernels.hip.h", "fx_hop_kernel.hip.h",
            os.path.join("..", "..", "include", "fx.h")]
 
 # -ffp-contract=off : the reference FFT never fuses a*b+c; spectra must be bit-identical.

@@ -17,20 +17,10 @@
 
 #include "fx_kernels.h"
 #include "fx_context.h"
+#include "fx_planar_tile.hip.h"
 
 namespace fxk {
 namespace {
-
-// A workgroup takes DI_FRAMES frames of DI_TRACKS consecutive tracks.  Load: lane = track, wavefront = frame, so a wavefront reads
-// samples[f][map[c0 .. c0 + 63]] -- one contiguous run of 64 samples for the identity map or any map of consecutive sources.  The tile
-// goes to LDS as rows of tracks, each row placed at the byte its planar destination has modulo 16, so that the store reads whole
-// 16-byte chunks back (ds_read_b128) and writes them to 16-byte aligned addresses (global_store_dwordx4), consecutive lanes along a
-// row and on into the next one.  Only the first and last chunk of a row's segment are partial: they are written byte by byte, each
-// byte once, whatever the row pitch n * B makes of the alignment.
-// TWIN: fx_rtp.hip's gather restates this tile (tile_at, store_sample, pick, the store stage below as tile_to_rows): a change to the
-// layout or the drain here belongs there too.
-constexpr int DI_FRAMES = 64, DI_TRACKS = 64, DI_THREADS = 256;
-static_assert(DI_THREADS == 4 * 64 && DI_TRACKS == 64, "lane = track, four wavefronts step through the frames");
 
 struct DeinterleaveParams {
     const unsigned char* in;    // [n][K] samples of B bytes
@@ -40,14 +30,6 @@ struct DeinterleaveParams {
     int                  K, C;
 };
 
-// Byte `col` of tile row r: chunks of 16 bytes in order, the four dwords of a chunk rotated by (r / 8) % 4.  Row pitches of a whole
-// number of chunks put rows r and r + 8 on the same banks; the rotation moves them apart, so the load stage's stores (32 lanes = 32
-// rows at one column) fall on 32 distinct banks.  The store stage's reads of whole chunks are not affected.
-__device__ __forceinline__ int tile_at(int r, int row_bytes, int col)
-{
-    return r * row_bytes + (col & ~15) + ((((col >> 2) + (r >> 3)) & 3) << 2) + (col & 3);
-}
-
 template <int B> __device__ __forceinline__ unsigned load_sample(const unsigned char* p)
 {
     if constexpr (B == 4) return *reinterpret_cast<const unsigned*>(p);
@@ -55,33 +37,19 @@ template <int B> __device__ __forceinline__ unsigned load_sample(const unsigned 
     else return (unsigned) p[0] | ((unsigned) p[1] << 8) | ((unsigned) p[2] << 16);
 }
 
-// (a row's offset modulo 16 is a multiple of B's alignment for 2- and 4-byte samples: those never straddle a dword of the tile)
-template <int B> __device__ __forceinline__ void store_sample(unsigned char* tile, int r, int row_bytes, int col, unsigned v)
-{
-    if constexpr (B == 4) *reinterpret_cast<unsigned*>(tile + tile_at(r, row_bytes, col)) = v;
-    else if constexpr (B == 2) *reinterpret_cast<unsigned short*>(tile + tile_at(r, row_bytes, col)) = (unsigned short) v;
-    else {
-#pragma unroll
-        for (int i = 0; i < 3; i++) tile[tile_at(r, row_bytes, col + i)] = (unsigned char) (v >> (8 * i));
-    }
-}
-
-__device__ __forceinline__ unsigned pick(const uint4& q, int j)
-{
-    j &= 3;
-    return j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w;
-}
-
+// A workgroup takes PT_FRAMES frames of PT_TRACKS consecutive tracks.  Load: lane = track, wavefront = frame, so a wavefront reads
+// samples[f][map[c0 .. c0 + 63]] -- one contiguous run of 64 samples for the identity map or any map of consecutive sources.  The
+// samples go to the tile of fx_planar_tile.hip.h, each row at the byte its planar destination has modulo 16, and from there to the
+// planar rows.
 template <int B>
-__global__ void __launch_bounds__(DI_THREADS)
+__global__ void __launch_bounds__(PT_THREADS)
 fx_deinterleave_kernel(const DeinterleaveParams p)
 {
-    constexpr int CHUNKS = DI_FRAMES * B / 16 + 1;      // a row's segment of DI_FRAMES * B bytes, placed at its offset modulo 16
-    constexpr int ROW = 16 * CHUNKS;
-    __shared__ __attribute__((aligned(16))) unsigned char tile[DI_TRACKS * ROW];
-    const long long f0 = (long long) blockIdx.x * DI_FRAMES;
-    const int c0 = (int) blockIdx.y * DI_TRACKS;
-    const int nf = p.n - f0 < DI_FRAMES ? (int) (p.n - f0) : DI_FRAMES;
+    constexpr int ROW = pt_row_bytes(B);
+    __shared__ __attribute__((aligned(16))) unsigned char tile[PT_TRACKS * ROW];
+    const long long f0 = (long long) blockIdx.x * PT_FRAMES;
+    const int c0 = (int) blockIdx.y * PT_TRACKS;
+    const int nf = p.n - f0 < PT_FRAMES ? (int) (p.n - f0) : PT_FRAMES;
     const long long row_bytes = p.n * B;
 
     {
@@ -90,14 +58,14 @@ fx_deinterleave_kernel(const DeinterleaveParams p)
             const int m = (int) (((long long) c * row_bytes + f0 * B) & 15);
             const unsigned char* src = p.in + (f0 * p.K + p.map[c]) * B;
             const long long pitch = (long long) p.K * B;
-            unsigned v[DI_FRAMES / 4];
+            unsigned v[PT_FRAMES / 4];
 #pragma unroll
-            for (int j = 0; j < DI_FRAMES / 4; j++) {
+            for (int j = 0; j < PT_FRAMES / 4; j++) {
                 const int f = wave + 4 * j;
                 if (f < nf) v[j] = load_sample<B>(src + f * pitch);
             }
 #pragma unroll
-            for (int j = 0; j < DI_FRAMES / 4; j++) {
+            for (int j = 0; j < PT_FRAMES / 4; j++) {
                 const int f = wave + 4 * j;
                 if (f < nf) store_sample<B>(tile, lane, ROW, m + f * B, v[j]);
             }
@@ -105,31 +73,15 @@ fx_deinterleave_kernel(const DeinterleaveParams p)
     }
     __syncthreads();
 
-    for (int i = threadIdx.x; i < DI_TRACKS * CHUNKS; i += DI_THREADS) {
-        const int r = i / CHUNKS, k = i - r * CHUNKS, c = c0 + r;
-        if (c >= p.C) break;                                // (r only grows with i)
-        const long long seg = (long long) c * row_bytes + f0 * B;
-        const int m = (int) (seg & 15);
-        const int lo = m > 16 * k ? m : 16 * k, hi = m + nf * B < 16 * k + 16 ? m + nf * B : 16 * k + 16;
-        if (lo >= hi) continue;
-        const uint4 s = *reinterpret_cast<const uint4*>(tile + r * ROW + 16 * k);
-        const int rot = r >> 3;
-        const uint4 q{pick(s, rot), pick(s, rot + 1), pick(s, rot + 2), pick(s, rot + 3)};
-        unsigned char* dst = p.out + (seg - m) + 16 * k;
-        if (hi - lo == 16) {
-            *reinterpret_cast<uint4*>(dst) = q;
-        } else {
-            for (int b = lo - 16 * k; b < hi - 16 * k; b++) dst[b] = (unsigned char) (pick(q, b >> 2) >> (8 * (b & 3)));
-        }
-    }
+    tile_to_rows<B>(tile, p.out, c0, p.C, row_bytes, f0 * B, nf);
 }
 
 hipError_t launch_deinterleave_kernel(const DeinterleaveParams& p, int bytes_per_sample, hipStream_t stream)
 {
     if (p.n <= 0 || p.C <= 0) return hipSuccess;
-    const long long gx = (p.n + DI_FRAMES - 1) / DI_FRAMES, gy = ((long long) p.C + DI_TRACKS - 1) / DI_TRACKS;
+    const long long gx = (p.n + PT_FRAMES - 1) / PT_FRAMES, gy = ((long long) p.C + PT_TRACKS - 1) / PT_TRACKS;
     if (gx > 0x7fffffffll || gy > 65535) return hipErrorInvalidValue;
-    const dim3 grid((unsigned) gx, (unsigned) gy), block(DI_THREADS);
+    const dim3 grid((unsigned) gx, (unsigned) gy), block(PT_THREADS);
     switch (bytes_per_sample) {
         case 4: hipLaunchKernelGGL(fx_deinterleave_kernel<4>, grid, block, 0, stream, p); break;
         case 3: hipLaunchKernelGGL(fx_deinterleave_kernel<3>, grid, block, 0, stream, p); break;

@@ -39,6 +39,7 @@
 #include "fx_kernels.h"
 #include "fx_context.h"
 #include "fx_rtp_packet.h"
+#include "fx_planar_tile.hip.h"
 
 namespace fxk {
 
@@ -102,9 +103,14 @@ struct SlotBytes {
 
 // One wavefront per packet.  Every lane forms the same few values from the same header bytes (uniform loads); the lanes then spread
 // along the positions the packet covers.  Lane 0 leaves the record, the disposition and the packet's counts.
-__global__ void __launch_bounds__(256)
-fx_rtp_parse_kernel(const RtpTick p)
+// (One body for both forms of the tick, as rtp_gather below: Span = nullptr_t without a reorder window, const RtpSpan* with one.  The
+// packet is then placed in the span of n + W positions and claims each covered position where that part of the span keeps its owners
+// (the unit's header comment).  A position of [n, W) whose stamp was 0 is newly held: counted here; the far end's and the consumed
+// positions' share of `held` is the count's.)
+template <typename Span>
+__device__ __forceinline__ void rtp_parse(const RtpTick& p, Span w)
 {
+    constexpr bool WINDOW = !std::is_same<Span, std::nullptr_t>::value;
     const int lane = threadIdx.x & 63, i = (int) blockIdx.x * 4 + (int) (threadIdx.x >> 6);
     if (i >= p.P) return;
     const int s = p.stream_of[i], len = p.lengths[i];
@@ -112,6 +118,7 @@ fx_rtp_parse_kernel(const RtpTick p)
     unsigned long long* stats = p.stats + (size_t) s * ST_FIELDS;
     fx_rtp_parsed h;
     unsigned bits;
+    [[maybe_unused]] RtpHeldRange keep{0, 0};
     if (!fx_rtp_parse(SlotBytes{p.slots + (size_t) i * (size_t) p.stride}, len, st.channels * p.B, &h)) {
         bits = FX_RTP_BIT_MALFORMED;
         if (lane == 0) atomicAdd(&stats[ST_MALFORMED], 1ull);
@@ -119,161 +126,86 @@ fx_rtp_parse_kernel(const RtpTick p)
         bits = FX_RTP_BIT_IGNORED;
         if (lane == 0) atomicAdd(&stats[ST_PACKETS], 1ull);
     } else {
-        const fx_rtp_placement at = fx_rtp_place(h.timestamp, st.origin + p.advanced, h.sample_times, p.n);
+        int W = 0;
+        if constexpr (WINDOW) W = w->W;
+        const fx_rtp_span_placement at = fx_rtp_place_span(h.timestamp, st.origin + p.advanced, h.sample_times, p.n, W);
         bits = at.bits;
+        const int lo = (int) at.lo, hi = (int) at.hi;       // (n + W fits an int: the host saw to it)
         int* owner = p.owner + (size_t) s * (size_t) p.n;
-        for (int q = at.lo + lane; q < at.hi; q += 64) atomicMax(&owner[q], i);
-        if (lane == 0) {
-            p.records[i] = RtpRecord{h.payload, at.d0};
-            atomicAdd(&stats[ST_PACKETS], 1ull);
-            if (!(bits & FX_RTP_BIT_PLACED) && (bits & FX_RTP_BIT_LATE)) atomicAdd(&stats[ST_LATE], 1ull);
-            if (!(bits & FX_RTP_BIT_PLACED) && (bits & FX_RTP_BIT_EARLY)) atomicAdd(&stats[ST_EARLY], 1ull);
-        }
-    }
-    if (lane == 0 && p.disposition) p.disposition[i] = (unsigned char) bits;
-}
-
-// The same with a reorder window: the packet is placed in the span of n + W positions and claims each covered position where that
-// part of the span keeps its owners (the unit's header comment).  A position of [n, W) whose stamp was 0 is newly held: counted here;
-// the far end's and the consumed positions' share of `held` is fx_rtp_count_span_kernel's.
-__global__ void __launch_bounds__(256)
-fx_rtp_parse_span_kernel(const RtpSpan w)
-{
-    const RtpTick& p = w.t;
-    const int lane = threadIdx.x & 63, i = (int) blockIdx.x * 4 + (int) (threadIdx.x >> 6);
-    if (i >= p.P) return;
-    const int s = p.stream_of[i], len = p.lengths[i];
-    const RtpStream st = p.streams[s];
-    unsigned long long* stats = p.stats + (size_t) s * ST_FIELDS;
-    fx_rtp_parsed h;
-    unsigned bits;
-    RtpHeldRange keep{0, 0};
-    if (!fx_rtp_parse(SlotBytes{p.slots + (size_t) i * (size_t) p.stride}, len, st.channels * p.B, &h)) {
-        bits = FX_RTP_BIT_MALFORMED;
-        if (lane == 0) atomicAdd(&stats[ST_MALFORMED], 1ull);
-    } else if (!st.running) {
-        bits = FX_RTP_BIT_IGNORED;
-        if (lane == 0) atomicAdd(&stats[ST_PACKETS], 1ull);
-    } else {
-        const fx_rtp_span_placement at = fx_rtp_place_span(h.timestamp, st.origin + p.advanced, h.sample_times, p.n, w.W);
-        bits = at.bits;
-        const int lo = (int) at.lo, hi = (int) at.hi, far0 = p.n > w.W ? p.n : w.W;       // (n + W fits an int: the host saw to it)
-        int* owner = p.owner + (size_t) s * (size_t) p.n;
-        int* far = w.far + (size_t) s * (size_t) w.E;
-        unsigned long long* stamps = w.stamps + (size_t) s * (size_t) w.W;
-        const unsigned long long mine = span_stamp(w.tick, i);
-        int fresh = 0;
-        for (int q = lo + lane; q < hi; q += 64) {
-            if (q < p.n) atomicMax(&owner[q], i);
-            else if (q >= far0) atomicMax(&far[q - far0], i);
-            else fresh += atomicMax(&stamps[span_slot(w, q)], mine) == 0ull;
-        }
-        if (bits & FX_RTP_BIT_HELD) keep = RtpHeldRange{lo > p.n ? lo : p.n, hi};
-        if (p.n < w.W) {                                    // (uniform: only then is there a part [n, W))
-            for (int d = 32; d > 0; d >>= 1) fresh += __shfl_xor(fresh, d);
-            if (lane == 0 && fresh) atomicAdd(&w.wstats[(size_t) WS_HELD * p.S + s], (unsigned long long) fresh);
+        if constexpr (!WINDOW) {
+            for (int q = lo + lane; q < hi; q += 64) atomicMax(&owner[q], i);
+        } else {
+            const int far0 = p.n > W ? p.n : W;
+            int* far = w->far + (size_t) s * (size_t) w->E;
+            unsigned long long* stamps = w->stamps + (size_t) s * (size_t) W;
+            const unsigned long long mine = span_stamp(w->tick, i);
+            int fresh = 0;
+            for (int q = lo + lane; q < hi; q += 64) {
+                if (q < p.n) atomicMax(&owner[q], i);
+                else if (q >= far0) atomicMax(&far[q - far0], i);
+                else fresh += atomicMax(&stamps[span_slot(*w, q)], mine) == 0ull;
+            }
+            if (bits & FX_RTP_BIT_HELD) keep = RtpHeldRange{lo > p.n ? lo : p.n, hi};
+            if (p.n < W) {                                      // (uniform: only then is there a part [n, W))
+                for (int d = 32; d > 0; d >>= 1) fresh += __shfl_xor(fresh, d);
+                if (lane == 0 && fresh) atomicAdd(&w->wstats[(size_t) WS_HELD * p.S + s], (unsigned long long) fresh);
+            }
         }
         if (lane == 0) {
             p.records[i] = RtpRecord{h.payload, at.d0};
             atomicAdd(&stats[ST_PACKETS], 1ull);
-            const bool in_span = bits & (FX_RTP_BIT_PLACED | FX_RTP_BIT_HELD);
+            const bool in_span = bits & (FX_RTP_BIT_PLACED | FX_RTP_BIT_HELD);          // (HELD: only ever with a window)
             if (!in_span && (bits & FX_RTP_BIT_LATE)) atomicAdd(&stats[ST_LATE], 1ull);
             if (!in_span && (bits & FX_RTP_BIT_EARLY)) atomicAdd(&stats[ST_EARLY], 1ull);
         }
     }
     if (lane == 0) {
-        w.held[i] = keep;
+        if constexpr (WINDOW) w->held[i] = keep;
         if (p.disposition) p.disposition[i] = (unsigned char) bits;
     }
 }
 
-// The B bytes of a big-endian sample at byte `at` of the slots, as the little-endian sample in the low bytes.  The sample lies inside
-// its packet and a slot starts and ends on a dword boundary, so the one or two aligned dwords around it lie inside the slot: no wide
-// load that could cross the end of the slots' memory.
-template <int B> __device__ __forceinline__ unsigned load_reversed(const unsigned char* slots, long long at)
+__global__ void __launch_bounds__(256)
+fx_rtp_parse_kernel(const RtpTick p)
+{
+    rtp_parse(p, nullptr);
+}
+
+__global__ void __launch_bounds__(256)
+fx_rtp_parse_span_kernel(const RtpSpan w)
+{
+    rtp_parse(w.t, &w);
+}
+
+// The B bytes (1 .. 4) at byte `at` of `base`, first byte lowest; what lies above them is whatever follows.  They lie inside one
+// datagram, and a slot starts and ends on a dword boundary (as a stream's ring does, with a dword of slack behind it), so the one or
+// two aligned dwords around them lie inside the slot: no wide load that could cross the end of the slots' memory.
+template <int B> __device__ __forceinline__ unsigned load_bytes(const unsigned char* base, long long at)
 {
     const unsigned sh = (unsigned) at & 3u;
-    const unsigned* w = reinterpret_cast<const unsigned*>(slots + (at - sh));
+    const unsigned* w = reinterpret_cast<const unsigned*>(base + (at - sh));
     const unsigned lo = w[0], hi = sh + B > 4 ? w[1] : 0u;
-    const unsigned v = __builtin_amdgcn_alignbyte(hi, lo, sh);         // the sample's bytes from bit 0 up, first byte lowest
-    return __builtin_bswap32(v) >> (32 - 8 * B);                        // (one v_perm_b32 and a shift)
+    return __builtin_amdgcn_alignbyte(hi, lo, sh);
 }
 
-// ---- the tile: PT_TRACKS planar rows on their way to memory through LDS ----
-// TWIN: tile_at, store_sample, pick and tile_to_rows restate the tile of fx_deinterleave_kernel (fx_interleave.hip: tile_at,
-// store_sample, pick and the kernel's store stage) for 2- and 3-byte samples.  A change to the layout or the drain of one belongs in
-// the other too.  (They are two copies because that kernel's machine code moves when its tile comes from a shared header.)
-// The load stage puts sample f of tile row r at byte m + f * B of the row, m the byte the row's segment has in the planar block
-// modulo 16.  The store stage reads whole 16-byte chunks back (ds_read_b128) and writes them to 16-byte aligned addresses
-// (global_store_dwordx4), consecutive lanes along a row and on into the next one.  Only the first and last chunk of a row's segment
-// are partial: they are written byte by byte, each byte once, whatever the row pitch n * B makes of the alignment.
-constexpr int PT_FRAMES = 64, PT_TRACKS = 64, PT_THREADS = 256, PT_GROUP = 8;
-static_assert(PT_THREADS == 4 * 64 && PT_TRACKS == 64 && (PT_FRAMES / 4) % PT_GROUP == 0, "lane = track, four wavefronts step through the positions, PT_GROUP at a time");
-// a row's segment of PT_FRAMES * B bytes, placed at its offset modulo 16
-template <int B> constexpr int pt_chunks() { return PT_FRAMES * B / 16 + 1; }
-template <int B> constexpr int pt_row() { return 16 * pt_chunks<B>(); }
-
-// Byte `col` of tile row r: chunks of 16 bytes in order, the four dwords of a chunk rotated by (r / 8) % 4.  A row is 9 (L16) or 13
-// (L24) chunks, 36 or 52 dwords: on the 32 banks a store sees, row r starts at bank 4 r or 20 r modulo 32, eight distinct multiples
-// of 4 for r = 0 .. 7 and the same again for r + 8; the rotation moves those apart, so the load stage's stores (a group of 32 lanes =
-// 32 rows at one sample) fall on 32 distinct banks where the rows' offsets modulo 16 agree, and on at most two lanes a bank where
-// they do not.  The store stage's reads of whole chunks are not affected.
-__device__ __forceinline__ int tile_at(int r, int row_bytes, int col)
+// a big-endian sample of B bytes there, as the little-endian sample in the low bytes (one v_perm_b32 and a shift)
+template <int B> __device__ __forceinline__ unsigned load_reversed(const unsigned char* base, long long at)
 {
-    return r * row_bytes + (col & ~15) + ((((col >> 2) + (r >> 3)) & 3) << 2) + (col & 3);
-}
-
-// (a row's offset modulo 16 is even for 2-byte samples: those never straddle a dword of the tile)
-template <int B> __device__ __forceinline__ void store_sample(unsigned char* tile, int r, int row_bytes, int col, unsigned v)
-{
-    if constexpr (B == 2) *reinterpret_cast<unsigned short*>(tile + tile_at(r, row_bytes, col)) = (unsigned short) v;
-    else {
-#pragma unroll
-        for (int i = 0; i < 3; i++) tile[tile_at(r, row_bytes, col + i)] = (unsigned char) (v >> (8 * i));
-    }
-}
-
-__device__ __forceinline__ unsigned pick(const uint4& q, int j)
-{
-    j &= 3;
-    return j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w;
-}
-
-// The tile's rows to out [C][n] samples of B bytes (16-byte aligned): tracks c0 .. of the block's C, positions q0 .. q0 + nq of n.
-// All PT_THREADS threads of the workgroup, after the barrier that ends the load stage.
-template <int B>
-__device__ __forceinline__ void tile_to_rows(const unsigned char* tile, unsigned char* out, int c0, int C, int q0, int nq, int n)
-{
-    constexpr int CHUNKS = pt_chunks<B>(), ROW = pt_row<B>();
-    for (int i = threadIdx.x; i < PT_TRACKS * CHUNKS; i += PT_THREADS) {
-        const int r = i / CHUNKS, k = i - r * CHUNKS, c = c0 + r;
-        if (c >= C) break;                                  // (r only grows with i)
-        const long long seg = ((long long) c * n + q0) * B;
-        const int m = (int) (seg & 15);
-        const int lo = m > 16 * k ? m : 16 * k, hi = m + nq * B < 16 * k + 16 ? m + nq * B : 16 * k + 16;
-        if (lo >= hi) continue;
-        const uint4 s = *reinterpret_cast<const uint4*>(tile + r * ROW + 16 * k);
-        const int rot = r >> 3;
-        const uint4 q{pick(s, rot), pick(s, rot + 1), pick(s, rot + 2), pick(s, rot + 3)};
-        unsigned char* dst = out + (seg - m) + 16 * k;
-        if (hi - lo == 16) {
-            *reinterpret_cast<uint4*>(dst) = q;
-        } else {
-            for (int b = lo - 16 * k; b < hi - 16 * k; b++) dst[b] = (unsigned char) (pick(q, b >> 2) >> (8 * (b & 3)));
-        }
-    }
+    return __builtin_bswap32(load_bytes<B>(base, at)) >> (32 - 8 * B);
 }
 
 // A workgroup takes PT_FRAMES positions of PT_TRACKS consecutive tracks.  Load: lane = track, wavefront = position, so a wavefront
 // reads, of every stream its tracks hear, one sample time of one packet: F contiguous bytes where consecutive tracks hear consecutive
 // channels, and the sample time after it four steps later.  The owner and the record are the same address for all lanes of a stream
-// (one request).  The samples go to the tile above and from there to the planar rows.
+// (one request).  The samples go to the tile of fx_planar_tile.hip.h and from there to the planar rows.
 // (One body for both forms of the tick: Span = const RtpSpan* with a reorder window -- a position no packet of the tick owns is then
 // read from the stream's ring where its stamp says it is held -- and nullptr_t without, which is the kernel as it was.)
+constexpr int PT_GROUP = 8;
+static_assert((PT_FRAMES / 4) % PT_GROUP == 0, "four wavefronts step through the positions, PT_GROUP at a time");
 template <int B, typename Span>
 __device__ __forceinline__ void rtp_gather(const RtpTick& p, Span w)
 {
-    constexpr int ROW = pt_row<B>();
+    constexpr int ROW = pt_row_bytes(B);
     constexpr bool WINDOW = !std::is_same<Span, std::nullptr_t>::value;
     __shared__ __attribute__((aligned(16))) unsigned char tile[PT_TRACKS * ROW];
     const int q0 = (int) blockIdx.x * PT_FRAMES;
@@ -340,7 +272,7 @@ __device__ __forceinline__ void rtp_gather(const RtpTick& p, Span w)
     }
     __syncthreads();
 
-    tile_to_rows<B>(tile, p.out, c0, p.C, q0, nq, p.n);
+    tile_to_rows<B>(tile, p.out, c0, p.C, (long long) p.n * B, (long long) q0 * B, nq);
 }
 
 template <int B>
@@ -358,77 +290,66 @@ fx_rtp_gather_span_kernel(const RtpSpan w)
 }
 
 // Owned and missing positions of the tick, per running stream: workgroup (s, y) steps through the stream's row of the owner table,
-// every wavefront counts by ballot and adds its two sums once.
-__global__ void __launch_bounds__(256)
-fx_rtp_count_kernel(const RtpTick p)
+// every wavefront counts by ballot and adds its sums once.
+// (One body for both forms of the tick.  With a reorder window a position of the tick is owned through a packet of the tick or,
+// failing that, through the held state (recovered).  The thread of a position q < E = min(n, W) is also the only one that touches
+// ring slot (head + q) % W in this launch: it has read the stamp of the position the tick consumes, and leaves the stamp of the
+// far-end position that takes the slot over -- Q = q + W for n < W, else the one Q of [n, n + W) with Q = q modulo W -- or 0.
+// `held` moves by the difference.)
+template <typename Span>
+__device__ __forceinline__ void rtp_count(const RtpTick& p, Span w)
 {
+    constexpr bool WINDOW = !std::is_same<Span, std::nullptr_t>::value;
     const int s = (int) blockIdx.x;
     if (!p.streams[s].running) return;
     const int* owner = p.owner + (size_t) s * (size_t) p.n;
     int owned = 0, seen = 0;
+    [[maybe_unused]] int recovered = 0, gained = 0, lost = 0;
     for (int q0 = (int) blockIdx.y * 256; q0 < p.n; q0 += 256 * (int) gridDim.y) {
         const int q = q0 + (int) threadIdx.x;
         const bool in = q < p.n;
         seen += __popcll(__ballot(in));
-        owned += __popcll(__ballot(in && owner[q] >= 0));
+        const bool own = in && owner[q] >= 0;
+        if constexpr (!WINDOW) {
+            owned += __popcll(__ballot(own));
+        } else {
+            bool was = false, next = false;
+            if (in && q < w->E) {
+                unsigned long long* stamp = w->stamps + (size_t) s * (size_t) w->W + span_slot(*w, q);
+                was = *stamp != 0ull;
+                int k = q;
+                if (p.n >= w->W) { k = (q - p.n) % w->W; if (k < 0) k += w->W; }
+                const int i = w->far[(size_t) s * (size_t) w->E + k];
+                next = i >= 0;
+                *stamp = next ? span_stamp(w->tick, i) : 0ull;
+            }
+            owned += __popcll(__ballot(own || was));
+            recovered += __popcll(__ballot(was && !own));
+            gained += __popcll(__ballot(next));
+            lost += __popcll(__ballot(was));
+        }
     }
     if ((threadIdx.x & 63) == 0 && seen) {
         unsigned long long* stats = p.stats + (size_t) s * ST_FIELDS;
         atomicAdd(&stats[ST_PLACED], (unsigned long long) owned);
         atomicAdd(&stats[ST_MISSING], (unsigned long long) (seen - owned));
+        if constexpr (WINDOW) {
+            if (recovered) atomicAdd(&w->wstats[(size_t) WS_RECOVERED * p.S + s], (unsigned long long) recovered);
+            if (gained != lost) atomicAdd(&w->wstats[(size_t) WS_HELD * p.S + s], (unsigned long long) (long long) (gained - lost));   // (wraps to the sum)
+        }
     }
 }
 
-// The count with a reorder window: a position of the tick is owned through a packet of the tick or, failing that, through the held
-// state (recovered).  The thread of a position q < E = min(n, W) is also the only one that touches ring slot (head + q) % W in this
-// launch: it has read the stamp of the position the tick consumes, and leaves the stamp of the far-end position that takes the
-// slot over -- Q = q + W for n < W, else the one Q of [n, n + W) with Q = q modulo W -- or 0.  `held` moves by the difference.
+__global__ void __launch_bounds__(256)
+fx_rtp_count_kernel(const RtpTick p)
+{
+    rtp_count(p, nullptr);
+}
+
 __global__ void __launch_bounds__(256)
 fx_rtp_count_span_kernel(const RtpSpan w)
 {
-    const RtpTick& p = w.t;
-    const int s = (int) blockIdx.x;
-    if (!p.streams[s].running) return;
-    const int* owner = p.owner + (size_t) s * (size_t) p.n;
-    const int* far = w.far + (size_t) s * (size_t) w.E;
-    unsigned long long* stamps = w.stamps + (size_t) s * (size_t) w.W;
-    int owned = 0, seen = 0, recovered = 0, gained = 0, lost = 0;
-    for (int q0 = (int) blockIdx.y * 256; q0 < p.n; q0 += 256 * (int) gridDim.y) {
-        const int q = q0 + (int) threadIdx.x;
-        const bool in = q < p.n;
-        const bool own = in && owner[q] >= 0;
-        bool was = false, next = false;
-        if (in && q < w.E) {
-            const int at = span_slot(w, q);
-            was = stamps[at] != 0ull;
-            int k = q;
-            if (p.n >= w.W) { k = (q - p.n) % w.W; if (k < 0) k += w.W; }
-            const int i = far[k];
-            next = i >= 0;
-            stamps[at] = next ? span_stamp(w.tick, i) : 0ull;
-        }
-        seen += __popcll(__ballot(in));
-        owned += __popcll(__ballot(own || was));
-        recovered += __popcll(__ballot(was && !own));
-        gained += __popcll(__ballot(next));
-        lost += __popcll(__ballot(was));
-    }
-    if ((threadIdx.x & 63) == 0 && seen) {
-        unsigned long long* stats = p.stats + (size_t) s * ST_FIELDS;
-        atomicAdd(&stats[ST_PLACED], (unsigned long long) owned);
-        atomicAdd(&stats[ST_MISSING], (unsigned long long) (seen - owned));
-        if (recovered) atomicAdd(&w.wstats[(size_t) WS_RECOVERED * p.S + s], (unsigned long long) recovered);
-        if (gained != lost) atomicAdd(&w.wstats[(size_t) WS_HELD * p.S + s], (unsigned long long) (long long) (gained - lost));   // (wraps to the sum)
-    }
-}
-
-// The 4 bytes at byte `at` of the slots (all inside one datagram, so the aligned dwords around them lie inside its slot), first lowest.
-__device__ __forceinline__ unsigned load_shifted(const unsigned char* slots, long long at)
-{
-    const unsigned sh = (unsigned) at & 3u;
-    const unsigned* w = reinterpret_cast<const unsigned*>(slots + (at - sh));
-    const unsigned lo = w[0], hi = sh ? w[1] : 0u;
-    return __builtin_amdgcn_alignbyte(hi, lo, sh);
+    rtp_count(w.t, &w);
 }
 
 // Bytes [r0, r1) of stream s's ring (ring slots [r0 / F, r1 / F), which hold the span positions from qa on) from byte `src` of the
@@ -450,7 +371,7 @@ __device__ __forceinline__ void deposit_run(const RtpSpan& w, int s, int i, int 
         const int first = b0 / F, last = (b1 - 1) / F;
         const bool own_first = owns(qa + (first - slot0)), own_last = last == first ? own_first : owns(qa + (last - slot0));
         if (b1 - b0 == 4 && own_first && own_last) {
-            *reinterpret_cast<unsigned*>(ring + a) = load_shifted(p.slots, src + (a - r0));
+            *reinterpret_cast<unsigned*>(ring + a) = load_bytes<4>(p.slots, src + (a - r0));
         } else {
             for (int b = b0; b < b1; b++)
                 if (b / F == first ? own_first : own_last) ring[b] = p.slots[src + (b - r0)];
@@ -477,24 +398,6 @@ fx_rtp_deposit_kernel(const RtpSpan w)
     if (head < count) deposit_run(w, s, i, F, lane, 0, (count - head) * F, keep.lo + head, src + (long long) head * F);
 }
 
-hipError_t launch_rtp_span_kernels(const RtpSpan& w, hipStream_t stream)
-{
-    const RtpTick& p = w.t;
-    const long long gx = ((long long) p.n + PT_FRAMES - 1) / PT_FRAMES, gy = ((long long) p.C + PT_TRACKS - 1) / PT_TRACKS;
-    if (gy > 65535) return hipErrorInvalidValue;
-    // (owner and far are one allocation, [S][n] then [S][E])
-    hipError_t e = hipMemsetAsync(p.owner, 0xff, sizeof(int) * (size_t) p.S * ((size_t) p.n + (size_t) w.E), stream);
-    if (e != hipSuccess) return e;
-    const dim3 packets((unsigned) ((p.P + 3) / 4)), gather((unsigned) gx, (unsigned) gy);
-    const dim3 count((unsigned) p.S, (unsigned) (gx < 16 ? (gx + 3) / 4 : 4));
-    if (p.P > 0) hipLaunchKernelGGL(fx_rtp_parse_span_kernel, packets, dim3(256), 0, stream, w);
-    if (p.B == 2) hipLaunchKernelGGL(fx_rtp_gather_span_kernel<2>, gather, dim3(PT_THREADS), 0, stream, w);
-    else hipLaunchKernelGGL(fx_rtp_gather_span_kernel<3>, gather, dim3(PT_THREADS), 0, stream, w);
-    hipLaunchKernelGGL(fx_rtp_count_span_kernel, count, dim3(256), 0, stream, w);
-    if (p.P > 0) hipLaunchKernelGGL(fx_rtp_deposit_kernel, packets, dim3(256), 0, stream, w);
-    return hipGetLastError();
-}
-
 // Before the tick number would wrap: every held position's stamp becomes the least one, which any later claim beats.
 __global__ void __launch_bounds__(256)
 fx_rtp_rebase_stamps_kernel(unsigned long long* stamps, long long count)
@@ -503,22 +406,82 @@ fx_rtp_rebase_stamps_kernel(unsigned long long* stamps, long long count)
     if (k < count && stamps[k] != 0ull) stamps[k] = 1ull;
 }
 
-hipError_t launch_rtp_kernels(const RtpTick& p, hipStream_t stream)
+// A tick's fill and launches, in the order the unit's header comment gives; w: the tick's span (w->t is p), null without a window.
+hipError_t launch_rtp_kernels(const RtpTick& p, const RtpSpan* w /* null: no window */, hipStream_t stream)
 {
     const long long gx = ((long long) p.n + PT_FRAMES - 1) / PT_FRAMES, gy = ((long long) p.C + PT_TRACKS - 1) / PT_TRACKS;
     if (gy > 65535) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(p.owner, 0xff, sizeof(int) * (size_t) p.S * (size_t) p.n, stream);
+    // (owner and far are one allocation, [S][n] then [S][E]; no window: no far end)
+    hipError_t e = hipMemsetAsync(p.owner, 0xff, sizeof(int) * (size_t) p.S * ((size_t) p.n + (size_t) (w ? w->E : 0)), stream);
     if (e != hipSuccess) return e;
-    const dim3 parse((unsigned) ((p.P + 3) / 4)), gather((unsigned) gx, (unsigned) gy);
-    const dim3 count((unsigned) p.S, (unsigned) (gx < 16 ? (gx + 3) / 4 : 4));
-    if (p.P > 0) hipLaunchKernelGGL(fx_rtp_parse_kernel, parse, dim3(256), 0, stream, p);
-    if (p.B == 2) hipLaunchKernelGGL(fx_rtp_gather_kernel<2>, gather, dim3(PT_THREADS), 0, stream, p);
-    else hipLaunchKernelGGL(fx_rtp_gather_kernel<3>, gather, dim3(PT_THREADS), 0, stream, p);
-    hipLaunchKernelGGL(fx_rtp_count_kernel, count, dim3(256), 0, stream, p);
+    const dim3 packets((unsigned) ((p.P + 3) / 4)), tiles((unsigned) gx, (unsigned) gy);
+    const dim3 rows((unsigned) p.S, (unsigned) (gx < 16 ? (gx + 3) / 4 : 4));
+    const auto stages = [&](auto parse, auto gather2, auto gather3, auto count, const auto& arg) {
+        const auto gather = p.B == 2 ? gather2 : gather3;
+        if (p.P > 0) hipLaunchKernelGGL(parse, packets, dim3(256), 0, stream, arg);
+        hipLaunchKernelGGL(gather, tiles, dim3(PT_THREADS), 0, stream, arg);
+        hipLaunchKernelGGL(count, rows, dim3(256), 0, stream, arg);
+    };
+    if (!w) {
+        stages(fx_rtp_parse_kernel, fx_rtp_gather_kernel<2>, fx_rtp_gather_kernel<3>, fx_rtp_count_kernel, p);
+    } else {
+        stages(fx_rtp_parse_span_kernel, fx_rtp_gather_span_kernel<2>, fx_rtp_gather_span_kernel<3>, fx_rtp_count_span_kernel, *w);
+        if (p.P > 0) hipLaunchKernelGGL(fx_rtp_deposit_kernel, packets, dim3(256), 0, stream, *w);
+    }
     return hipGetLastError();
 }
 
 } // namespace fxk
+
+// The reorder window's device state: nothing of it exists while window == 0.  It is allocated whole by fx_rtp_set_window and never by
+// a tick, so no tick's growing buffer can drop what is held.
+struct fx_rtp_window {
+    int      window = 0;                        // W
+    int      head = 0;                          // the ring slot of the next tick's position 0
+    unsigned tick_no = 1;                       // the next tick's number in the stamps
+    unsigned char*      ring = nullptr;         // every stream's ring: W * channels * B bytes from a 4-byte boundary, 4 bytes of slack behind
+    long long*          ring_base = nullptr;    // [S]
+    unsigned long long* stamps = nullptr;       // [S][W]
+    unsigned long long* wstats = nullptr;       // [2][S]: held, recovered
+};
+
+static void rtp_window_free(fx_rtp_window* w)
+{
+    fx_free_device({w->ring, w->ring_base, w->stamps, w->wstats});
+    *w = fx_rtp_window();
+}
+
+// *out (empty on entry): a window of W > 0 sample times for these streams of B-byte samples, nothing held; a failure leaves it empty
+static fx_status rtp_window_alloc(fx_rtp_window* out, const std::vector<fxk::RtpStream>& streams, int W, int B)
+{
+    const size_t S = streams.size();
+    std::vector<long long> base;
+    try {
+        base.resize(S);
+    } catch (const std::bad_alloc&) {
+        return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    }
+    long long ring_bytes = 0;
+    for (size_t k = 0; k < S; k++) {                    // each ring from a dword boundary, a dword of slack behind it
+        base[k] = ring_bytes;
+        ring_bytes += (((long long) W * streams[k].channels * B + 3) & ~3ll) + 4;
+    }
+    const size_t stamp_bytes = sizeof(unsigned long long) * S * (size_t) W, wstats_bytes = sizeof(unsigned long long) * fxk::WS_FIELDS * S;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&out->ring), (size_t) ring_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&out->ring_base), sizeof(long long) * S);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&out->stamps), stamp_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&out->wstats), wstats_bytes);
+    if (e == hipSuccess) e = hipMemset(out->ring, 0, (size_t) ring_bytes);
+    if (e == hipSuccess) e = hipMemset(out->stamps, 0, stamp_bytes);
+    if (e == hipSuccess) e = hipMemset(out->wstats, 0, wstats_bytes);
+    if (e == hipSuccess) e = hipMemcpy(out->ring_base, base.data(), sizeof(long long) * S, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        rtp_window_free(out);
+        return fx_fail(fx_hip_status(e), "allocating a reorder window of %d sample times failed: %s", W, hipGetErrorString(e));
+    }
+    out->window = W;
+    return FX_OK;
+}
 
 struct fx_rtp {
     int format = FX_RTP_L16;                    // FX_RTP_L16 / FX_RTP_L24
@@ -540,16 +503,8 @@ struct fx_rtp {
     int*           d_owner = nullptr;
     unsigned char* d_planar = nullptr;          // the planar block handed to fx_push_block
     size_t slots_cap = 0, disposition_cap = 0, records_cap = 0, owner_cap = 0, planar_cap = 0;
-    // the reorder window (fx_rtp_set_window): nothing of it exists while window == 0.  The ring, the stamps and the counters are
-    // allocated there and never by a tick, so no tick's growing buffer can drop what is held.
-    int      window = 0;                        // W
-    int      head = 0;                          // the ring slot of the next tick's position 0
-    unsigned tick_no = 1;                       // the next tick's number in the stamps
-    unsigned char*      d_ring = nullptr;       // every stream's ring: W * channels * B bytes from a 4-byte boundary, 4 bytes of slack behind
-    long long*          d_ring_base = nullptr;  // [S]
-    unsigned long long* d_stamps = nullptr;     // [S][W]
-    unsigned long long* d_wstats = nullptr;     // [2][S]: held, recovered
-    fxk::RtpHeldRange*  d_held = nullptr;       // [P], a tick's scratch
+    fx_rtp_window win;                          // the reorder window (fx_rtp_set_window)
+    fxk::RtpHeldRange*  d_held = nullptr;       // [P], a tick's scratch with a window
     size_t held_cap = 0;
 
     int bytes() const { return format == FX_RTP_L16 ? 2 : 3; }
@@ -562,8 +517,8 @@ void rtp_release(fx_context* c)
 {
     fx_rtp* s = c->rtp;
     if (!s) return;
-    fx_free_device({s->d_streams, s->d_tracks, s->d_stats, s->d_slots, s->d_disposition, s->d_records, s->d_owner, s->d_planar,
-                    s->d_ring, s->d_ring_base, s->d_stamps, s->d_wstats, s->d_held});
+    fx_free_device({s->d_streams, s->d_tracks, s->d_stats, s->d_slots, s->d_disposition, s->d_records, s->d_owner, s->d_planar, s->d_held});
+    rtp_window_free(&s->win);
     for (int k = 0; k < 2; k++) {
         fx_release_list(&s->meta[k]);
         if (s->meta_done[k]) (void) hipEventDestroy(s->meta_done[k]);
@@ -699,7 +654,7 @@ fx_status fx_rtp_set_cursors(fx_context* c, const int* streams, int num, const u
         r.origin = timestamp[i] - s->advanced;
         r.running = 1;
     }
-    if (s->window > 0) {
+    if (s->win.window > 0) {
         // the listed streams' time base has moved: what they hold goes, run of consecutive streams by run
         std::vector<int> listed;
         try {
@@ -712,8 +667,8 @@ fx_status fx_rtp_set_cursors(fx_context* c, const int* streams, int num, const u
             size_t b = a + 1;
             while (b < listed.size() && listed[b] <= listed[b - 1] + 1) b++;
             const size_t first = (size_t) listed[a], rows = (size_t) (listed[b - 1] - listed[a] + 1);
-            HIP_TRY(hipMemset(s->d_stamps + first * (size_t) s->window, 0, rows * (size_t) s->window * sizeof(unsigned long long)));
-            HIP_TRY(hipMemset(s->d_wstats + (size_t) fxk::WS_HELD * s->streams.size() + first, 0, rows * sizeof(unsigned long long)));
+            HIP_TRY(hipMemset(s->win.stamps + first * (size_t) s->win.window, 0, rows * (size_t) s->win.window * sizeof(unsigned long long)));
+            HIP_TRY(hipMemset(s->win.wstats + (size_t) fxk::WS_HELD * s->streams.size() + first, 0, rows * sizeof(unsigned long long)));
             a = b;
         }
     }
@@ -758,7 +713,8 @@ fx_status fx_push_rtp(fx_context* c, const void* packets, const int* lengths, co
     // fx_push_block's own refusals, before anything is launched: a refused call changes nothing
     const int format = s->sample_format(), B = s->bytes();
     { const fx_status rs = fx_block_refusal(c, num_samples, format); if (rs != FX_OK) return rs; }
-    const int W = s->window, E = num_samples < W ? num_samples : W;     // (E: the far end's claims, fxk::RtpSpan)
+    fx_rtp_window& win = s->win;
+    const int W = win.window, E = num_samples < W ? num_samples : W;    // (E: the far end's claims, fxk::RtpSpan)
     if (W > 0 && num_samples > INT32_MAX - W) return fx_fail(FX_ERR_INVALID_ARGUMENT, "%d samples and a window of %d: the span is too long for one call", num_samples, W);
 
     HIP_TRY(hipSetDevice(c->device));
@@ -815,30 +771,30 @@ fx_status fx_push_rtp(fx_context* c, const void* packets, const int* lengths, co
     p.advanced = s->advanced;
     if (fx_launch_record* r = note_launch(c, FX_LAUNCH_RTP, 0)) r->T = num_samples;
     if (W == 0) {
-        HIP_TRY(fxk::launch_rtp_kernels(p, c->stream));
+        HIP_TRY(fxk::launch_rtp_kernels(p, nullptr, c->stream));
     } else {
         // the stamps' tick numbers start over below every later one before they would wrap (FX_HOOK_RTP_FEW_TICK_NUMBERS, tests: after 3)
-        if (s->tick_no >= ((c->test_hooks & FX_HOOK_RTP_FEW_TICK_NUMBERS) ? 4u : UINT32_MAX)) {
+        if (win.tick_no >= ((c->test_hooks & FX_HOOK_RTP_FEW_TICK_NUMBERS) ? 4u : UINT32_MAX)) {
             const long long count = (long long) S * W;
-            hipLaunchKernelGGL(fxk::fx_rtp_rebase_stamps_kernel, dim3((unsigned) ((count + 255) / 256)), dim3(256), 0, c->stream, s->d_stamps, count);
+            hipLaunchKernelGGL(fxk::fx_rtp_rebase_stamps_kernel, dim3((unsigned) ((count + 255) / 256)), dim3(256), 0, c->stream, win.stamps, count);
             HIP_TRY(hipGetLastError());
-            s->tick_no = 1;
+            win.tick_no = 1;
         }
         fxk::RtpSpan w;
         w.t = p;
         w.far = s->d_owner + (size_t) S * (size_t) num_samples;
         w.held = s->d_held;
-        w.ring = s->d_ring;
-        w.ring_base = s->d_ring_base;
-        w.stamps = s->d_stamps;
-        w.wstats = s->d_wstats;
+        w.ring = win.ring;
+        w.ring_base = win.ring_base;
+        w.stamps = win.stamps;
+        w.wstats = win.wstats;
         w.W = W;
         w.E = E;
-        w.head = s->head;
-        w.tick = s->tick_no;
-        HIP_TRY(fxk::launch_rtp_span_kernels(w, c->stream));
-        s->head = (int) (((long long) s->head + num_samples) % W);
-        s->tick_no++;
+        w.head = win.head;
+        w.tick = win.tick_no;
+        HIP_TRY(fxk::launch_rtp_kernels(w.t, &w, c->stream));
+        win.head = (int) (((long long) win.head + num_samples) % W);
+        win.tick_no++;
     }
     s->advanced += (unsigned) num_samples;              // every running stream's cursor
     s->last_n = num_samples;
@@ -902,44 +858,13 @@ fx_status fx_rtp_set_window(fx_context* c, int window)
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));           // ticks in flight read and write the held state
     // the new window's state whole, then the old one goes: a failure leaves the unit as it was
-    unsigned char* ring = nullptr;
-    long long* ring_base = nullptr;
-    unsigned long long *stamps = nullptr, *wstats = nullptr;
+    fx_rtp_window next;
     if (window > 0) {
-        const size_t S = s->streams.size();
-        std::vector<long long> base;
-        try {
-            base.resize(S);
-        } catch (const std::bad_alloc&) {
-            return fx_fail(FX_ERR_OUT_OF_MEMORY, "host allocation failed");
-        }
-        long long ring_bytes = 0;
-        for (size_t k = 0; k < S; k++) {                // each ring from a dword boundary, a dword of slack behind it
-            base[k] = ring_bytes;
-            ring_bytes += (((long long) window * s->streams[k].channels * s->bytes() + 3) & ~3ll) + 4;
-        }
-        const size_t stamp_bytes = sizeof(unsigned long long) * S * (size_t) window, wstats_bytes = sizeof(unsigned long long) * fxk::WS_FIELDS * S;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ring), (size_t) ring_bytes);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ring_base), sizeof(long long) * S);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&stamps), stamp_bytes);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&wstats), wstats_bytes);
-        if (e == hipSuccess) e = hipMemset(ring, 0, (size_t) ring_bytes);
-        if (e == hipSuccess) e = hipMemset(stamps, 0, stamp_bytes);
-        if (e == hipSuccess) e = hipMemset(wstats, 0, wstats_bytes);
-        if (e == hipSuccess) e = hipMemcpy(ring_base, base.data(), sizeof(long long) * S, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            fx_free_device({ring, ring_base, stamps, wstats});
-            return fx_fail(fx_hip_status(e), "allocating a reorder window of %d sample times failed: %s", window, hipGetErrorString(e));
-        }
+        const fx_status st = rtp_window_alloc(&next, s->streams, window, s->bytes());
+        if (st != FX_OK) return st;
     }
-    fx_free_device({s->d_ring, s->d_ring_base, s->d_stamps, s->d_wstats});
-    s->d_ring = ring;
-    s->d_ring_base = ring_base;
-    s->d_stamps = stamps;
-    s->d_wstats = wstats;
-    s->window = window;
-    s->head = 0;
-    s->tick_no = 1;
+    rtp_window_free(&s->win);
+    s->win = next;
     return FX_OK;
 }
 
@@ -948,10 +873,10 @@ fx_status fx_rtp_get_window(fx_context* c, int* window, fx_rtp_window_stats* out
     if (!c) return fx_fail(FX_ERR_INVALID_ARGUMENT, "null context");
     fx_rtp* s = nullptr;
     { const fx_status st = rtp_configured(c, &s); if (st != FX_OK) return st; }
-    if (window) *window = s->window;
+    if (window) *window = s->win.window;
     if (!out) return FX_OK;
     const size_t S = s->streams.size();
-    if (s->window == 0) {
+    if (s->win.window == 0) {
         for (size_t k = 0; k < S; k++) out[k] = fx_rtp_window_stats{0, 0};
         return FX_OK;
     }
@@ -963,7 +888,7 @@ fx_status fx_rtp_get_window(fx_context* c, int* window, fx_rtp_window_stats* out
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(got.data(), s->d_wstats, sizeof(unsigned long long) * got.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(got.data(), s->win.wstats, sizeof(unsigned long long) * got.size(), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < S; k++) out[k] = fx_rtp_window_stats{(long long) got[fxk::WS_HELD * S + k], (long long) got[fxk::WS_RECOVERED * S + k]};
     return fx_check_device_error(c);
 }

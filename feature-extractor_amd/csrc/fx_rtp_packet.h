@@ -55,28 +55,15 @@ struct fx_rtp_placement {
     unsigned bits;          // FX_RTP_BIT_PLACED / LATE / EARLY
 };
 
-// a valid packet of m sample times at timestamp T, in a tick of n positions whose first has timestamp `cursor`
-FX_RTP_FN fx_rtp_placement fx_rtp_place(unsigned T, unsigned cursor, int m, int n)
-{
-    fx_rtp_placement p;
-    p.d0 = (int) (T - cursor);
-    const long long end = (long long) p.d0 + m;
-    p.lo = p.d0 > 0 ? p.d0 : 0;
-    p.hi = end < n ? (int) end : n;
-    const unsigned late = FX_RTP_BIT_LATE, early = FX_RTP_BIT_EARLY, placed = FX_RTP_BIT_PLACED;
-    p.bits = (p.d0 < 0 ? late : 0u) | (end > n ? early : 0u) | (p.lo < p.hi ? placed : 0u);
-    if (p.lo >= p.hi) p.lo = p.hi = 0;
-    return p;
-}
-
 struct fx_rtp_span_placement {
     int       d0;           // as fx_rtp_placement
     long long lo, hi;       // the positions it covers inside the span [0, n + W), [lo, hi); empty unless PLACED or HELD
     unsigned  bits;         // FX_RTP_BIT_PLACED / HELD / LATE / EARLY
 };
 
-// the same packet against a tick with a reorder window of W sample times (include/fx.h, "the reorder window"): the span is the
-// tick's n positions and the W beyond them.  64-bit ends: neither d0 + m nor n + W overflows.  W == 0 gives fx_rtp_place's bits.
+// a valid packet of m sample times at timestamp T, in a tick of n positions whose first has timestamp `cursor`, with a reorder window
+// of W sample times (include/fx.h, "the reorder window"; 0: none): the span is the tick's n positions and the W beyond them.  64-bit
+// ends: neither d0 + m nor n + W overflows.
 FX_RTP_FN fx_rtp_span_placement fx_rtp_place_span(unsigned T, unsigned cursor, int m, int n, int W)
 {
     fx_rtp_span_placement p;
@@ -85,9 +72,17 @@ FX_RTP_FN fx_rtp_span_placement fx_rtp_place_span(unsigned T, unsigned cursor, i
     p.lo = p.d0 > 0 ? p.d0 : 0;
     p.hi = end < span ? end : span;
     const unsigned late = FX_RTP_BIT_LATE, early = FX_RTP_BIT_EARLY, placed = FX_RTP_BIT_PLACED, held = FX_RTP_BIT_HELD;
-    p.bits = (p.d0 < 0 ? late : 0u) | (end > span ? early : 0u) | (p.lo < p.hi && p.lo < n ? placed : 0u) | (p.lo < p.hi && p.hi > n ? held : 0u);
-    if (p.lo >= p.hi) p.lo = p.hi = 0;
+    const bool some = p.lo < end && p.lo < span;        // lo < hi, asked of the two ends: without a window nothing 64-bit but `end` is left
+    p.bits = (p.d0 < 0 ? late : 0u) | (end > span ? early : 0u) | (some && p.lo < n ? placed : 0u) | (some && p.hi > n ? held : 0u);
+    if (!some) p.lo = p.hi = 0;
     return p;
+}
+
+// the same without a window: the span is the tick, so hi <= n fits an int and HELD is never set
+FX_RTP_FN fx_rtp_placement fx_rtp_place(unsigned T, unsigned cursor, int m, int n)
+{
+    const fx_rtp_span_placement p = fx_rtp_place_span(T, cursor, m, n, 0);
+    return fx_rtp_placement{p.d0, (int) p.lo, (int) p.hi, p.bits};
 }
 
 #endif

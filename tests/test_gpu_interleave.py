@@ -91,6 +91,22 @@ def test_interleaved_blocks_equal_the_planar_twin(gpu_fx, N, fmt, device, block,
     an.close(); twin.close()
 
 
+@pytest.mark.parametrize("fmt", ["s16", "s24", "f32"])
+def test_blocks_at_the_tiles_seams(gpu_fx, fmt):
+    """65 tracks and 65 samples: the smallest shape with a second workgroup in tracks (one row of its tile) and a second in positions
+    (one sample), after a block of exactly one tile's 64 samples; every byte width the tile carries"""
+    C = K = 65
+    N = 256                                           # (the smallest window: the analysis behind the blocks is cheap)
+    cmap = im.maps(C, K, seed=65)["reversed"]
+    block = im.interleave(_sources(K, N, 64 + 65, seed=65), fmt)
+    an, twin = _pair(gpu_fx, C, N, cmap)
+    frames = _step(an, twin, np.ascontiguousarray(block[:64]), cmap, fmt, True)
+    frames += _step(an, twin, np.ascontiguousarray(block[64:]), cmap, fmt, True)
+    assert frames == (64 + 65) // (N // 2)
+    assert same(an.get_features(), twin.get_features())
+    an.close(); twin.close()
+
+
 def test_interleaved_and_planar_calls_alternate(gpu_fx):
     C, K, N = 5, 9, 1024
     cmap = im.maps(C, K, seed=1)["random"]

@@ -8,7 +8,7 @@ alternated, medians and spreads over the passes:
   planar       fx_push_samples of the same planar block [8192][480] s24
   interleaved  fx_push_interleaved of [480][8192] s24: the nearest existing byte mover, the same bytes each way
 What the unpack adds to a tick is rtp - planar and what the de-interleave adds is interleaved - planar (both run on the stream ahead
-of the same analysis): differences of whole calls, host side included, not kernel times.  The de-interleave's device code is byte for byte the parent commit's (tools/kernel_resources.py --digests).
+of the same analysis): differences of whole calls, host side included, not kernel times.
 
     python tools/rtp_ingest.py [--passes 15] [--out profiles/rtp_ingest_bench.txt]
 
@@ -16,10 +16,10 @@ The reorder window (fx_rtp_set_window).  --window W[,W..] adds, per W, the call
   rtp_wW       fx_push_rtp with a window of W sample times: the same datagrams, each delivered 0 .. W - 48 sample times ahead of its
                own sample time by a seeded draw (feature-extractor_amd/rtp.py, arrival_ticks / cut_into_ticks), so a tick's slots hold
                what arrived during it, part of it for later ticks; the pass's last block must be the planar block, nothing missing
-and --parent FILE adds
-  rtp_parent   the `rtp` call on the library FILE, a build of the parent commit, loaded beside this one: the W = 0 tick must lie
-               inside that call's own spread (the window adds one host test to it and no launch)
-to the alternated passes (`interleaved` is left out).
+(`interleaved` is then left out unless --parent is given), and --parent FILE adds, for `rtp`, `interleaved` and every `rtp_wW`,
+  NAME_parent  the same call on the library FILE, a build of the parent commit, loaded beside this one: this build's median must lie
+               inside that call's own spread over its passes, which is what the measurement resolves (one gate line per pair)
+to the alternated passes.
 
     python tools/rtp_ingest.py --window 480,4800 --parent PARENT/libfx_hip.so [--out profiles/rtp_window_bench.txt]
 
@@ -64,7 +64,8 @@ def kernels(db_path, out, label):
         if "rtp" in name or "deinterleave" in name or "owner table" in name:
             v = by_name[name]
             lines.append("  %-50s %7.1f (%.1f - %.1f) of %d" % (name, statistics.median(v), min(v), max(v), len(v)))
-    lines.append("  %-50s %7.1f (%.1f - %.1f) of %d" % ("a tick's unpack, fill start to last launch's end", statistics.median(spans), min(spans), max(spans), len(spans)))
+    if spans:                                             # (none in a trace of the interleaved call)
+        lines.append("  %-50s %7.1f (%.1f - %.1f) of %d" % ("a tick's unpack, fill start to last launch's end", statistics.median(spans), min(spans), max(spans), len(spans)))
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     with open(out, "a") as f:
@@ -110,21 +111,26 @@ def main():
     stamps = fx.rtp.timestamps_of(slots)
     restamped = lambda k: np.frombuffer((stamps + k * N_TICK).astype(">u4").tobytes(), np.uint8).reshape(P, 4)
     ip = ctypes.POINTER(ctypes.c_int)
-    names = ["rtp"] + (["rtp_parent"] if args.parent else []) + ["planar"] + ([] if windows or args.parent else ["interleaved"]) + ["rtp_w%d" % w for w in windows]
+    paired = ["rtp"] + ([] if windows and not args.parent else ["interleaved"]) + ["rtp_w%d" % w for w in windows]
+    base = lambda name: name[:-len("_parent")] if name.endswith("_parent") else name
+    names = []
+    for n in ["rtp", "planar"] + paired[1:]:
+        names += [n, n + "_parent"] if args.parent and n in paired else [n]
     if args.only:
         if args.only not in names:
             raise SystemExit("--only: one of %s" % ", ".join(names))
         names = [args.only]
+    called = {base(n) for n in names}
     ticks = {}                                            # per call: [(slots on the device, lengths, stream_of, P)] * TICKS
-    if any(n in names for n in ("rtp", "rtp_parent")):
+    if "rtp" in called:
         on_time = []
         for k in range(TICKS):
             s = slots.copy()
             s[:, 4:8] = restamped(k)
             on_time.append((torch.from_numpy(s).cuda(), lengths, stream_of, P))
-        ticks["rtp"] = ticks["rtp_parent"] = on_time
+        ticks["rtp"] = on_time
     for w in windows:
-        if "rtp_w%d" % w not in names:
+        if "rtp_w%d" % w not in called:
             continue
         # a pass's datagrams as one list, in time order, each submitted in the tick during which it arrives
         everything = np.concatenate([slots] * TICKS)
@@ -144,7 +150,7 @@ def main():
 
     def analyser(name):
         """(the analyser, the library its calls go to)"""
-        its = other_library(capi, args.parent) if name == "rtp_parent" else lib
+        its = parent_lib if name.endswith("_parent") else lib
         kept, capi._lib = capi._lib, its                  # (a BatchAnalyser keeps the library it was made with)
         try:
             an = fx.BatchAnalyser(C, WINDOW)
@@ -154,9 +160,10 @@ def main():
             an.rtp_configure("l24", [PER] * STREAMS)
             an.set_rtp_sources(np.arange(C), np.arange(C) // PER, np.arange(C) % PER)
             if name.startswith("rtp_w"):
-                an.rtp_set_window(int(name[5:]))
+                an.rtp_set_window(int(base(name)[5:]))
         return an, its
 
+    parent_lib = other_library(capi, args.parent) if args.parent else None
     ans = {name: analyser(name) for name in names}
 
     def one_pass(name):
@@ -168,7 +175,7 @@ def main():
         t0 = time.perf_counter()
         for k in range(TICKS):
             if name.startswith("rtp"):
-                d, ln, so, count = ticks[name][k]
+                d, ln, so, count = ticks[base(name)][k]
                 st = its.fx_push_rtp(an._h, vp(d) if count else None, ln.ctypes.data_as(ip), so.ctypes.data_as(ip), count, stride, N_TICK, capi.MEM_DEVICE, vp(raw), vp(sm), ctypes.byref(frames), None)
             elif name == "planar":
                 st = its.fx_push_samples(an._h, vp(planar), N_TICK, capi.SAMPLE_S24, capi.MEM_DEVICE, vp(raw), vp(sm), ctypes.byref(frames))
@@ -192,9 +199,10 @@ def main():
         assert int(stats["samples_missing"].sum()) == 0 and int(stats["packets"].sum()) == P * TICKS, name
         if name.startswith("rtp_w"):
             w = an.rtp_window()
-            counts = [t[3] for t in ticks[name]]
+            counts = [t[3] for t in ticks[base(name)]]
             assert int(w["held"].sum()) == 0 and int(w["recovered"].sum()) > 0
-            notes.append("  %s: datagrams per tick %d .. %d (first %d, last %d); %.1f %% of a pass's positions came out of the held state"
+            if name == base(name):
+                notes.append("  %s: datagrams per tick %d .. %d (first %d, last %d); %.1f %% of a pass's positions came out of the held state"
                          % (name, min(counts), max(counts), counts[0], counts[-1], 100.0 * int(w["recovered"].sum()) / (STREAMS * N_TICK * TICKS)))
     for name in names:                                    # warm-up
         one_pass(name)
@@ -207,11 +215,11 @@ def main():
              "%d datagrams of %d bytes (slot stride %d) a tick; %d-point context; %d ticks back to back per pass on the library's stream, device" % (P, int(lengths[0]), stride, WINDOW, TICKS),
              "buffers, one synchronisation per pass, the calls' passes alternated, %d passes each; us per tick, median (min - max):" % args.passes]
     for name in names:
-        lines.append("  %-12s %8.1f (%.1f - %.1f)" % (name, med[name], min(times[name]), max(times[name])))
+        lines.append("  %-16s %8.1f (%.1f - %.1f)" % (name, med[name], min(times[name]), max(times[name])))
     pairs = [("what the unpack adds (rtp - planar, pass by pass):", "rtp", "planar"),
-             ("what the de-interleave adds (interleaved - planar, pass by pass):", "interleaved", "planar"),
-             ("this build less the parent's (rtp - rtp_parent, pass by pass):", "rtp", "rtp_parent")]
+             ("what the de-interleave adds (interleaved - planar, pass by pass):", "interleaved", "planar")]
     pairs += [("what a window of %d adds (rtp_w%d - rtp, pass by pass):" % (w, w), "rtp_w%d" % w, "rtp") for w in windows]
+    pairs += [("this build less the parent's (%s - %s_parent, pass by pass):" % (n, n), n, n + "_parent") for n in paired]
     diff = {}
     for what, a, b in pairs:
         if a in times and b in times:
@@ -220,9 +228,10 @@ def main():
             lines.append("  %-66s %8.1f (%.1f - %.1f)" % (what, diff[(a, b)], min(d), max(d)))
     if ("interleaved", "planar") in diff and diff[("interleaved", "planar")] > 0:
         lines.append("  ratio of the two: %.2f   whole tick rtp / planar: %.3f" % (diff[("rtp", "planar")] / diff[("interleaved", "planar")], med["rtp"] / med["planar"]))
-    if "rtp_parent" in times and "rtp" in times:
-        lo, hi = min(times["rtp_parent"]), max(times["rtp_parent"])
-        lines.append("  W = 0 gate: this build's rtp median %.1f %s the parent's own spread %.1f - %.1f" % (med["rtp"], "lies inside" if lo <= med["rtp"] <= hi else "lies OUTSIDE", lo, hi))
+    for n in paired:                                      # the gate: the parent's own spread over its passes is what this measurement resolves
+        if n in times and n + "_parent" in times:
+            lo, hi = min(times[n + "_parent"]), max(times[n + "_parent"])
+            lines.append("  %s gate: this build's %s median %.1f %s the parent's own spread %.1f - %.1f" % ("W = 0" if n == "rtp" else n, n, med[n], "lies inside" if lo <= med[n] <= hi else "lies OUTSIDE (%s)" % ("below" if med[n] < lo else "above"), lo, hi))
     lines += notes
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
